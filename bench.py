@@ -17,9 +17,17 @@ torch.distributed (backend nccl = RCCL) carries the setup and the re-neighboring
 (or re-neighbor when an atom moved > skin/2), force evaluation through the C-ABI, ghost reverse
 comm, integrate.  Inputs are resident in HBM before the timed region.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (library HIP-event timing on
-the launch stream); `cpu_baseline` is the torch oracle (port of the libtorch reference path) timed
-on this box's host cores on a bounded sample (BASELINE configs[1], 10 648 atoms).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`, the stage times of the timed steps).  --full adds what takes work of its own:
+`roofline` for the dominant kernel (library HIP-event timing on the launch stream, plus one untimed
+evaluation for the edge count), the cost and cadence of re-neighboring (`value_with_amortised_rebuilds`),
+`cpu_baseline` -- the torch oracle (port of the libtorch reference path) timed on the host's cores on
+a bounded sample (BASELINE configs[1], 10 648 atoms) -- and `parity_vs_oracle` on that sample.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64): positions,
+velocities and forces by global atom id (all atoms up to 2^19, else a fixed seeded sample of 2^19 atom
+ids in ascending order), and the total potential energy and virial.  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -185,6 +193,35 @@ def spawn_ranks(n: int, budget_s: float = None) -> int:
     return rc
 
 
+DUMP_MAX_ATOMS = 1 << 19
+
+
+def dump_outputs(out_dir: str, sim, rank: int) -> None:
+    """--dump-outputs: what the last timed step hands its caller, as float64 DIR/<name>.npy -- positions, velocities and forces with one
+    row per global atom id (every atom up to DUMP_MAX_ATOMS, else a fixed seeded sample of that many ids in ascending order), the total
+    potential energy and the virial.  Collective over the ranks; rank 0 writes."""
+    import torch
+    n = sim.natoms_global
+    ids = np.arange(n) if n <= DUMP_MAX_ATOMS else np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ATOMS, replace=False))
+    row = torch.full((n,), -1, dtype=torch.int64, device=sim.dev)
+    row[torch.from_numpy(ids).to(sim.dev)] = torch.arange(len(ids), dtype=torch.int64, device=sim.dev)
+    nl = sim.nlocal
+    r = row[sim.tag[:nl]]
+    keep = r >= 0
+    buf = torch.zeros((len(ids), 9), dtype=torch.float64, device=sim.dev)
+    buf[r[keep]] = torch.cat([sim.x[:nl], sim.v[:nl], sim.f[:nl]], dim=1)[keep]
+    ev = sim.engvir.clone()
+    if sim.nranks > 1:
+        sim.dist.all_reduce(buf)
+        sim.dist.all_reduce(ev)
+    if rank != 0:
+        return
+    buf, ev = buf.cpu().numpy(), ev.cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("positions", buf[:, 0:3]), ("velocities", buf[:, 3:6]), ("forces", buf[:, 6:9]), ("energy", ev[0:1]), ("virial", ev[1:7])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -200,7 +237,11 @@ def main():
     ap.add_argument("--l-max", type=int, default=-1, help="override the model's l_max (e.g. 3 on config 2: a shape outside every fused kernel, i.e. a line of the layer-at-a-time path on an l_max = 3 model)")
     ap.add_argument("--eval-only", action="store_true", help="ablation runs only (timing builds that compute wrong forces): time force evaluations at fixed positions instead of NVE steps; the line is NOT a benchmark result")
     ap.add_argument("--force-overlap", action="store_true", help="overlapped three-range schedule even on one rank (A/B: what the schedule itself costs)")
+    ap.add_argument("--full", action="store_true", help="also measure the roofline, the re-neighboring cost and cadence, the CPU baseline and the parity against the oracle (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -339,33 +380,36 @@ def main():
         stage_max = {k: float(tmax[1 + i].item()) for i, k in enumerate(STAGES) if float(tmax[1 + i].item()) > 0.0}
     else:
         stage_max = dict(stage_sum)
-    # edges of this rank's centres: one un-timed evaluation of all of them in a single call (the timed calls do not read their counts back)
-    scratch_f = torch.zeros_like(sim.f)
-    scratch_ev = torch.zeros(7, dtype=torch.float64, device=device)
-    backend.compute(sim.x, sim.mtype, scratch_f, sim.nlocal, scratch_ev)
-    edges_rank0 = model.nedges()
-    slots_used, slots_total = model.tile_occupancy()
-    model.timings()
-    del scratch_f
-    th = sim.thermo(wl["masses"])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sim, rank)
     rebuilds_timed = sim.nrebuild - nrebuild0
-    # cost of one re-neighboring (migration, borders, cell list + neighbor table), measured outside the timed region: the metric counts
-    # amortised rebuilds; a short timed window may contain none
-    barrier()
-    tr0 = time.perf_counter()
-    sim.rebuild()
-    barrier()
-    rebuild_ms = 1e3 * (time.perf_counter() - tr0)
-    # ... and how often the run re-neighbors: when the timed window held no re-neighboring, the cadence is MEASURED on an untimed
-    # continuation of the same trajectory (up to 96 steps, until two re-neighborings have happened) and `value_with_amortised_rebuilds` prices it in
-    cadence_steps, cadence_rebuilds = 0, 0
-    if rebuilds_timed == 0 and not args.eval_only:
-        nr0 = sim.nrebuild
-        while cadence_steps < 96 and sim.nrebuild - nr0 < 2:
-            sim.step()
-            cadence_steps += 1
-        cadence_rebuilds = sim.nrebuild - nr0
+    th = sim.thermo(wl["masses"])
+    rebuild_ms, cadence_steps, cadence_rebuilds = None, 0, 0
+    if args.full:
+        # edges of this rank's centres: one un-timed evaluation of all of them in a single call (the timed calls do not read their counts back)
+        scratch_f = torch.zeros_like(sim.f)
+        scratch_ev = torch.zeros(7, dtype=torch.float64, device=device)
+        backend.compute(sim.x, sim.mtype, scratch_f, sim.nlocal, scratch_ev)
+        edges_rank0 = model.nedges()
+        slots_used, slots_total = model.tile_occupancy()
+        model.timings()
+        del scratch_f
+        # cost of one re-neighboring (migration, borders, cell list + neighbor table), measured outside the timed region: the metric counts
+        # amortised rebuilds; a short timed window may contain none
         barrier()
+        tr0 = time.perf_counter()
+        sim.rebuild()
+        barrier()
+        rebuild_ms = 1e3 * (time.perf_counter() - tr0)
+        # ... and how often the run re-neighbors: when the timed window held no re-neighboring, the cadence is MEASURED on an untimed
+        # continuation of the same trajectory (up to 96 steps, until two re-neighborings have happened) and `value_with_amortised_rebuilds` prices it in
+        if rebuilds_timed == 0 and not args.eval_only:
+            nr0 = sim.nrebuild
+            while cadence_steps < 96 and sim.nrebuild - nr0 < 2:
+                sim.step()
+                cadence_steps += 1
+            cadence_rebuilds = sim.nrebuild - nr0
+            barrier()
 
     if rank == 0:
         ms_per_step = 1e3 * dt / args.steps
@@ -393,12 +437,12 @@ def main():
         roof = None
         traffic, traffic_src, traffic_hash = None, None, None
         tj = os.path.join(ROOT, "profiles", "traffic.json")          # measured in separate --pmc passes (cannot be collected live)
-        if os.path.exists(tj) and world == 1:
+        if args.full and os.path.exists(tj) and world == 1:
             ent = json.load(open(tj)).get(f"config{args.config}:{used_path}:{natoms}")
             if ent:
                 traffic, traffic_src = ent["traffic_bytes_per_launch"], ent["source"]
                 traffic_hash = ent.get("kernel_hash")
-        if dom is not None:
+        if args.full and dom is not None:
             t_dom = stage_avg[dom] * 1e-3                       # seconds of the dominant kernel per step (all its launches: one evaluation of edges_rank0 edges)
             ach = flops_per_edge * edges_rank0 / t_dom / 1e12
             # Headline roof (north-star wording): the HBM roofline on SURVEY 8d's ALGORITHMIC bytes -- bytes function above x the edges one
@@ -459,13 +503,13 @@ def main():
         cpu = None
         max_df = None
         parity = None
-        if not args.no_cpu_baseline and world == 1:       # reported baseline: rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:       # reported baseline: rank 0 at N = 1 only
             cpu, parity = cpu_baseline_and_parity(lib, args.config, dev_index, args.cpu_sample_ncell, args.path)
             max_df = parity["max_abs_dF"]
         # the metric counts amortised re-neighborings: a timed window that held some has paid for them; one that held none is corrected with
         # the measured cost of one re-neighboring and the measured cadence of this trajectory
         value_amortised = value
-        if rebuilds_timed == 0 and cadence_rebuilds > 0:
+        if args.full and rebuilds_timed == 0 and cadence_rebuilds > 0:
             value_amortised = natoms / ((ms_per_step + rebuild_ms * cadence_rebuilds / cadence_steps) * 1e-3)
         out = {
             "metric": "atom_steps_per_sec" if not args.eval_only else "atom_evaluations_per_sec (ablation run, not the benchmark)", "value": round(value, 1), "unit": "atom-steps/s", "n_gpus": world,
@@ -473,7 +517,7 @@ def main():
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": DTYPE.get(used_path, "f32"), "data": "synthetic",
             "config": {"workload": f"{('BASELINE config ' + str(args.config)) if args.config <= 5 else 'extra config 6 (not in BASELINE.json)'}: {wl['name']}, r_max {cfg['r_max']} A + skin 1.0 A, NVE dt=1 fs",
                        "grid": "x".join(map(str, grid)), "kernel_path": used_path, "arith_note": model.arith_note, "rebuilds": sim.nrebuild,
-                       "rebuilds_in_timed_steps": rebuilds_timed, "rebuild_ms": round(rebuild_ms, 3),
+                       "rebuilds_in_timed_steps": rebuilds_timed, "rebuild_ms": (round(rebuild_ms, 3) if args.full else None),
                        "steps_per_rebuild": (round(args.steps / rebuilds_timed, 1) if rebuilds_timed else None),
                        "rebuild_cadence_measured": ({"steps": cadence_steps, "rebuilds": cadence_rebuilds} if cadence_steps else None),
                        "comm": "overlapped" if sim.overlap else "serial", "comm_autotune": autotune,
@@ -489,6 +533,12 @@ def main():
             "roofline": roof,
             "cpu_baseline": cpu,
         }
+        if not args.full:
+            # a plain run measured the headline only: what --full adds has no entry in its line
+            for k in ("rebuild_ms", "rebuild_cadence_measured"):
+                del out["config"][k]
+            for k in ("value_with_amortised_rebuilds", "max_abs_dF_vs_oracle", "parity_vs_oracle", "roofline", "cpu_baseline"):
+                del out[k]
         print(json.dumps(out), flush=True)
     model.close()
     if dist is not None:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-end evidence run (from the repo root on the GPU box): kernel trace + stats of the default bench, HBM-side
-# traffic of the fused kernel (separate --pmc passes), the plain bench line, the micro-benchmarks.
+# traffic of the fused kernel (separate --pmc passes), the bench line with --full, the micro-benchmarks.
 # Usage: pair_allegro_amd/tools/final_profile.sh <tag> ["bench.py arguments"]     (default: the default bench = config 4)
 tag=${1:-r01f}; bargs=${2:-}
 root=$(pwd)
@@ -26,5 +26,5 @@ for kern in ("k_fused", "k_build_edges"):
         print(kern, c, 'dispatches', len(v), 'avg', sum(v) / max(len(v), 1))
 PY
 tail -1 $out/trace.log | cut -c1-300
-python bench.py $bargs > $out/bench_default.json 2> $out/bench_default.err; tail -1 $out/bench_default.json
+python bench.py $bargs --full > $out/bench_default.json 2> $out/bench_default.err; tail -1 $out/bench_default.json
 find $out -name "*kernel_stats.csv" | head -2

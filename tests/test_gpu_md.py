@@ -125,17 +125,18 @@ def test_multi_rank_on_one_gpu(hip_lib, model_dir, tmp_path, world, port):
 
 
 @pytest.mark.parametrize("launcher", ["spawn", "torchrun"])
-def test_bench_two_ranks_on_one_gpu(launcher):
-    """`bench.py --gpus 2` end to end on a 1-GPU box (AHIP_BENCH_ONE_DEVICE=1: both ranks on cuda:0, messages staged through gloo):
+def test_bench_two_ranks_on_one_gpu(launcher, tmp_path):
+    """`bench.py --gpus 2 --full` end to end on a 1-GPU box (AHIP_BENCH_ONE_DEVICE=1: both ranks on cuda:0, messages staged through gloo):
     the rank start-up both ways the contract allows (bench.py's own spawn and `python -m torch.distributed.run`), the brick
-    decomposition, the overlapped schedule through the library's ghost exchange, max-over-ranks timing and the ONE JSON line of rank 0.
-    What it cannot cover is the RCCL communicator between two devices."""
+    decomposition, the overlapped schedule through the library's ghost exchange, max-over-ranks timing and the ONE JSON line of rank 0,
+    and --dump-outputs gathering every rank's atoms.  What it cannot cover is the RCCL communicator between two devices."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, AHIP_BENCH_ONE_DEVICE="1", OMP_NUM_THREADS="1", MASTER_ADDR="127.0.0.1")
-    args = ["--gpus", "2", "--config", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
+    dump = tmp_path / "outputs"
+    args = ["--gpus", "2", "--config", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--dump-outputs", str(dump)]
     if launcher == "spawn":
         args.append("--force-overlap")                 # the three-range schedule itself; the other launcher lets bench.py time both schedules and choose
         cmd = [sys.executable, os.path.join(root, "bench.py")] + args
@@ -161,6 +162,41 @@ def test_bench_two_ranks_on_one_gpu(launcher):
         assert at["overlapped_ms"] > 0 and at["serial_ms"] > 0 and at["chosen"] == d["config"]["comm"]
         assert at["chosen"] == ("overlapped" if at["overlapped_ms"] <= at["serial_ms"] else "serial")
     assert d["roofline"]["launches_per_step"] == (3 if d["config"]["comm"] == "overlapped" else 1)
+    out = {k: np.load(dump / f"{k}.npy") for k in ("positions", "velocities", "forces", "energy", "virial")}
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in out.values())
+    assert out["positions"].shape == out["velocities"].shape == out["forces"].shape == (10648, 3)
+    assert np.all(np.abs(out["forces"]).max(axis=1) > 0), "an atom of some rank is missing from the gathered outputs"
+    np.testing.assert_allclose(out["energy"][0] / 10648, d["config"]["pe_per_atom"], rtol=1e-12)
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): the headline line without the figures --full adds, and --dump-outputs writes what the last
+    timed step computed -- positions, velocities and forces by atom id, the potential energy and the virial -- as float64 arrays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "2", "--ncell", "6", "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout.decode()[-2000:]
+    d = json.loads(lines[0])
+    natoms = 1728
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["metric"] == "atom_steps_per_sec" and d["unit"] == "atom-steps/s"
+    assert d["higher_is_better"] is True and d["dtype"] and d["value"] > 0
+    assert abs(d["ms_per_step"] - 1e3 * natoms / d["value"]) <= 6e-4               # ms_per_step is rounded to 1 us
+    assert d["config"]["kernel_path"] in pc.FUSED_F32EQ and d["config"]["stage_ms_rank0"]["model_fused"] > 0
+    for k in ("roofline", "cpu_baseline", "parity_vs_oracle", "max_abs_dF_vs_oracle", "value_with_amortised_rebuilds"):
+        assert k not in d, k
+    out = {k: np.load(dump / f"{k}.npy") for k in ("positions", "velocities", "forces", "energy", "virial")}
+    assert all(a.dtype == np.float64 and np.all(np.isfinite(a)) for a in out.values())
+    assert out["positions"].shape == out["velocities"].shape == out["forces"].shape == (natoms, 3)
+    assert out["energy"].shape == (1,) and out["virial"].shape == (6,)
+    assert np.all(np.abs(out["forces"]).max(axis=1) > 0)
+    np.testing.assert_allclose(out["energy"][0] / natoms, d["config"]["pe_per_atom"], rtol=1e-12)
 
 def test_bench_fails_fast_when_a_rank_dies():
     """`bench.py --gpus 2`, rank 1 exits with status 17 after start-up (AHIP_BENCH_TEST_KILL_RANK): the parent must stop rank 0 -- which is
