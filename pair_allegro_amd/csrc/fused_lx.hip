@@ -413,6 +413,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
     if constexpr (AR == 3) {
       int bex;
       (void)frexpf(lds.scale[ti] * A.cenv, &bex);
+      bex = min(max(bex, -100), 100);         // a subnormal or huge scale (bex ~ -130 for 1e-39) would make one of 2^-bex, 2^bex inf: both stay finite and normal
       bsc = ldexpf(1.f, -bex);
       if (g == 0) lds.stage[0][s * STG_LD + D * 16] = ldexpf(1.f, bex);
     }

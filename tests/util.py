@@ -89,9 +89,8 @@ def run_pair(lib, model_path, cell, pos, types, lmp_names, skin=1.0, grid=(1, 1,
     return dict(forces=forces, eatom=eatom, pe=pe, virial=virial, edges=(i, j, d), info=info)
 
 
-def oracle_run(cfg, w, cell, pos, types, lmp_names, skin=1.0):
-    oracle = allegro_torch.build(cfg, w)
-    rs = lmp_like.build_rank_system(cell, pos, types, cfg["r_max"] + skin)
+def type_mapper_and_cutoffs(cfg, lmp_names):
+    """LAMMPS type -> model type index, and the [T][T] cutoff matrix over LAMMPS types (what the pair style hands the glue)."""
     model_types = cfg["type_names"]
     mapper = np.array([model_types.index(s) if s in model_types else -1 for s in lmp_names], dtype=np.int32)
     T = len(lmp_names)
@@ -101,6 +100,14 @@ def oracle_run(cfg, w, cell, pos, types, lmp_names, skin=1.0):
         for a in range(T):
             for b in range(T):
                 cm[a, b] = pc[mapper[a], mapper[b]]
+    return mapper, cm
+
+
+def oracle_run(cfg, w, cell, pos, types, lmp_names, skin=1.0, oracle=None):
+    """`oracle`: an already built (e.g. edited) allegro_torch module to evaluate instead of build(cfg, w)."""
+    oracle = allegro_torch.build(cfg, w) if oracle is None else oracle
+    rs = lmp_like.build_rank_system(cell, pos, types, cfg["r_max"] + skin)
+    mapper, cm = type_mapper_and_cutoffs(cfg, lmp_names)
     f = np.zeros_like(rs.x)
     ea = np.zeros(rs.nall)
     eng, vir, inp = glue.compute(oracle, rs.x, rs.type, rs.nlocal, rs.ilist, rs.numneigh, rs.firstneigh, mapper, cm, f, ea)
