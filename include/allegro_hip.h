@@ -175,10 +175,15 @@ long long ahip_last_list_size(ahip_model *m);
  * add_custom_output, pair_nequip_allegro.cpp:403-406,681-684; compute/compute_allegro.cpp:81,114,145 reads them).
  * Entries this model's graph returns: "atomic_energy" [nlocal+nghost] (ghosts carry only their per-type shift, as in the
  * TorchScript model), "forces" [nlocal+nghost][3] (this evaluation's forces, before they are added to f),
- * "virial" [3][3], "total_energy" [1] (sum of atomic_energy over locals AND ghosts, cf. compute/README.md).
+ * "virial" [3][3], "total_energy" [1] (sum of atomic_energy over locals AND ghosts, cf. compute/README.md), and this
+ * library's own "atomic_virial" [nlocal+nghost][9], the per-atom virial for a heat current:
+ *     W_j[a][b] = - sum over the edges e = (i -> j) with NEIGHBOUR j of r_e[a] * dE/dr_e[b],   r_e = x_j - x_i,  row-major a, b
+ * not symmetrised; ghost rows belong to their owners (reverse-communicate them: `compute ID all allegro/atom atomic_virial 9 1`);
+ * the symmetric part of the sum over all rows is "virial".  Only a registered "atomic_virial" allocates its [nall][9] device
+ * buffer and selects the model kernels' instances that produce it.
  * ahip_output_register: unknown names are accepted here and fail at the next ahip_compute, like the reference's
  * `output.at(name)`.  ahip_output_get copies the flattened tensor (capacity in doubles; *count = its length; pass out = NULL
- * to query the length).  Host-pointer ahip_compute only. */
+ * to query the length).  ahip_compute and ahip_compute_dev (not ahip_compute_dev_range). */
 int ahip_output_register(ahip_model *m, const char *name);
 int ahip_output_get(ahip_model *m, const char *name, double *out, long long capacity, long long *count);
 

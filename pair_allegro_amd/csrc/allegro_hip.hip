@@ -199,7 +199,7 @@ void ahip_model_free(ahip_model *m) {
   if (m->rcut_model_dev) (void)hipFree(m->rcut_model_dev);
   for (DevBuf *b : {&m->b_flagwork, &m->b_ilist, &m->b_nloff, &m->b_nlj, &m->b_x, &m->b_ftype, &m->b_mtype, &m->b_f, &m->b_eatom,
                     &m->b_engvir, &m->b_cutsq, &m->b_cnt, &m->b_eoff, &m->b_eii, &m->b_ej, &m->b_rvec, &m->b_ett, &m->b_partial,
-                    &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles})
+                    &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom})
     b->release();
   for (auto &t : m->slots) for (auto &e : t.ring) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (hipEvent_t e : m->f_events) (void)hipEventDestroy(e);
@@ -670,6 +670,8 @@ static void run_model(ahip_model *m, const ComputeArgs &a) {
 }
 static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   m->nedges = 0;
+  // W restarts with every dispatch: it always belongs to the evaluation whose forces reach f (self-check passes, ArithDegraded re-dispatch, float32 fallback)
+  if (a.vatom) AHIP_CHECK(hipMemsetAsync(a.vatom, 0, (size_t)(a.nlocal + a.nghost) * 9 * sizeof(double), a.stream));
   const bool f64 = (m->opt_precision == "float64") || (m->hm.model_dtype == "float64");
   // the 7 energy / virial sums start from zero: the single-pass edge build clears them in its first kernel, every other way here
   if (m->inum == 0 || f64) AHIP_CHECK(hipMemsetAsync(a.engvir, 0, 7 * sizeof(double), a.stream));
@@ -728,6 +730,27 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   m->last_path = "generic_f32";
 }
 
+// `compute allegro` names this model returns; "atomic_virial" [nall][9] is this library's own (no nequip key): the per-atom virial
+// W_j[a][b] = -sum over the edges e = (i -> j) of r_e[a] dE/dr_e[b], each edge owned by its NEIGHBOUR j (ghost rows reverse-communicated by the caller)
+static void check_output_names(const ahip_model *m) {
+  for (const std::string &nm : m->custom_names)
+    if (nm != "atomic_energy" && nm != "forces" && nm != "virial" && nm != "total_energy" && nm != "atomic_virial")
+      throw ArgError("model output '" + nm + "' not found (this model returns atomic_energy, forces, virial, total_energy, atomic_virial)");
+}
+static bool want_atomic_virial(const ahip_model *m) {
+  return std::find(m->custom_names.begin(), m->custom_names.end(), "atomic_virial") != m->custom_names.end();
+}
+static double *vatom_buffer(ahip_model *m, int nall) {
+  m->b_vatom.reserve((size_t)std::max(nall, 1) * 9 * sizeof(double));
+  return m->b_vatom.as<double>();
+}
+// after the stream has been synchronised
+static void store_atomic_virial(ahip_model *m, int nall) {
+  std::vector<double> &w = m->custom_out["atomic_virial"];
+  w.resize((size_t)nall * 9);
+  if (nall > 0) copy_d2h(w.data(), m->b_vatom.p, w.size() * sizeof(double));
+}
+
 // Page-locks a persistent host vector for as long as it keeps its storage: copies from / into pageable memory are staged by the runtime
 // and "asynchronous" in name only; the vectors of the host-pointer path only ever grow, so this registers once per growth.
 // resize_pinned: a growing resize frees the old storage, so the registration of that storage is dropped FIRST (unregistering a freed
@@ -769,10 +792,9 @@ int ahip_compute(ahip_model *m, int nlocal, int nghost, const double *x, const i
     if (virial) for (int k = 0; k < 6; ++k) virial[k] = 0;
     m->custom_out.clear();
     if (m->inum == 0) return;          // empty domain: nothing is stored (compute_allegro.cpp:106-112)
-    for (const std::string &nm : m->custom_names)                      // the reference's output.at(name) (:404-405)
-      if (nm != "atomic_energy" && nm != "forces" && nm != "virial" && nm != "total_energy")
-        throw ArgError("model output '" + nm + "' not found (this model returns atomic_energy, forces, virial, total_energy)");
+    check_output_names(m);                                             // the reference's output.at(name) (:404-405)
     const bool want_eatom = eatom != nullptr || !m->custom_names.empty();
+    double *vatom = want_atomic_virial(m) ? vatom_buffer(m, nall) : nullptr;
 
     // types: LAMMPS 1-based -> filter index (type-1) and model type (pair_nequip_allegro.cpp:576)
     unpin_if_growing(m, m->h_ftype, (size_t)nall); unpin_if_growing(m, m->h_mtype, (size_t)nall);
@@ -833,7 +855,7 @@ int ahip_compute(ahip_model *m, int nlocal, int nghost, const double *x, const i
 
     ComputeArgs a{nlocal, nghost, m->b_x.as<double>(), m->b_ftype.as<int>(), m->b_cutsq.as<double>(), ntypes,
                   m->b_mtype.as<int>(), m->b_f.as<double>(), want_eatom ? m->b_eatom.as<double>() : nullptr,
-                  m->b_engvir.as<double>(), s};
+                  m->b_engvir.as<double>(), s, vatom};
     run_model(m, a);
 
     // Order on the stream: the 7 energy / virial sums and an event (the kernel has finished once it fires: the float16-range alarm of THIS evaluation is
@@ -893,6 +915,7 @@ int ahip_compute(ahip_model *m, int nlocal, int nghost, const double *x, const i
         if (nm == "atomic_energy") m->custom_out[nm] = ae;
         else if (nm == "forces") m->custom_out[nm] = m->h_f;
         else if (nm == "total_energy") m->custom_out[nm] = {tot};
+        else if (nm == "atomic_virial") store_atomic_virial(m, nall);
         else m->custom_out[nm] = {ev[1], ev[4], ev[5], ev[4], ev[2], ev[6], ev[5], ev[6], ev[3]};    // [3][3] from xx yy zz xy xz yz
       }
     }
@@ -953,14 +976,13 @@ int ahip_compute_dev(ahip_model *m, int nlocal, int nghost, const double *x_dev,
       // pair_nequip_allegro_kokkos.cpp:342-344): evaluate into the library's own zeroed force / energy arrays, add them to the
       // caller's, and keep host copies of the named entries.  Costs two extra array passes and a read-back, only when a
       // compute is registered.
-      for (const std::string &nm : m->custom_names)
-        if (nm != "atomic_energy" && nm != "forces" && nm != "virial" && nm != "total_energy")
-          throw ArgError("model output '" + nm + "' not found (this model returns atomic_energy, forces, virial, total_energy)");
+      check_output_names(m);
+      double *vatom = want_atomic_virial(m) ? vatom_buffer(m, nall) : nullptr;
       m->b_f.reserve((size_t)std::max(nall, 1) * 3 * sizeof(double));
       m->b_eatom.reserve((size_t)std::max(nall, 1) * sizeof(double));
       AHIP_CHECK(hipMemsetAsync(m->b_f.p, 0, (size_t)nall * 3 * sizeof(double), s));
       AHIP_CHECK(hipMemsetAsync(m->b_eatom.p, 0, (size_t)nall * sizeof(double), s));
-      ComputeArgs a{nlocal, nghost, x_dev, mtype_dev, m->b_cutsq.as<double>(), T, mtype_dev, m->b_f.as<double>(), m->b_eatom.as<double>(), eng_vir_dev, s};
+      ComputeArgs a{nlocal, nghost, x_dev, mtype_dev, m->b_cutsq.as<double>(), T, mtype_dev, m->b_f.as<double>(), m->b_eatom.as<double>(), eng_vir_dev, s, vatom};
       run_model(m, a);
       const int inum = m->inum;
       if (nall > 0) hipLaunchKernelGGL(k_add_n, dim3((unsigned)((3LL * nall + 255) / 256)), dim3(256), 0, s, 3LL * nall, f_dev, m->b_f.as<double>());
@@ -986,6 +1008,7 @@ int ahip_compute_dev(ahip_model *m, int nlocal, int nghost, const double *x_dev,
         if (nm == "atomic_energy") m->custom_out[nm] = ae;
         else if (nm == "forces") m->custom_out[nm] = m->h_f;
         else if (nm == "total_energy") m->custom_out[nm] = {tot};
+        else if (nm == "atomic_virial") store_atomic_virial(m, nall);
         else m->custom_out[nm] = {ev[1], ev[4], ev[5], ev[4], ev[2], ev[6], ev[5], ev[6], ev[3]};
       }
     }

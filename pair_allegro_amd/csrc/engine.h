@@ -178,6 +178,7 @@ struct Model {
   // `compute allegro`: registered output names and their values from the last host-path compute
   std::vector<std::string> custom_names;
   std::map<std::string, std::vector<double>> custom_out;
+  DevBuf b_vatom;                           // "atomic_virial" [nall][9], allocated only while that output is registered
 
   // timings
   std::vector<TimingSlot> slots;
@@ -234,6 +235,7 @@ struct ComputeArgs {
   double *eatom;            // device [nall] or null
   double *engvir;           // device [7]
   hipStream_t stream;
+  double *vatom = nullptr;  // device [nall][9] or null: per-atom virial W_j[a][b] = -sum over edges e with NEIGHBOUR j of r_e[a] g_e[b] (output "atomic_virial"), accumulated
 };
 
 // ---- fused path entry points (fused.hip; the host-emulation test build links a stub) ---------

@@ -98,6 +98,7 @@ struct FusedArgs {
   float *dbg;                             // [E][8] per-edge diagnostics or null
   float cp[6];                            // cutoff polynomial: a, b, c of f = 1 - a x^p + b x^(p+1) - c x^(p+2) and a p, b (p + 1), c (p + 2) of its derivative (scalar registers, not per-lane values held over a tile)
   int *err;                               // host-mapped word: set when an edge gradient comes out non-finite (float16 range exceeded)
+  double *vatom;                          // [nall][9] per-atom virial (the VA instances only)
 };
 
 template <int NW, int NL = MAXNL> struct __attribute__((aligned(16))) Lds {
@@ -360,7 +361,8 @@ __device__ __forceinline__ void tile_fetch(const FusedArgs &A, int tile, int nti
   if (tid <= na) n.eoff = A.eoff[n.a0 + tid];
 }
 
-template <int NW, bool PROF, int AR, bool TBT, int NLT, int MD = 2>
+// VA: also the per-atom virial (output "atomic_virial"); instances launched only while that output is registered, so the default ones keep their code
+template <int NW, bool PROF, int AR, bool TBT, int NLT, int MD = 2, bool VA = false>
 __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   constexpr int NTHREADS = NW * 64, MAXA = Lds<NW>::MAXA;
   // f16x2 instances (round 5): the last hidden layer of the latent MLP saves its RAW pre-activation rows and the layer's output rows u are not saved at all: the backward
@@ -1014,6 +1016,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
         const float mine = lane == 0 ? w6[0] : lane == 1 ? w6[1] : lane == 2 ? w6[2] : lane == 3 ? w6[3] : lane == 4 ? w6[4] : w6[5];
         lds.virw[wave][lane] += (double)mine;
       }
+      if constexpr (VA) vatom_scatter(A.vatom, jat, g, valid, rx, ry, rz, gx, gy, gz);
     }
     // everything the finish derives from the thread index is formed here, from an opaque copy: computed once at kernel entry, those addresses lived
     // the whole tile in scratch and their reloads drained the in-order load queue
@@ -1080,13 +1083,14 @@ void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const 
 #endif
   hipLaunchKernelGGL((k_fused<AHIP_ASM_NW, false, 3, true, 2, 2>), dim3(grid), dim3(AHIP_ASM_NW * 64), 0, s, A);
 #else
-#define AHIP_LAUNCH_NL(NWV, PROFV, NLV, MDV) hipLaunchKernelGGL((k_fused<NWV, PROFV, 3, true, NLV, MDV>), dim3(grid), dim3(NWV * 64), 0, s, A)
-#define AHIP_LAUNCH(NWV, PROFV, MDV) do { if (A.NL == 1) AHIP_LAUNCH_NL(NWV, PROFV, 1, MDV); else if (A.NL == 2) AHIP_LAUNCH_NL(NWV, PROFV, 2, MDV); else AHIP_LAUNCH_NL(NWV, PROFV, 3, MDV); } while (0)
-#define AHIP_LAUNCH_NW(PROFV, MDV) do { if (nw == 4) AHIP_LAUNCH(4, PROFV, MDV); else AHIP_LAUNCH(8, PROFV, MDV); } while (0)
-  if (md == 1) AHIP_LAUNCH_NW(false, 1);
-  else if (md == 3) AHIP_LAUNCH_NW(false, 3);
-  else if (prof) AHIP_LAUNCH_NW(true, 2);
-  else AHIP_LAUNCH_NW(false, 2);
+#define AHIP_LAUNCH_NL(NWV, PROFV, NLV, MDV, VAV) hipLaunchKernelGGL((k_fused<NWV, PROFV, 3, true, NLV, MDV, VAV>), dim3(grid), dim3(NWV * 64), 0, s, A)
+#define AHIP_LAUNCH(NWV, PROFV, MDV, VAV) do { if (A.NL == 1) AHIP_LAUNCH_NL(NWV, PROFV, 1, MDV, VAV); else if (A.NL == 2) AHIP_LAUNCH_NL(NWV, PROFV, 2, MDV, VAV); else AHIP_LAUNCH_NL(NWV, PROFV, 3, MDV, VAV); } while (0)
+#define AHIP_LAUNCH_NW(PROFV, MDV, VAV) do { if (nw == 4) AHIP_LAUNCH(4, PROFV, MDV, VAV); else AHIP_LAUNCH(8, PROFV, MDV, VAV); } while (0)
+  if (A.vatom) { if (md == 1) AHIP_LAUNCH_NW(false, 1, true); else if (md == 3) AHIP_LAUNCH_NW(false, 3, true); else AHIP_LAUNCH_NW(false, 2, true); }    // "atomic_virial" (no profiling instance)
+  else if (md == 1) AHIP_LAUNCH_NW(false, 1, false);
+  else if (md == 3) AHIP_LAUNCH_NW(false, 3, false);
+  else if (prof) AHIP_LAUNCH_NW(true, 2, false);
+  else AHIP_LAUNCH_NW(false, 2, false);
 #undef AHIP_LAUNCH_NW
 #undef AHIP_LAUNCH
 #undef AHIP_LAUNCH_NL
@@ -1095,12 +1099,13 @@ void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const 
 #endif
 #if AHIP_FUSED_PART == 1
 void fused_launch_bf16(int nw, bool prof, int arith, bool tbt, int grid, hipStream_t s, const FusedArgs &A) {
-#define AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, NLV) hipLaunchKernelGGL((k_fused<NWV, PROFV, B3V, TBV, NLV>), dim3(grid), dim3(NWV * 64), 0, s, A)
-#define AHIP_LAUNCH(NWV, PROFV, B3V, TBV) do { if (A.NL == 1) AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, 1); else if (A.NL == 2) AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, 2); else AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, 3); } while (0)
-#define AHIP_LAUNCH_TB(NWV, PROFV, B3V) do { if (tbt) AHIP_LAUNCH(NWV, PROFV, B3V, true); else AHIP_LAUNCH(NWV, PROFV, B3V, false); } while (0)
-#define AHIP_LAUNCH_NW(PROFV, B3V) do { if (nw == 4) AHIP_LAUNCH_TB(4, PROFV, B3V); else AHIP_LAUNCH_TB(8, PROFV, B3V); } while (0)
-  if (prof) { if (arith == 1) AHIP_LAUNCH_NW(true, 1); else AHIP_LAUNCH_NW(true, 2); }
-  else { if (arith == 1) AHIP_LAUNCH_NW(false, 1); else AHIP_LAUNCH_NW(false, 2); }
+#define AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, NLV, VAV) hipLaunchKernelGGL((k_fused<NWV, PROFV, B3V, TBV, NLV, 2, VAV>), dim3(grid), dim3(NWV * 64), 0, s, A)
+#define AHIP_LAUNCH(NWV, PROFV, B3V, TBV, VAV) do { if (A.NL == 1) AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, 1, VAV); else if (A.NL == 2) AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, 2, VAV); else AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, 3, VAV); } while (0)
+#define AHIP_LAUNCH_TB(NWV, PROFV, B3V, VAV) do { if (tbt) AHIP_LAUNCH(NWV, PROFV, B3V, true, VAV); else AHIP_LAUNCH(NWV, PROFV, B3V, false, VAV); } while (0)
+#define AHIP_LAUNCH_NW(PROFV, B3V, VAV) do { if (nw == 4) AHIP_LAUNCH_TB(4, PROFV, B3V, VAV); else AHIP_LAUNCH_TB(8, PROFV, B3V, VAV); } while (0)
+  if (A.vatom) { if (arith == 1) AHIP_LAUNCH_NW(false, 1, true); else AHIP_LAUNCH_NW(false, 2, true); }    // "atomic_virial" (no profiling instance)
+  else if (prof) { if (arith == 1) AHIP_LAUNCH_NW(true, 1, false); else AHIP_LAUNCH_NW(true, 2, false); }
+  else { if (arith == 1) AHIP_LAUNCH_NW(false, 1, false); else AHIP_LAUNCH_NW(false, 2, false); }
 #undef AHIP_LAUNCH_NW
 #undef AHIP_LAUNCH_TB
 #undef AHIP_LAUNCH
@@ -1397,7 +1402,7 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
   A.tile_counter = (unsigned int *)(ntl + 1);
   A.maxdeg_sel = maxdeg_sel;
   m.d_ntiles_last = ntl; m.last_tile_slots = nw == 0 ? 0 : 16 * nw;
-  A.f = a.f; A.eatom = a.eatom; A.partial = st.partial.as<double>();
+  A.f = a.f; A.eatom = a.eatom; A.partial = st.partial.as<double>(); A.vatom = a.vatom;
   // edge total for the claim size below: the value itself when it is on the host, else the last one that was, else the list's size
   // scaled by the volume ratio of cutoff and list spheres at a skin of 1 A
   const long long nedges_est = !m.counts_pending ? m.nedges : m.nedges_hint > 0 ? m.nedges_hint : (long long)(0.58 * (double)m.nneigh);
@@ -1427,11 +1432,12 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
       if (const char *tc = std::getenv("AHIP_TCHUNK")) A.tchunk = std::max(1, std::atoi(tc));       // experiments
       if (st.arith == 3) { fused_launch_f16(shape, st.prof_on, st.md, g, s, A); continue; }                        // fused_h.o
       if (st.arith != 0) { fused_launch_bf16(shape, st.prof_on, st.arith, st.tbt, g, s, A); continue; }     // fused_bf.o
-#define AHIP_LAUNCH_NL(NWV, PROFV, TBV, NLV) hipLaunchKernelGGL((k_fused<NWV, PROFV, 0, TBV, NLV>), dim3(g), dim3(NWV * 64), 0, s, A)
-#define AHIP_LAUNCH(NWV, PROFV, TBV) do { if (A.NL == 1) AHIP_LAUNCH_NL(NWV, PROFV, TBV, 1); else if (A.NL == 2) AHIP_LAUNCH_NL(NWV, PROFV, TBV, 2); else AHIP_LAUNCH_NL(NWV, PROFV, TBV, 3); } while (0)
-#define AHIP_LAUNCH_TB(NWV, PROFV) do { if (st.tbt) AHIP_LAUNCH(NWV, PROFV, true); else AHIP_LAUNCH(NWV, PROFV, false); } while (0)
-#define AHIP_LAUNCH_NW(PROFV) do { if (shape == 4) AHIP_LAUNCH_TB(4, PROFV); else AHIP_LAUNCH_TB(8, PROFV); } while (0)
-      if (st.prof_on) AHIP_LAUNCH_NW(true); else AHIP_LAUNCH_NW(false);
+#define AHIP_LAUNCH_NL(NWV, PROFV, TBV, NLV, VAV) hipLaunchKernelGGL((k_fused<NWV, PROFV, 0, TBV, NLV, 2, VAV>), dim3(g), dim3(NWV * 64), 0, s, A)
+#define AHIP_LAUNCH(NWV, PROFV, TBV, VAV) do { if (A.NL == 1) AHIP_LAUNCH_NL(NWV, PROFV, TBV, 1, VAV); else if (A.NL == 2) AHIP_LAUNCH_NL(NWV, PROFV, TBV, 2, VAV); else AHIP_LAUNCH_NL(NWV, PROFV, TBV, 3, VAV); } while (0)
+#define AHIP_LAUNCH_TB(NWV, PROFV, VAV) do { if (st.tbt) AHIP_LAUNCH(NWV, PROFV, true, VAV); else AHIP_LAUNCH(NWV, PROFV, false, VAV); } while (0)
+#define AHIP_LAUNCH_NW(PROFV, VAV) do { if (shape == 4) AHIP_LAUNCH_TB(4, PROFV, VAV); else AHIP_LAUNCH_TB(8, PROFV, VAV); } while (0)
+      if (A.vatom) AHIP_LAUNCH_NW(false, true);               // "atomic_virial" (no profiling instance)
+      else if (st.prof_on) AHIP_LAUNCH_NW(true, false); else AHIP_LAUNCH_NW(false, false);
 #undef AHIP_LAUNCH_NW
 #undef AHIP_LAUNCH_TB
 #undef AHIP_LAUNCH

@@ -321,6 +321,25 @@ __device__ __forceinline__ float gsum(float v) {       // sum over the 4 lanes (
   return v;
 }
 
+// Per-atom virial (output "atomic_virial", instances with the template flag VA only): the 9 products -r[a] g[b] of one edge, in double, added to the row
+// W[jat] of its NEIGHBOUR.  The four lanes of an edge slot (groups g = lane >> 4) hold the same edge and, after gsum, the same gradient; group g adds the
+// row's components g and g + 4 (group 0 also component 8), so one wave-instruction writes 32 contiguous bytes of each of its 16 rows: 3 atomic
+// instructions per wave and edge slot instead of 9 with one lane per row.
+__device__ __forceinline__ void vatom_scatter(double *W, int jat, int g, bool valid, float rx, float ry, float rz, float gx, float gy, float gz) {
+  __builtin_amdgcn_sched_barrier(0);          // kept in place: the kernels around it sit at the register limit
+  if (valid) {
+  asm volatile("" : "+v"(g));                  // the lane-group selects below are formed here, not hoisted out of the tile loop
+  double *const w = W + 9 * (size_t)jat;
+  // component c = 3 a + b: g -> (0,0) (0,1) (0,2) (1,0); g + 4 -> (1,1) (1,2) (2,0) (2,1); 8 -> (2,2)
+  const float ra = g == 3 ? ry : rx, gb = g == 1 ? gy : g == 2 ? gz : gx;
+  const float ra2 = g < 2 ? ry : rz, gb2 = g == 1 ? gz : g == 2 ? gx : gy;
+  atomicAdd(&w[g], -(double)ra * (double)gb);
+  atomicAdd(&w[g + 4], -(double)ra2 * (double)gb2);
+  if (g == 0) atomicAdd(&w[8], -(double)rz * (double)gz);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
 
 // ---------------------------------------------------------------------------- tile packing
 // Greedy packing of consecutive centre atoms into tiles (<= tile_slots edges, <= maxa atoms), done

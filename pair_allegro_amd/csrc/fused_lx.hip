@@ -144,7 +144,8 @@ enum { PX_GEOM = 0, PX_EMB, PX_ENV, PX_TP, PX_LAT, PX_MIX, PX_OUT, PX_BLAT, PX_B
 // ---------------------------------------------------------------------------- the kernel
 // NLT = number of layers: the layer loops are unrolled so that `last layer` / `first layer` are compile-time facts -- with
 // run-time branches inside them the register allocator shuffles dozens of spill slots at every join (load, wait, store).
-template <int L, int UT, int NW, int NLT, bool PROF, int AR>
+// VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
+template <int L, int UT, int NW, int NLT, bool PROF, int AR, bool VA = false>
 __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
   using S = ShapeX<L, UT, NW>;
   constexpr int NTHREADS = NW * 64, D = S::D, U = S::U, EW = S::EW, MAXA = S::MAXA, STG_LD = S::STG_LD, ENVA = S::ENVA, NP = S::NP;
@@ -666,6 +667,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
           atomicAdd(&A.f[3 * (size_t)jat + 2], -(double)gz);
         }
       }
+      if constexpr (VA) vatom_scatter(A.vatom, jat, g, valid, rx, ry, rz, gx, gy, gz);
       float w6[6] = {-m * rx * gx, -m * ry * gy, -m * rz * gz, -m * 0.5f * (rx * gy + ry * gx),
                      -m * 0.5f * (rx * gz + rz * gx), -m * 0.5f * (ry * gz + rz * gy)};
 #pragma unroll
@@ -871,19 +873,23 @@ bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
   // claims of TCHUNK tiles amortise the counter's round trip; with few tiles per workgroup the last claim decides the makespan
   // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
   A.tchunk = (lx_nedges_estimate(m) / 64 > (long long)grid * 256) ? TCHUNK : 1;
-  A.f = a.f; A.eatom = a.eatom; A.partial = st.partial.as<double>();
+  A.f = a.f; A.eatom = a.eatom; A.partial = st.partial.as<double>(); A.vatom = a.vatom;
   {
     StageTimer tm(m, "model_fused", s);
-#define LX_LAUNCH(UTV, NLV, PROFV) do { if (st.arith == 3) hipLaunchKernelGGL((k_fused_lx<2, UTV, NW, NLV, PROFV, 3>), dim3(grid), dim3(NW * 64), 0, s, A); \
-                                        else hipLaunchKernelGGL((k_fused_lx<2, UTV, NW, NLV, PROFV, 0>), dim3(grid), dim3(NW * 64), 0, s, A); } while (0)
+#define LX_LAUNCH_VA(UTV, NLV, PROFV, VAV) do { if (st.arith == 3) hipLaunchKernelGGL((k_fused_lx<2, UTV, NW, NLV, PROFV, 3, VAV>), dim3(grid), dim3(NW * 64), 0, s, A); \
+                                        else hipLaunchKernelGGL((k_fused_lx<2, UTV, NW, NLV, PROFV, 0, VAV>), dim3(grid), dim3(NW * 64), 0, s, A); } while (0)
+#define LX_LAUNCH(UTV, NLV, PROFV) LX_LAUNCH_VA(UTV, NLV, PROFV, false)
 #define LX_LAUNCH_NL(UTV) do { if (A.NL == 3) LX_LAUNCH(UTV, 3, false); else if (A.NL == 2) LX_LAUNCH(UTV, 2, false); else LX_LAUNCH(UTV, 1, false); } while (0)
-    if (st.prof_on && A.NL == 3) {
+    if (A.vatom) {
+      if (A.NL == 3) LX_LAUNCH_VA(2, 3, false, true); else if (A.NL == 2) LX_LAUNCH_VA(2, 2, false, true); else LX_LAUNCH_VA(2, 1, false, true);
+    } else if (st.prof_on && A.NL == 3) {
       AHIP_CHECK(hipMemsetAsync(st.prof.p, 0, 64 * sizeof(long long), s));
       A.prof = st.prof.as<long long>();
       LX_LAUNCH(2, 3, true);
     } else LX_LAUNCH_NL(2);
 #undef LX_LAUNCH_NL
 #undef LX_LAUNCH
+#undef LX_LAUNCH_VA
   }
   AHIP_CHECK(hipGetLastError());
   AHIP_CHECK(prim_sum_columns_f64(m.prim, st.partial.as<double>(), grid, 7, a.engvir, s));

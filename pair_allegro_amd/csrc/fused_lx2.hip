@@ -206,7 +206,8 @@ enum { PP_GEOM = 0, PP_EMB, PP_ENV, PP_TP, PP_LAT, PP_MIX, PP_OUT, PP_BLAT, PP_B
 #define PHASEP(id) do { if (PROF) { long long _t = clock64(); pacc[id] += _t - tprev; tprev = _t; } } while (0)
 
 // ---------------------------------------------------------------------------- the kernel
-template <int NLT, bool PROF, int AR>
+// VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
+template <int NLT, bool PROF, int AR, bool VA = false>
 __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
   using S = ShapeP;
   constexpr int NTHREADS = 512, D = S::D, U = S::U, HT = S::HT, EWH = S::EWH, MAXA = S::MAXA, STG_LD = S::STG_LD, ENVA = S::ENVA, NP = S::NP, L = S::L;
@@ -744,6 +745,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
             atomicAdd(&A.f[3 * (size_t)jat + 2], -(double)gz);
           }
         }
+        if constexpr (VA) vatom_scatter(A.vatom, jat, g, valid, rx, ry, rz, gx, gy, gz);
         float w6[6] = {-m * rx * gx, -m * ry * gy, -m * rz * gz, -m * 0.5f * (rx * gy + ry * gx),
                        -m * 0.5f * (rx * gz + rz * gx), -m * 0.5f * (ry * gz + rz * gy)};
 #pragma unroll
@@ -935,13 +937,16 @@ bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
   A.e_tt = m.b_ett.as<unsigned char>(); A.rvec = m.b_rvec.as<float>(); A.rcut = m.rcut_model_dev;
   lx_tile_args(m, st, A, SLOTS, S::MAXA);
   A.tchunk = (lx_nedges_estimate(m) / SLOTS > (long long)grid * 256) ? TCHUNK : 1;
-  A.f = a.f; A.eatom = a.eatom; A.partial = st.partial.as<double>();
+  A.f = a.f; A.eatom = a.eatom; A.partial = st.partial.as<double>(); A.vatom = a.vatom;
   (void)inum;
   {
     StageTimer tm(m, "model_fused", s);
-#define LX2_LAUNCH(NLV, PROFV) do { if (st.arith == 3) hipLaunchKernelGGL((k_fused_lx2<NLV, PROFV, 3>), dim3(grid), dim3(NW * 64), 0, s, A); \
-                                    else hipLaunchKernelGGL((k_fused_lx2<NLV, PROFV, 0>), dim3(grid), dim3(NW * 64), 0, s, A); } while (0)
-    if (st.prof_on && A.NL == 3) {
+#define LX2_LAUNCH_VA(NLV, PROFV, VAV) do { if (st.arith == 3) hipLaunchKernelGGL((k_fused_lx2<NLV, PROFV, 3, VAV>), dim3(grid), dim3(NW * 64), 0, s, A); \
+                                    else hipLaunchKernelGGL((k_fused_lx2<NLV, PROFV, 0, VAV>), dim3(grid), dim3(NW * 64), 0, s, A); } while (0)
+#define LX2_LAUNCH(NLV, PROFV) LX2_LAUNCH_VA(NLV, PROFV, false)
+    if (A.vatom) {
+      if (A.NL == 3) LX2_LAUNCH_VA(3, false, true); else if (A.NL == 2) LX2_LAUNCH_VA(2, false, true); else LX2_LAUNCH_VA(1, false, true);
+    } else if (st.prof_on && A.NL == 3) {
       AHIP_CHECK(hipMemsetAsync(st.prof.p, 0, 64 * sizeof(long long), s));
       A.prof = st.prof.as<long long>();
       LX2_LAUNCH(3, true);
@@ -949,6 +954,7 @@ bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
     else if (A.NL == 2) LX2_LAUNCH(2, false);
     else LX2_LAUNCH(1, false);
 #undef LX2_LAUNCH
+#undef LX2_LAUNCH_VA
   }
   AHIP_CHECK(hipGetLastError());
   AHIP_CHECK(prim_sum_columns_f64(m.prim, st.partial.as<double>(), grid, 7, a.engvir, s));

@@ -46,6 +46,7 @@ struct FusedLxArgs {
   long long *prof;
   float cp[6];                            // cutoff polynomial coefficients (fused_common.h: cutoff_poly_c): wave-uniform kernel arguments instead of per-lane values held over a tile
   int *err;                               // host-mapped word: set when an edge gradient comes out non-finite (float16 range exceeded)
+  double *vatom;                          // [nall][9] per-atom virial (the VA instances only)
 };
 
 // Arithmetic of the wide kernels' streamed linears: AR = 0 the f32-input MFMA (linear_s), AR = 3 f16x2 (fused_h.h: linear_h, one edge group).  Both

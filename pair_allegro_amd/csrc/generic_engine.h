@@ -276,7 +276,7 @@ static void generic_chunk(Model &m, const ComputeArgs &a, Arena &A, int c0, int 
   T *g = A.get<T>(E * 3);
   RUN(k_geom_bwd<T>, Ec, s, Ec, gp, rvec, e_ii, e_j, m.d_ilist, a.mtype, m.rcut_model_dev, da, dfc, dY, g);
   RUN(k_readout<T>, nc, s, nc, c0, eoff, e0, m.d_ilist, a.mtype, e_j, rvec, eps, g, go ? W.get("scale") : nullptr,
-      go ? W.get("shift") : nullptr, cenv, a.f, a.eatom, m.b_partial.as<double>());
+      go ? W.get("shift") : nullptr, cenv, a.f, a.eatom, m.b_partial.as<double>(), a.vatom);
 #undef RUN
 }
 

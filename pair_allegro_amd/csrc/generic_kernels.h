@@ -474,7 +474,7 @@ __global__ void k_seed_deps(long long E, const int *e_ii, const int *ilist, cons
 template <typename T>
 __global__ void k_readout(int nc, int c0, const int *eoff, long long e0, const int *ilist, const int *mtype,
                           const int *e_j, const T *rvec, const T *eps, const T *g, const T *scale,
-                          const T *shift, T cE, double *f, double *eatom, double *partial /*[inum][7]*/) {
+                          const T *shift, T cE, double *f, double *eatom, double *partial /*[inum][7]*/, double *vatom /*[nall][9] or null*/) {
   long long c = AHIP_GID();
   if (c >= nc) return;
   int ii = c0 + (int)c;
@@ -489,6 +489,12 @@ __global__ void k_readout(int nc, int c0, const int *eoff, long long e0, const i
     atomicAdd(&f[3 * (long long)j], -gx);
     atomicAdd(&f[3 * (long long)j + 1], -gy);
     atomicAdd(&f[3 * (long long)j + 2], -gz);
+    if (vatom) {            // per-atom virial: the edge belongs to its neighbour j, W_j[a][b] -= r[a] g[b]
+      double *w = vatom + 9 * (long long)j;
+      const double r[3] = {rx, ry, rz}, gg[3] = {gx, gy, gz};
+      for (int p = 0; p < 3; ++p)
+        for (int q = 0; q < 3; ++q) atomicAdd(&w[3 * p + q], -r[p] * gg[q]);
+    }
     v0 -= rx * gx; v1 -= ry * gy; v2 -= rz * gz;
     v3 -= 0.5 * (rx * gy + ry * gx);
     v4 -= 0.5 * (rx * gz + rz * gx);
