@@ -155,12 +155,14 @@ bool alarm_take(Model &m) {
   if (m.h_alarm && *(volatile int *)m.h_alarm != 0) { *m.h_alarm = 0; return true; }
   return false;
 }
+// every fused kernel state of the model (weight streams are rebuilt on the next compute)
+static void free_fused_states(Model &m) { fused_free(m); fusedlx_free(m); }
 // fused_arith=auto falls back to the f32-input MFMA instances for the rest of this model's life (engine.h): the prepared f16x2 weight streams go, the next
 // dispatch prepares the f32 ones; said once on stderr and kept for ahip_arith_note
 static void arith_degrade(Model &m, const std::string &why) {
   m.arith_degraded = true;
   m.arith_note = "fused_arith=auto: float32 instance (f32-input MFMA) selected: " + why;
-  fused_free(m); fusedlx_free(m); fusedlx2_free(m);
+  free_fused_states(m);
   std::fprintf(stderr, "[allegro-hip] %s\n", m.arith_note.c_str());
 }
 // An alarm found at the START of an evaluation, or by an accessor, was raised by an EARLIER device-resident evaluation that nobody waited for: its forces were
@@ -187,9 +189,7 @@ void ahip_model_free(ahip_model *m) {
                                              "(float16 range exceeded); set fused_arith=f32\n");
     (void)hipHostFree(m->h_alarm); m->h_alarm = nullptr;
   }
-  fused_free(*m);
-  fusedlx_free(*m);
-  fusedlx2_free(*m);
+  free_fused_states(*m);
   neigh_free(*m);
   edges_free(*m);
   m->prim.release();
@@ -247,7 +247,7 @@ int ahip_set_option(ahip_model *m, const char *key, const char *value) {
       m->opt_precision = v;
     } else if (k == "fused_arith") {
       if (v != "bf16x3" && v != "f32" && v != "tf32eq" && v != "f16x2" && v != "auto") throw ArgError("option fused_arith: expected auto|f32|f16x2|bf16x3|tf32eq");
-      if (v != m->opt_fused_arith) { m->opt_fused_arith = v; fused_free(*m); fusedlx_free(*m); fusedlx2_free(*m); }     // weight streams are rebuilt on the next compute
+      if (v != m->opt_fused_arith) { m->opt_fused_arith = v; free_fused_states(*m); }
     } else if (k == "fused_tb") {
       if (v != "table" && v != "mlp") throw ArgError("option fused_tb: expected table|mlp");
       if (v != m->opt_fused_tb) { m->opt_fused_tb = v; fused_free(*m); }
@@ -584,6 +584,18 @@ static void heavy_generic(ahip_model *m, const ComputeArgs &a) {
   hipLaunchKernelGGL(k_add7, dim3(1), dim3(64), 0, a.stream, a.engvir, a2.engvir);
 }
 
+// The fused kernel family that serves the model: k_fused (l_max = 1), k_fused_lx (l_max = 2, 32 tensor features), k_fused_lx2 (64), or none (why: the
+// reasons of both).  Not cached: it depends on arith_force / arith_degraded (fused_model_supported: MLP depth 1 / 3 need f16x2), which the
+// self-check and an ArithDegraded fallback change.
+enum class FusedFamily { none, k_fused, lx32, lx64 };
+static FusedFamily fused_family(const Model &m, std::string *why) {
+  std::string why1, why2;
+  if (fused_model_supported(m, &why1)) return FusedFamily::k_fused;
+  if (fusedlx_model_supported(m, &why2)) return fused_UF(m.hm) == 64 ? FusedFamily::lx64 : FusedFamily::lx32;
+  if (why) *why = why1 + "; " + why2;
+  return FusedFamily::none;
+}
+
 static void run_model_once(ahip_model *m, const ComputeArgs &a);
 // dispatch with the auto fallback: a prepare step that finds the model outside the f16x2 split's reach (ArithDegraded) costs one more dispatch, on f32
 static void run_model_dispatch(ahip_model *m, const ComputeArgs &a) {
@@ -619,10 +631,10 @@ static void run_model_selfcheck(ahip_model *m, const ComputeArgs &a) {
   ComputeArgs a1 = a;
   a1.f = f32f; a1.eatom = nullptr; a1.engvir = ev;
   m->arith_force = 0;
-  fused_free(*m); fusedlx_free(*m); fusedlx2_free(*m);
-  try { run_model_dispatch(m, a1); } catch (...) { m->arith_force = -1; fused_free(*m); fusedlx_free(*m); fusedlx2_free(*m); throw; }
+  free_fused_states(*m);
+  try { run_model_dispatch(m, a1); } catch (...) { m->arith_force = -1; free_fused_states(*m); throw; }
   m->arith_force = -1;                       // (a shape without a float32 fused instance -- MLP depth 1 / 3 -- was just evaluated by the layer-at-a-time float32 kernels)
-  fused_free(*m); fusedlx_free(*m); fusedlx2_free(*m);
+  free_fused_states(*m);
   ComputeArgs a2 = a;
   a2.f = f16f;
   run_model_dispatch(m, a2);                 // (a prepare-time fallback inside lands on f32 as well: the comparison below is then trivially green)
@@ -661,7 +673,7 @@ static void run_model(ahip_model *m, const ComputeArgs &a) {
   fused_poll_alarm(*m);                      // raised by an EARLIER device-resident evaluation (nobody waits for those kernels)
   const bool f64 = (m->opt_precision == "float64") || (m->hm.model_dtype == "float64");
   const bool wants_check = !m->arith_checked && !m->arith_degraded && m->inum > 0 && !f64 && m->opt_path != "generic" && arith_option(*m) == "auto" &&
-                           !m->hm.allow_tf32 && (fused_model_supported(*m, nullptr) || fusedlx_model_supported(*m, nullptr)) &&
+                           !m->hm.allow_tf32 && fused_family(*m, nullptr) != FusedFamily::none &&
                            std::getenv("AHIP_NO_ARITH_SELFCHECK") == nullptr;
   if (wants_check) {
     run_model_selfcheck(m, a);
@@ -683,9 +695,12 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
     m->last_path = "generic_f64";
     return;
   }
+  std::string why;
+  const FusedFamily fam = m->opt_path == "generic" ? FusedFamily::none : fused_family(*m, &why);
+  const bool wide = fam == FusedFamily::lx32 || fam == FusedFamily::lx64;
   m->have_ett = false;
   m->nheavy = 0;
-  m->heavy_thresh = (m->opt_path != "generic" && !fused_model_supported(*m, nullptr) && fusedlx_model_supported(*m, nullptr)) ? 64 : 0;
+  m->heavy_thresh = wide ? LX_TILE_SLOTS : 0;
   // Tile packing rides on the edge build when the tile shape is known before it runs: k_fused with every list row <= 64 entries (4-wave tiles:
   // 64 slots, 6 centres), the wide kernels always (64 slots, 4 centres).  Otherwise (shape chosen on the device, two-pass edge build) the
   // stand-alone packing kernels run after it, as before.
@@ -693,9 +708,9 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   // ... and up to 262 144 centres per call: the packing runs on the scanning wave of every unit, i.e. serially inside the edge build, and costs there what
   // the stand-alone kernels cost beside it once they have a chip to spread over (1 M atoms: 0.062 vs 0.064 ms); below that the six launches they need are
   // the cost (10 648 atoms: 0.026 ms, 125 000: 0.056 ms, three times per step in the overlapped multi-rank schedule)
-  if (m->opt_path != "generic" && m->opt_tile_pack != "separate" && (m->inum <= 262144 || m->opt_tile_pack == "fused")) {
-    if (fused_model_supported(*m, nullptr)) { if (m->max_list_row >= 0 && m->max_list_row <= 64) { m->pack_slots = 64; m->pack_maxa = 6; } }
-    else if (fusedlx_model_supported(*m, nullptr)) { m->pack_slots = 64; m->pack_maxa = 4; }
+  if (m->opt_tile_pack != "separate" && (m->inum <= 262144 || m->opt_tile_pack == "fused")) {
+    if (fam == FusedFamily::k_fused) { if (m->max_list_row >= 0 && m->max_list_row <= FUSED_TILE_SLOTS) { m->pack_slots = FUSED_TILE_SLOTS; m->pack_maxa = FUSED_TILE_MAXA; } }
+    else if (wide) { m->pack_slots = LX_TILE_SLOTS; m->pack_maxa = LX_TILE_MAXA; }
   }
   m->tiles_packed = false;
   if (!edges_build_f32(*m, a)) { m->nheavy = 0; m->heavy_thresh = 0; AHIP_CHECK(hipMemsetAsync(a.engvir, 0, 7 * sizeof(double), a.stream)); build_edges<float>(*m, a); }
@@ -703,16 +718,12 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   static const bool edges_only = std::getenv("AHIP_EDGES_ONLY") != nullptr;     // timing experiments on the edge build alone
   if (edges_only) { m->last_path = "edges_only"; return; }
 #endif
-  std::string why;
   bool fused_ok = false;
   if (m->opt_path != "generic") {
     m->last_fused_arith = 0;
-    if (fused_model_supported(*m, &why)) fused_ok = fused_run(*m, a, &why);
-    else {
-      std::string why2;
-      if (fusedlx_model_supported(*m, &why2)) { fused_ok = fusedlx_run(*m, a, &why2); why = why2; }
-      else why += "; " + why2;
-    }
+    if (fam == FusedFamily::k_fused) fused_ok = fused_run(*m, a, &why);
+    else if (fam == FusedFamily::lx32) fused_ok = fusedlx_run(*m, a, &why);
+    else if (fam == FusedFamily::lx64) fused_ok = fusedlx2_run(*m, a, &why);
     if (!fused_ok && m->opt_path == "fused") throw UnsupportedError("fused path unavailable: " + why);
   }
   if (fused_ok) {
@@ -744,11 +755,26 @@ static double *vatom_buffer(ahip_model *m, int nall) {
   m->b_vatom.reserve((size_t)std::max(nall, 1) * 9 * sizeof(double));
   return m->b_vatom.as<double>();
 }
-// after the stream has been synchronised
-static void store_atomic_virial(ahip_model *m, int nall) {
-  std::vector<double> &w = m->custom_out["atomic_virial"];
-  w.resize((size_t)nall * 9);
-  if (nall > 0) copy_d2h(w.data(), m->b_vatom.p, w.size() * sizeof(double));
+// The `compute allegro` output table, i.e. the model's output dict entries (pair_nequip_allegro.cpp:403-406), rows for locals AND ghosts: from h_f,
+// h_eatom, h_mtype (host copies of this evaluation), b_vatom and ev[7] (energy, virial xx yy zz xy xz yz), after the stream has been synchronised.
+// ilist: the host centre list of the inum centres, or null for centres 0 .. inum - 1.
+static void store_custom_outputs(ahip_model *m, int nall, int inum, const int *ilist, const double *ev) {
+  std::vector<double> ae(nall);
+  const HostTensor &shift = m->hm.get("shift");
+  for (int i = 0; i < nall; ++i) ae[i] = shift.data[m->h_mtype[i]];        // ghosts: no centre edges -> shift only
+  for (int ii = 0; ii < inum; ++ii) { const int i = ilist ? ilist[ii] : ii; ae[i] = m->h_eatom[i]; }
+  double tot = 0;
+  for (double v : ae) tot += v;
+  for (const std::string &nm : m->custom_names) {
+    if (nm == "atomic_energy") m->custom_out[nm] = ae;
+    else if (nm == "forces") m->custom_out[nm] = m->h_f;
+    else if (nm == "total_energy") m->custom_out[nm] = {tot};
+    else if (nm == "atomic_virial") {
+      std::vector<double> &w = m->custom_out[nm];
+      w.resize((size_t)nall * 9);
+      if (nall > 0) copy_d2h(w.data(), m->b_vatom.p, w.size() * sizeof(double));
+    } else m->custom_out[nm] = {ev[1], ev[4], ev[5], ev[4], ev[2], ev[6], ev[5], ev[6], ev[3]};    // [3][3] from xx yy zz xy xz yz
+  }
 }
 
 // Page-locks a persistent host vector for as long as it keeps its storage: copies from / into pageable memory are staged by the runtime
@@ -903,22 +929,7 @@ int ahip_compute(ahip_model *m, int nlocal, int nghost, const double *x, const i
     }
     *eng = ev[0];
     if (virial) for (int k = 0; k < 6; ++k) virial[k] = ev[1 + k];
-    if (!m->custom_names.empty()) {
-      // the model's output dict entries (pair_nequip_allegro.cpp:403-406): rows for locals AND ghosts
-      std::vector<double> ae(nall);
-      const HostTensor &shift = m->hm.get("shift");
-      for (int i = 0; i < nall; ++i) ae[i] = shift.data[m->h_mtype[i]];        // ghosts: no centre edges -> shift only
-      for (int ii = 0; ii < m->inum; ++ii) { int i = m->h_ilist.empty() ? ii : m->h_ilist[ii]; ae[i] = m->h_eatom[i]; }
-      double tot = 0;
-      for (double v : ae) tot += v;
-      for (const std::string &nm : m->custom_names) {
-        if (nm == "atomic_energy") m->custom_out[nm] = ae;
-        else if (nm == "forces") m->custom_out[nm] = m->h_f;
-        else if (nm == "total_energy") m->custom_out[nm] = {tot};
-        else if (nm == "atomic_virial") store_atomic_virial(m, nall);
-        else m->custom_out[nm] = {ev[1], ev[4], ev[5], ev[4], ev[2], ev[6], ev[5], ev[6], ev[3]};    // [3][3] from xx yy zz xy xz yz
-      }
-    }
+    if (!m->custom_names.empty()) store_custom_outputs(m, nall, m->inum, m->h_ilist.empty() ? nullptr : m->h_ilist.data(), ev);
   });
 }
 
@@ -998,19 +1009,7 @@ int ahip_compute_dev(ahip_model *m, int nlocal, int nghost, const double *x_dev,
       copy_d2h(m->h_mtype.data(), mtype_dev, (size_t)nall * sizeof(int));
       if (inum > 0) copy_d2h(il.data(), m->d_ilist, (size_t)inum * sizeof(int));
       copy_d2h(ev, eng_vir_dev, 7 * sizeof(double));
-      std::vector<double> ae(nall);
-      const HostTensor &shift = m->hm.get("shift");
-      for (int i = 0; i < nall; ++i) ae[i] = shift.data[m->h_mtype[i]];        // ghosts: no centre edges -> shift only
-      for (int ii = 0; ii < inum; ++ii) ae[il[ii]] = m->h_eatom[il[ii]];
-      double tot = 0;
-      for (double v : ae) tot += v;
-      for (const std::string &nm : m->custom_names) {
-        if (nm == "atomic_energy") m->custom_out[nm] = ae;
-        else if (nm == "forces") m->custom_out[nm] = m->h_f;
-        else if (nm == "total_energy") m->custom_out[nm] = {tot};
-        else if (nm == "atomic_virial") store_atomic_virial(m, nall);
-        else m->custom_out[nm] = {ev[1], ev[4], ev[5], ev[4], ev[2], ev[6], ev[5], ev[6], ev[3]};
-      }
+      store_custom_outputs(m, nall, inum, il.data(), ev);
     }
   });
 }

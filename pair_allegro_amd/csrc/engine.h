@@ -91,6 +91,9 @@ struct TimingSlot {
 };
 static constexpr size_t TIMING_RING = 1024;
 
+struct FusedState;       // fused.hip
+struct FusedLxState;     // fused_lx_common.h
+
 struct Model {
   HostModel hm;
   int device = 0;
@@ -188,12 +191,12 @@ struct Model {
   // scratch of the device-wide primitives (scan, column sums): per model, see prims.h
   PrimScratch prim;
 
-  // fused path private state (fused.hip: model S shape; fused_lx.hip: l_max = 2 shapes)
+  // fused path private state (fused.hip: model S shape; fused_lx.hip / fused_lx2.hip: l_max = 2, 32 / 64 tensor features)
   std::vector<hipEvent_t> f_events;          // host-pointer path: one event per returned chunk of f (allegro_hip.hip: ahip_compute)
   int *h_alarm = nullptr;                    // page-locked, device-mapped word raised by the f16x2 instances of the fused kernels (fused_h.h): see alarm_word()
-  void *fused_state = nullptr;
-  void *fusedlx_state = nullptr;
-  void *fusedlx2_state = nullptr;            // wave-pair version of the 64-feature shape (fused_lx2.hip)
+  FusedState *fused_state = nullptr;
+  FusedLxState *fusedlx_state = nullptr;
+  FusedLxState *fusedlx2_state = nullptr;    // wave-pair version of the 64-feature shape (fused_lx2.hip)
 
   // neighbor builder state
   void *nb_state = nullptr;
@@ -245,6 +248,9 @@ bool fused_model_supported(const Model &m, std::string *why);
 // Returns false (and sets *why) if this particular list cannot be handled (e.g. too many edges per atom).
 bool fused_run(Model &m, const ComputeArgs &a, std::string *why);
 void fused_free(Model &m);
+// Tile shapes (edge slots, centres) the single-pass edge build packs for (allegro_hip.hip: run_model_once); the kernel files static_assert their own shapes against them
+inline constexpr int FUSED_TILE_SLOTS = 64, FUSED_TILE_MAXA = 6;     // k_fused, 4-wave tiles
+inline constexpr int LX_TILE_SLOTS = 64, LX_TILE_MAXA = 4;           // k_fused_lx and k_fused_lx2; also the edge count above which a centre is "heavy"
 // f16x2 arithmetic (fused_h.h): device address of the model's alarm word (allocated on first use); fused_poll_alarm throws StateError when a kernel has
 // raised it -- the host-pointer call polls behind its own synchronisation, device-resident callers meet it at their next evaluation
 int *alarm_word(Model &m);
@@ -305,13 +311,12 @@ inline void arith_range_verdict(const Model &m, int flags) {
 // f16x2 arithmetic: the backward pass is linear in its upstream gradient scale[type] / sqrt(avg_num_neighbors) and runs scaled by the power of two that brings that
 // gradient into [0.5, 1) -- PER CENTRE TYPE since round 6 (the kernels derive it from scale[t_i] with frexp: energy scales that differ by orders of magnitude
 // between species each get their own; one global power of two from the largest left the small species in float16's subnormals)
-// the same three for the wide shapes (l_max = 2; fused_lx.hip)
+// the same for the wide shapes (l_max = 2): 32 tensor features on k_fused_lx (fused_lx.hip), 64 on the wave-pair kernel k_fused_lx2 (fused_lx2.hip:
+// two waves per SIMD, each wave half of the channels); fusedlx_free releases the states of both
 bool fusedlx_model_supported(const Model &m, std::string *why);
 bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why);
-void fusedlx_free(Model &m);
-// wave-pair kernel for l_max = 2, 64 tensor features (fused_lx2.hip): two waves per SIMD, each wave half of the channels
 bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why);
-void fusedlx2_free(Model &m);
+void fusedlx_free(Model &m);
 
 // ---- single-pass float32 edge build (edges.hip; the host-emulation build links a stub returning false) ----
 // Fills m.nedges, m.last_max_deg, b_eoff/b_eii/b_ej/b_rvec exactly like build_edges<float>; false = a list

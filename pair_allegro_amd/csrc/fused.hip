@@ -1083,40 +1083,25 @@ void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const 
 #endif
   hipLaunchKernelGGL((k_fused<AHIP_ASM_NW, false, 3, true, 2, 2>), dim3(grid), dim3(AHIP_ASM_NW * 64), 0, s, A);
 #else
-#define AHIP_LAUNCH_NL(NWV, PROFV, NLV, MDV, VAV) hipLaunchKernelGGL((k_fused<NWV, PROFV, 3, true, NLV, MDV, VAV>), dim3(grid), dim3(NWV * 64), 0, s, A)
-#define AHIP_LAUNCH(NWV, PROFV, MDV, VAV) do { if (A.NL == 1) AHIP_LAUNCH_NL(NWV, PROFV, 1, MDV, VAV); else if (A.NL == 2) AHIP_LAUNCH_NL(NWV, PROFV, 2, MDV, VAV); else AHIP_LAUNCH_NL(NWV, PROFV, 3, MDV, VAV); } while (0)
-#define AHIP_LAUNCH_NW(PROFV, MDV, VAV) do { if (nw == 4) AHIP_LAUNCH(4, PROFV, MDV, VAV); else AHIP_LAUNCH(8, PROFV, MDV, VAV); } while (0)
-  if (A.vatom) { if (md == 1) AHIP_LAUNCH_NW(false, 1, true); else if (md == 3) AHIP_LAUNCH_NW(false, 3, true); else AHIP_LAUNCH_NW(false, 2, true); }    // "atomic_virial" (no profiling instance)
-  else if (md == 1) AHIP_LAUNCH_NW(false, 1, false);
-  else if (md == 3) AHIP_LAUNCH_NW(false, 3, false);
-  else if (prof) AHIP_LAUNCH_NW(true, 2, false);
-  else AHIP_LAUNCH_NW(false, 2, false);
-#undef AHIP_LAUNCH_NW
-#undef AHIP_LAUNCH
-#undef AHIP_LAUNCH_NL
+  dispatch<Choices<4, 8>, Choices<1, 2, 3>, Choices<1, 3, 2>, Variants>([&](auto nw, auto nl, auto md, auto var) {
+    if constexpr (var != VAR_PROF || md == 2) hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, 3, true, nl, md, var == VAR_VA>), dim3(grid), dim3(nw * 64), 0, s, A);
+  }, nw, A.NL, md, fused_variant(A.vatom, prof && md == 2));
 #endif
 }
 #endif
 #if AHIP_FUSED_PART == 1
 void fused_launch_bf16(int nw, bool prof, int arith, bool tbt, int grid, hipStream_t s, const FusedArgs &A) {
-#define AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, NLV, VAV) hipLaunchKernelGGL((k_fused<NWV, PROFV, B3V, TBV, NLV, 2, VAV>), dim3(grid), dim3(NWV * 64), 0, s, A)
-#define AHIP_LAUNCH(NWV, PROFV, B3V, TBV, VAV) do { if (A.NL == 1) AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, 1, VAV); else if (A.NL == 2) AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, 2, VAV); else AHIP_LAUNCH_NL(NWV, PROFV, B3V, TBV, 3, VAV); } while (0)
-#define AHIP_LAUNCH_TB(NWV, PROFV, B3V, VAV) do { if (tbt) AHIP_LAUNCH(NWV, PROFV, B3V, true, VAV); else AHIP_LAUNCH(NWV, PROFV, B3V, false, VAV); } while (0)
-#define AHIP_LAUNCH_NW(PROFV, B3V, VAV) do { if (nw == 4) AHIP_LAUNCH_TB(4, PROFV, B3V, VAV); else AHIP_LAUNCH_TB(8, PROFV, B3V, VAV); } while (0)
-  if (A.vatom) { if (arith == 1) AHIP_LAUNCH_NW(false, 1, true); else AHIP_LAUNCH_NW(false, 2, true); }    // "atomic_virial" (no profiling instance)
-  else if (prof) { if (arith == 1) AHIP_LAUNCH_NW(true, 1, false); else AHIP_LAUNCH_NW(true, 2, false); }
-  else { if (arith == 1) AHIP_LAUNCH_NW(false, 1, false); else AHIP_LAUNCH_NW(false, 2, false); }
-#undef AHIP_LAUNCH_NW
-#undef AHIP_LAUNCH_TB
-#undef AHIP_LAUNCH
-#undef AHIP_LAUNCH_NL
+  dispatch<Choices<4, 8>, Choices<1, 2>, Choices<1, 0>, Choices<1, 2, 3>, Variants>([&](auto nw, auto b3, auto tb, auto nl, auto var) {
+    hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, b3, tb != 0, nl, 2, var == VAR_VA>), dim3(grid), dim3(nw * 64), 0, s, A);
+  }, nw, arith, tbt, A.NL, fused_variant(A.vatom, prof));
 }
 #endif
 
 #if AHIP_FUSED_PART == 0
 // ---------------------------------------------------------------------------- host side
 struct FusedState {
-  DevBuf wbuf, scratch, seg_count, seg_base, tile_a0, tile_e0, centre, ntiles, partial;
+  DevBuf wbuf, scratch;
+  TileBufs tiles;
   FusedArgs args;
   bool ready = false, prof_on = false, dbg_on = false, clk_on = false;
   bool tbt = true;             // two-body embedding from the spline table (default) or evaluated as an MLP (option fused_tb=mlp)
@@ -1197,7 +1182,7 @@ bool fused_model_supported(const Model &m, std::string *why) {
 
 static void fused_prepare(Model &m) {
   if (!m.fused_state) m.fused_state = new FusedState();
-  FusedState &st = *(FusedState *)m.fused_state;
+  FusedState &st = *m.fused_state;
   if (st.ready) return;
   const HostModel &h = fused_host_model(m);          // the model at the kernel's fixed widths (zero-padded when it is narrower)
   const int T = h.num_types, NL = h.num_layers;
@@ -1325,9 +1310,9 @@ static void fused_prepare(Model &m) {
   A.wave_scratch = (long long)R_TOTAL(NL, MD) * ROW;
   st.scratch.reserve((size_t)st.ncu * 8 * A.wave_scratch * sizeof(float));
   A.scratch = st.scratch.as<float>();
-  st.partial.reserve((size_t)st.ncu * 2 * 7 * sizeof(double));
+  st.tiles.partial.reserve((size_t)st.ncu * 2 * 7 * sizeof(double));
   if (const char *nwe = std::getenv("AHIP_FUSED_NW")) st.force_nw = std::atoi(nwe);
-  st.ntiles.reserve(64);
+  st.tiles.ntiles.reserve(64);
   st.prof.reserve((64 + 4 * 2 * (size_t)st.ncu) * sizeof(long long));
   const char *pe = std::getenv("AHIP_FUSED_PROF");
   st.prof_on = pe && pe[0] == '1';
@@ -1344,7 +1329,7 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
   // at once, ~3 us); only lists with longer rows (two-pass edge build, counts read back there) take the decision on the host.
   if (m.edges_T_size != 4) { if (why) *why = "edge vectors are not float32"; return false; }
   fused_prepare(m);
-  FusedState &st = *(FusedState *)m.fused_state;
+  FusedState &st = *m.fused_state;
   if (st.prof_on || st.clk_on || st.dbg_on) edges_counts(m);      // instrumented runs size their buffers / reports from the counts
   int nw = 0;                                   // 0: decided on the device
   if (!m.counts_pending) {
@@ -1359,58 +1344,17 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
   const int *maxdeg_sel = nw == 0 ? m.d_maxdeg : nullptr;
   m.last_fused_arith = st.arith;
   hipStream_t s = a.stream;
-  const int inum = m.inum;
   const int tile_slots = nw == 8 ? 128 : 64, maxa = nw == 8 ? Lds<8>::MAXA : Lds<4>::MAXA;      // nw == 0: the packing kernels widen them themselves
-  const int nseg = (inum + SEG - 1) / SEG;
-  st.seg_count.reserve((size_t)(nseg + 1) * sizeof(int));
-  st.seg_base.reserve((size_t)(nseg + 2) * sizeof(int));
-  st.tile_a0.reserve((size_t)(inum + nseg + 2) * sizeof(int));
-  st.tile_e0.reserve((size_t)(inum + nseg + 2) * sizeof(int));
-  static_assert(Lds<4>::MAXA == 6, "allegro_hip.hip requests the 4-wave tile shape as 64 slots / 6 centres");
-  const bool prepacked = m.tiles_packed && nw == 4 && m.pack_slots == tile_slots && m.pack_maxa == maxa;      // the edge build packed the tiles (edges.hip)
-  if (!prepacked) {
-    StageTimer tm(m, "tile_pack", s);
-    const unsigned B = 64;
-    st.centre.reserve((size_t)std::max(inum, 1) * sizeof(int2));
-    const bool small = inum <= PACK_SMALL_ATOMS;
-    if (small)
-      hipLaunchKernelGGL(k_pack_small, dim3(1), dim3(PACK_SMALL_SEGS), 0, s, inum, m.b_eoff.as<int>(), nseg, st.tile_a0.as<int>(), st.tile_e0.as<int>(), st.ntiles.as<int>(), tile_slots, maxa,
-                         m.d_ilist, a.mtype, st.centre.as<int2>(), maxdeg_sel);
-    else {
-      hipLaunchKernelGGL(k_pack_tiles<false>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, st.seg_count.as<int>(), (const int *)nullptr, (int *)nullptr, tile_slots, maxa, maxdeg_sel);
-      AHIP_CHECK(prim_exclusive_scan_i32(m.prim, st.seg_count.as<int>(), st.seg_base.as<int>(), nseg, s));
-      hipLaunchKernelGGL(k_pack_tiles<true>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, (int *)nullptr, st.seg_base.as<int>(), st.tile_a0.as<int>(), tile_slots, maxa, maxdeg_sel);
-      hipLaunchKernelGGL(k_pack_finish, dim3(1), dim3(1), 0, s, inum, nseg, st.seg_base.as<int>(), st.tile_a0.as<int>(), st.ntiles.as<int>());
-      hipLaunchKernelGGL(k_centre_info, dim3((inum + 255) / 256), dim3(256), 0, s, inum, m.d_ilist, a.mtype, st.centre.as<int2>());
-    }
-    if (!m.have_ett) {            // two-pass edge build: its counts are on the host
-      m.b_ett.reserve((size_t)std::max<long long>(m.nedges, 1));
-      hipLaunchKernelGGL(k_edge_types, dim3((unsigned)((m.nedges + 255) / 256)), dim3(256), 0, s, m.nedges, m.b_eii.as<int>(), m.b_ej.as<int>(), m.d_ilist, a.mtype, m.b_ett.as<unsigned char>());
-      m.have_ett = true;
-    }
-    if (!small) {
-      const int tcap = inum + nseg + 1;              // upper bound on tiles + 1
-      hipLaunchKernelGGL(k_tile_e0, dim3((tcap + 255) / 256), dim3(256), 0, s, st.ntiles.as<int>(), st.tile_a0.as<int>(), m.b_eoff.as<int>(), st.tile_e0.as<int>());
-    }
-  }
+  static_assert(Lds<4>::MAXA == FUSED_TILE_MAXA && FUSED_TILE_SLOTS == 64, "allegro_hip.hip requests the 4-wave tile shape from the edge build");
   FusedArgs A = st.args;
-  A.eoff = m.b_eoff.as<int>(); A.e_ii = m.b_eii.as<int>(); A.e_j = m.b_ej.as<int>();
-  A.e_tt = m.b_ett.as<unsigned char>(); A.rvec = m.b_rvec.as<float>(); A.rcut = m.rcut_model_dev;
-  int *const ntl = prepacked ? m.b_ntiles.as<int>() : st.ntiles.as<int>();
-  A.centre = prepacked ? m.b_centre.as<int2>() : st.centre.as<int2>();
-  A.tile_a0 = prepacked ? m.b_tile_a0.as<int>() : st.tile_a0.as<int>(); A.tile_e0 = prepacked ? m.b_tile_e0.as<int>() : st.tile_e0.as<int>(); A.ntiles = ntl;
-  A.tile_counter = (unsigned int *)(ntl + 1);
+  fused_tile_args(m, st.tiles, a, A, tile_slots, maxa, maxdeg_sel, nw == 4);       // (the edge build packs 4-wave tiles only)
   A.maxdeg_sel = maxdeg_sel;
-  m.d_ntiles_last = ntl; m.last_tile_slots = nw == 0 ? 0 : 16 * nw;
-  A.f = a.f; A.eatom = a.eatom; A.partial = st.partial.as<double>(); A.vatom = a.vatom;
-  // edge total for the claim size below: the value itself when it is on the host, else the last one that was, else the list's size
-  // scaled by the volume ratio of cutoff and list spheres at a skin of 1 A
-  const long long nedges_est = !m.counts_pending ? m.nedges : m.nedges_hint > 0 ? m.nedges_hint : (long long)(0.58 * (double)m.nneigh);
+  const long long nedges_est = fused_nedges_estimate(m);
   // persistent workgroups fill every CU; reserve_wgs leaves a few slots free so that the exchange kernels of another stream
   // (ghost pack / unpack, RCCL send / recv) can be scheduled while this kernel runs (md.py, overlapped schedule)
   const int grid4 = std::max(1, st.ncu * 2 - m.reserve_wgs), grid8 = std::max(1, st.ncu - m.reserve_wgs);
   const int grid = nw == 8 ? grid8 : grid4;     // rows of `partial` that are summed
-  if (nw == 0) AHIP_CHECK(hipMemsetAsync(st.partial.p, 0, (size_t)grid * 7 * sizeof(double), s));     // the shape that returns at once writes nothing
+  if (nw == 0) AHIP_CHECK(hipMemsetAsync(st.tiles.partial.p, 0, (size_t)grid * 7 * sizeof(double), s));     // the shape that returns at once writes nothing
   {
     StageTimer tm(m, "model_fused", s);
     if (st.dbg_on) {
@@ -1432,20 +1376,13 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
       if (const char *tc = std::getenv("AHIP_TCHUNK")) A.tchunk = std::max(1, std::atoi(tc));       // experiments
       if (st.arith == 3) { fused_launch_f16(shape, st.prof_on, st.md, g, s, A); continue; }                        // fused_h.o
       if (st.arith != 0) { fused_launch_bf16(shape, st.prof_on, st.arith, st.tbt, g, s, A); continue; }     // fused_bf.o
-#define AHIP_LAUNCH_NL(NWV, PROFV, TBV, NLV, VAV) hipLaunchKernelGGL((k_fused<NWV, PROFV, 0, TBV, NLV, 2, VAV>), dim3(g), dim3(NWV * 64), 0, s, A)
-#define AHIP_LAUNCH(NWV, PROFV, TBV, VAV) do { if (A.NL == 1) AHIP_LAUNCH_NL(NWV, PROFV, TBV, 1, VAV); else if (A.NL == 2) AHIP_LAUNCH_NL(NWV, PROFV, TBV, 2, VAV); else AHIP_LAUNCH_NL(NWV, PROFV, TBV, 3, VAV); } while (0)
-#define AHIP_LAUNCH_TB(NWV, PROFV, VAV) do { if (st.tbt) AHIP_LAUNCH(NWV, PROFV, true, VAV); else AHIP_LAUNCH(NWV, PROFV, false, VAV); } while (0)
-#define AHIP_LAUNCH_NW(PROFV, VAV) do { if (shape == 4) AHIP_LAUNCH_TB(4, PROFV, VAV); else AHIP_LAUNCH_TB(8, PROFV, VAV); } while (0)
-      if (A.vatom) AHIP_LAUNCH_NW(false, true);               // "atomic_virial" (no profiling instance)
-      else if (st.prof_on) AHIP_LAUNCH_NW(true, false); else AHIP_LAUNCH_NW(false, false);
-#undef AHIP_LAUNCH_NW
-#undef AHIP_LAUNCH_TB
-#undef AHIP_LAUNCH
-#undef AHIP_LAUNCH_NL
+      dispatch<Choices<4, 8>, Choices<1, 0>, Choices<1, 2, 3>, Variants>([&](auto nw, auto tb, auto nl, auto var) {
+        hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, 0, tb != 0, nl, 2, var == VAR_VA>), dim3(g), dim3(nw * 64), 0, s, A);
+      }, shape, st.tbt, A.NL, fused_variant(A.vatom, st.prof_on));
     }
   }
   AHIP_CHECK(hipGetLastError());
-  AHIP_CHECK(prim_sum_columns_f64(m.prim, st.partial.as<double>(), grid, 7, a.engvir, s));
+  AHIP_CHECK(prim_sum_columns_f64(m.prim, st.tiles.partial.as<double>(), grid, 7, a.engvir, s));
   if (st.prof_on || st.clk_on) {
     std::vector<long long> hp(PH_N + 4 * (size_t)grid);
     AHIP_CHECK(hipMemcpyAsync(hp.data(), st.prof.p, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
@@ -1487,8 +1424,9 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
 
 void fused_free(Model &m) {
   if (!m.fused_state) return;
-  FusedState *st = (FusedState *)m.fused_state;
-  for (DevBuf *b : {&st->wbuf, &st->scratch, &st->seg_count, &st->seg_base, &st->tile_a0, &st->tile_e0, &st->centre, &st->ntiles, &st->partial, &st->prof, &st->dbg}) b->release();
+  FusedState *st = m.fused_state;
+  for (DevBuf *b : {&st->wbuf, &st->scratch, &st->prof, &st->dbg}) b->release();
+  st->tiles.release();
   delete st;
   m.fused_state = nullptr;
 }
@@ -1587,7 +1525,7 @@ using namespace ahip;
 extern "C" int ahip_debug_fused_edges(ahip_model *mh, float *out, long long nedges) {
   ahip::Model *m = (ahip::Model *)mh;
   if (!m || !m->fused_state) return AHIP_ERR_STATE;
-  FusedState &st = *(FusedState *)m->fused_state;
+  FusedState &st = *m->fused_state;
   if (!st.dbg_on || !st.dbg.p || nedges != m->nedges) return AHIP_ERR_STATE;
   if (hipDeviceSynchronize() != hipSuccess) return AHIP_ERR_DEVICE;
   try { copy_d2h(out, st.dbg.p, (size_t)nedges * 8 * sizeof(float)); } catch (...) { return AHIP_ERR_DEVICE; }

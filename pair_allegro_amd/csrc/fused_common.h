@@ -1,14 +1,17 @@
-// Pieces shared by the fused MFMA kernels (fused.hip: model S, l_max = 1, 32 tensor features; fused_lx.hip: l_max <= 2,
-// 32 or 64 tensor features): register-image rows, the streamed register-chain linear with its epilogue functors, the
-// A-operand fragment layout of the weight stream, tile packing.  See fused.hip / DESIGN.md 4.2 for the mapping.
+// Pieces shared by the fused MFMA kernels (fused.hip: model S, l_max = 1, 32 tensor features; fused_lx.hip / fused_lx2.hip: l_max = 2,
+// 32 / 64 tensor features): register-image rows, the streamed register-chain linear with its epilogue functors, the
+// A-operand fragment layout of the weight stream, tile packing, instance dispatch.  See fused.hip / DESIGN.md 4.2 for the mapping.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "engine.h"
+#include "prims.h"
 
 namespace ahip {
 
@@ -478,6 +481,90 @@ static __global__ void k_tile_e0(const int *ntiles, const int *tile_a0, const in
   int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t <= *ntiles) tile_e0[t] = eoff[tile_a0[t]];
 }
+
+// Host side of the tile packing, shared by every fused kernel family: the stand-alone packing kernels' buffers and the per-workgroup
+// energy / virial partial sums of one kernel state
+struct TileBufs {
+  DevBuf seg_count, seg_base, tile_a0, tile_e0, centre, ntiles, partial;
+  void release() { for (DevBuf *b : {&seg_count, &seg_base, &tile_a0, &tile_e0, &centre, &ntiles, &partial}) b->release(); }
+};
+// edge total for the claim-size heuristic: the value itself when it is on the host, else the last one that was, else the list's size
+// scaled by the volume ratio of cutoff and list spheres at a skin of 1 A
+static long long fused_nedges_estimate(const Model &m) {
+  return !m.counts_pending ? m.nedges : m.nedges_hint > 0 ? m.nedges_hint : (long long)(0.58 * (double)m.nneigh);
+}
+// Packs the tiles unless the edge build already did at this shape (edges.hip; can_prepack: the caller's shape admits it) -- consecutive centres into
+// tiles of <= slots edges and <= maxa centres (k_pack_tiles), per-centre {atom, type}, per-edge packed types, first edge of every tile -- and points
+// A's edge, tile and output fields at the result.  maxdeg_sel (k_fused): device word of the largest degree, from which the packing kernels widen the shape themselves.
+template <class Args>
+static void fused_tile_args(Model &m, TileBufs &tb, const ComputeArgs &a, Args &A, int slots, int maxa, const int *maxdeg_sel = nullptr, bool can_prepack = true) {
+  const bool pre = can_prepack && m.tiles_packed && m.pack_slots == slots && m.pack_maxa == maxa;
+  hipStream_t s = a.stream;
+  const int inum = m.inum;
+  if (!pre) {
+    const int nseg = (inum + SEG - 1) / SEG;
+    tb.seg_count.reserve((size_t)(nseg + 1) * sizeof(int));
+    tb.seg_base.reserve((size_t)(nseg + 2) * sizeof(int));
+    tb.tile_a0.reserve((size_t)(inum + nseg + 2) * sizeof(int));
+    tb.tile_e0.reserve((size_t)(inum + nseg + 2) * sizeof(int));
+    StageTimer tm(m, "tile_pack", s);
+    const unsigned B = 64;
+    tb.centre.reserve((size_t)std::max(inum, 1) * sizeof(int2));
+    const bool small = inum <= PACK_SMALL_ATOMS;
+    if (small)
+      hipLaunchKernelGGL(k_pack_small, dim3(1), dim3(PACK_SMALL_SEGS), 0, s, inum, m.b_eoff.as<int>(), nseg, tb.tile_a0.as<int>(), tb.tile_e0.as<int>(), tb.ntiles.as<int>(), slots, maxa,
+                         m.d_ilist, a.mtype, tb.centre.as<int2>(), maxdeg_sel);
+    else {
+      hipLaunchKernelGGL(k_pack_tiles<false>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, tb.seg_count.as<int>(), (const int *)nullptr, (int *)nullptr, slots, maxa, maxdeg_sel);
+      AHIP_CHECK(prim_exclusive_scan_i32(m.prim, tb.seg_count.as<int>(), tb.seg_base.as<int>(), nseg, s));
+      hipLaunchKernelGGL(k_pack_tiles<true>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, (int *)nullptr, tb.seg_base.as<int>(), tb.tile_a0.as<int>(), slots, maxa, maxdeg_sel);
+      hipLaunchKernelGGL(k_pack_finish, dim3(1), dim3(1), 0, s, inum, nseg, tb.seg_base.as<int>(), tb.tile_a0.as<int>(), tb.ntiles.as<int>());
+      hipLaunchKernelGGL(k_centre_info, dim3((inum + 255) / 256), dim3(256), 0, s, inum, m.d_ilist, a.mtype, tb.centre.as<int2>());
+    }
+    if (!m.have_ett) {            // two-pass edge build: its counts are on the host
+      m.b_ett.reserve((size_t)std::max<long long>(m.nedges, 1));
+      hipLaunchKernelGGL(k_edge_types, dim3((unsigned)((m.nedges + 255) / 256)), dim3(256), 0, s, m.nedges, m.b_eii.as<int>(), m.b_ej.as<int>(), m.d_ilist, a.mtype, m.b_ett.as<unsigned char>());
+      m.have_ett = true;
+    }
+    if (!small) {
+      const int tcap = inum + nseg + 1;              // upper bound on tiles + 1
+      hipLaunchKernelGGL(k_tile_e0, dim3((tcap + 255) / 256), dim3(256), 0, s, tb.ntiles.as<int>(), tb.tile_a0.as<int>(), m.b_eoff.as<int>(), tb.tile_e0.as<int>());
+    }
+  }
+  A.eoff = m.b_eoff.as<int>(); A.e_ii = m.b_eii.as<int>(); A.e_j = m.b_ej.as<int>();
+  A.e_tt = m.b_ett.as<unsigned char>(); A.rvec = m.b_rvec.as<float>(); A.rcut = m.rcut_model_dev;
+  int *const ntl = pre ? m.b_ntiles.as<int>() : tb.ntiles.as<int>();
+  A.centre = pre ? m.b_centre.as<int2>() : tb.centre.as<int2>();
+  A.tile_a0 = pre ? m.b_tile_a0.as<int>() : tb.tile_a0.as<int>(); A.tile_e0 = pre ? m.b_tile_e0.as<int>() : tb.tile_e0.as<int>(); A.ntiles = ntl;
+  A.tile_counter = (unsigned int *)(ntl + 1);
+  m.d_ntiles_last = ntl; m.last_tile_slots = maxdeg_sel ? 0 : slots;
+  A.f = a.f; A.eatom = a.eatom; A.partial = tb.partial.as<double>(); A.vatom = a.vatom;
+}
+
+// ---- instance dispatch (host side) ----
+// dispatch<Choices<4, 8>, Choices<1, 2, 3>>(f, nw, nl) calls f(std::integral_constant<int, NW>{}, std::integral_constant<int, NL>{}): every run-time value
+// becomes the template argument equal to it (the LAST choice when none is), so a kernel instance exists exactly for what the choice lists name.
+template <int... Vs> struct Choices {};
+template <class... Sets> struct Dispatch;
+template <> struct Dispatch<> {
+  template <class F, class... C> static void run(F &f, const int *, C... c) { f(c...); }
+};
+template <int V, int... Vs, class... Rest> struct Dispatch<Choices<V, Vs...>, Rest...> {
+  template <class F, class... C> static void run(F &f, const int *v, C... c) {
+    if constexpr (sizeof...(Vs) == 0) Dispatch<Rest...>::run(f, v + 1, c..., std::integral_constant<int, V>{});
+    else if (*v == V) Dispatch<Rest...>::run(f, v + 1, c..., std::integral_constant<int, V>{});
+    else Dispatch<Choices<Vs...>, Rest...>::run(f, v, c...);
+  }
+};
+template <class... Sets, class F, class... I> static void dispatch(F &&f, I... v) {
+  static_assert(sizeof...(Sets) == sizeof...(I), "one run-time value per choice list");
+  const int vals[] = {(int)v...};
+  Dispatch<Sets...>::run(f, vals);
+}
+// instrumentation variant of a fused kernel instance: plain, phase-profiled, or with the per-atom virial (output "atomic_virial"; no profiled twin)
+enum { VAR_PLAIN = 0, VAR_PROF = 1, VAR_VA = 2 };
+using Variants = Choices<VAR_VA, VAR_PROF, VAR_PLAIN>;
+static inline int fused_variant(bool vatom, bool prof) { return vatom ? VAR_VA : prof ? VAR_PROF : VAR_PLAIN; }
 
 // Fragment tiling of a [K][N] linear: KT input tiles x NT output tiles of 16 features; NT is padded to
 // even (tile pairs), and a single-input-tile linear is padded to KT = 2 so that it consumes 8 fragments.

@@ -1,6 +1,5 @@
-// Fused MFMA path for the wider Allegro shapes: l_max = 1 or 2, 32 or 64 tensor features (BASELINE config 5's model L:
-// l_max = 2, U = 64, 3 layers; the reference test YAML's shape: l_max = 2, U = 32, 3 layers,
-// /root/reference/tests/test_data/test_repro_allegro.yaml:89-99).  Same mapping as fused.hip (one launch = forward + analytic
+// Fused MFMA path for the wider Allegro shape l_max = 2 with 32 tensor features (the reference test YAML's shape: l_max = 2, U = 32, 3 layers,
+// /root/reference/tests/test_data/test_repro_allegro.yaml:89-99; 64 tensor features, BASELINE config 5's model L, run on k_fused_lx2, fused_lx2.hip).  Same mapping as fused.hip (one launch = forward + analytic
 // backward, every per-edge vector in the v_mfma_f32_16x16x4_f32 C/D layout, weights as one A-fragment stream in consumption
 // order, per-centre reductions through LDS, saved rows in a per-wave scratch) with what the larger state forces:
 //
@@ -33,8 +32,9 @@
 
 namespace ahip {
 
-// Shapes of one instantiation
-template <int L, int UT, int NW> struct ShapeX {
+// The shape of k_fused_lx: l_max = 2, 2 16-feature tiles (32 tensor features), 4 waves
+struct ShapeX {
+  static constexpr int L = 2, UT = 2, NW = 4;
   static constexpr int D = (L + 1) * (L + 1), NLP = L + 1, U = 16 * UT, EW = NLP * UT;   // EW: 16-feature tiles of an (l, u) weight vector
   static constexpr int SLOTS = 16 * NW;
   static constexpr int MAXA = 4;                        // centre atoms per tile (LDS budget of the environment rows)
@@ -48,8 +48,9 @@ template <int L, int UT, int NW> struct ShapeX {
   static constexpr int O_OM = 0, O_Z1 = EW, O_Z2 = EW + 4, O_U = EW + 8, O_VIN = EW + 12;
 };
 
-template <int L, int UT, int NW> struct __attribute__((aligned(16))) LdsX {
-  using S = ShapeX<L, UT, NW>;
+struct __attribute__((aligned(16))) LdsX {
+  using S = ShapeX;
+  static constexpr int NW = S::NW;
   float stage[2][S::SLOTS * S::STG_LD];
   float env[LX_MAXNL][S::MAXA * S::ENVA];
   float denv[S::MAXA * S::ENVA];
@@ -67,15 +68,15 @@ template <int L, int UT, int NW> struct __attribute__((aligned(16))) LdsX {
   static constexpr int NLROW = 14;
   float rowsl[NW][NLROW * ROW];
 };
-static_assert(sizeof(LdsX<2, 2, 4>) <= 160 * 1024, "LDS budget of one CU");
+static_assert(sizeof(LdsX) <= 160 * 1024, "LDS budget of one CU");
 
 
 // Per-centre sum of one staged K-tile: env[a][lm][16 t + f] = scale * sum_{slots of a} stage[slot][lm][f].
 // Work item = (centre, 4-feature column); its LPI adjacent lanes take every LPI-th slot with 16-byte LDS reads (all of a lane's reads
 // are in flight together) and combine with log2(LPI) cross-lane adds -- a fixed order, so the sums are reproducible.
-template <int L, int UT, int NW>
 __device__ __forceinline__ void reduce_stage_x(const float *stg, const int *aoff, float *dst, int na, float scale, int t, int uwave) {
-  using S = ShapeX<L, UT, NW>;
+  using S = ShapeX;
+  constexpr int NW = S::NW;
   constexpr int LPI = 4;                    // lanes per work item: 36 columns x 4 lanes = one round for a tile that holds one centre
   constexpr int NC = S::D * 4, PER_ROUND = NW * 64 / LPI, NRD = S::SLOTS / LPI;
   // lane -> (item, part): part = lane / 16, item = 16 * wave + lane % 16.  The 16 lanes of one 16-byte LDS read phase then hold 16
@@ -145,15 +146,16 @@ enum { PX_GEOM = 0, PX_EMB, PX_ENV, PX_TP, PX_LAT, PX_MIX, PX_OUT, PX_BLAT, PX_B
 // NLT = number of layers: the layer loops are unrolled so that `last layer` / `first layer` are compile-time facts -- with
 // run-time branches inside them the register allocator shuffles dozens of spill slots at every join (load, wait, store).
 // VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
-template <int L, int UT, int NW, int NLT, bool PROF, int AR, bool VA = false>
-__global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
-  using S = ShapeX<L, UT, NW>;
+template <int NLT, bool PROF, int AR, bool VA = false>
+__global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) {
+  constexpr int L = ShapeX::L, UT = ShapeX::UT, NW = ShapeX::NW;
+  using S = ShapeX;
   constexpr int NTHREADS = NW * 64, D = S::D, U = S::U, EW = S::EW, MAXA = S::MAXA, STG_LD = S::STG_LD, ENVA = S::ENVA, NP = S::NP;
   constexpr bool SAVEZ = AR == 3;          // f16x2: raw pre-activation rows of the last hidden layer instead of silu' rows, no u rows (see fused.hip)
   // last-layer rows in LDS (LdsX::rowsl, stage[0] images): LDS rows [0, NOML) = omega l >= 1, [NOML, NLROW) = the first NVL rows of the input tensor
-  constexpr int NLROW = LdsX<L, UT, NW>::NLROW, NOML = L * UT, NVL = (NLROW - NOML) < D * UT ? (NLROW - NOML) : D * UT;
+  constexpr int NLROW = LdsX::NLROW, NOML = L * UT, NVL = (NLROW - NOML) < D * UT ? (NLROW - NOML) : D * UT;
   static_assert(NOML <= NLROW, "omega rows of the last layer fit the LDS rows");
-  __shared__ LdsX<L, UT, NW> lds;
+  __shared__ LdsX lds;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
   const int v16 = lane * 16;
@@ -298,7 +300,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
 #pragma unroll
           for (int lm = 0; lm < D; ++lm) *(f32x4 *)(sp + lm * 16) = lm == 0 ? om[t] : om[l_of_lm(lm) * UT + t] * Y[lm];
           __syncthreads();
-          reduce_stage_x<L, UT, NW>(lds.stage[t & 1], aoffp, envk, na, A.cenv, t, uwave);
+          reduce_stage_x(lds.stage[t & 1], aoffp, envk, na, A.cenv, t, uwave);
           __builtin_amdgcn_sched_barrier(0);
         }
 #endif
@@ -560,7 +562,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
             } else load_rows<L * UT>(SB, RL + S::O_OM + UT, omall, v16);
           }
           __syncthreads();
-          reduce_stage_x<L, UT, NW>(lds.stage[t & 1], aoffp, lds.denv, na, A.cenv, t, uwave);
+          reduce_stage_x(lds.stage[t & 1], aoffp, lds.denv, na, A.cenv, t, uwave);
           __builtin_amdgcn_sched_barrier(0);
         }
         __syncthreads();
@@ -729,37 +731,33 @@ bool fusedlx_model_supported(const Model &m, std::string *why) {
   return true;
 }
 
-template <int L, int UT> static void fusedlx_prepare_t(Model &m, FusedLxState &st) {
-  using S = ShapeX<L, UT, 4>;
-  const HostModel &h = fused_host_model(m);          // at the kernel's fixed widths (zero-padded when the model is narrower)
-  const int T = h.num_types, NL = h.num_layers, U = S::U, D = S::D;
-  std::vector<float> w;
-  FusedLxArgs &A = st.args;
-  std::memset(&A, 0, sizeof(A));
-  auto mark = [&]() { while (w.size() % 64) w.push_back(0.f); return (int)w.size(); };
+// k_fused_lx's weight stream, in the order one tile consumes it: whole-matrix fragments (see k_fused_lx)
+static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, int arith) {
+  using S = ShapeX;
+  constexpr int L = S::L, U = S::U, D = S::D;
+  const int NL = h.num_layers;
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
-  st.arith = lx_arith_of(m);
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
   auto frag = [&](const double *W, int K, int N, int ldw) {
-    if (st.arith == 3) h_flags |= append_frag_h(w, W, K, N, ldw);
+    if (arith == 3) h_flags |= append_frag_h(w, W, K, N, ldw);
     else append_frag(w, W, K, N, ldw);
   };
   auto fwd = [&](const double *W, int K, int N) { frag(W, K, N, N); };
   auto bwd = [&](const double *W, int K, int N) { auto t = transpose(W, K, N); frag(t.data(), N, K, K); };
-  // one channel-mixing row; with 32 features the last row is padded to 64 output columns (8 fragments, see mix_rows)
+  // one channel-mixing row; the last (ninth) row is padded to 64 output columns (8 fragments, see mix_rows)
+  static_assert(S::UT == 2 && D % 2 == 1, "rows alternate the ring phase");
   auto mixfrag = [&](const double *Wl, int lm, bool transposed) {
     std::vector<double> m2((size_t)U * U);
     for (int a = 0; a < U; ++a)
       for (int b = 0; b < U; ++b) m2[(size_t)a * U + b] = transposed ? Wl[(size_t)b * U + a] : Wl[(size_t)a * U + b];
-    if (UT == 2 && lm == D - 1 && (D % 2) == 1) {
+    if (lm == D - 1) {
       std::vector<double> pad((size_t)U * 2 * U, 0.0);
       for (int a = 0; a < U; ++a)
         for (int b = 0; b < U; ++b) pad[(size_t)a * 2 * U + b] = m2[(size_t)a * U + b];
       frag(pad.data(), U, 2 * U, 2 * U);
     } else frag(m2.data(), U, U, U);
   };
-  // ---- the weight stream, in the order one tile consumes it (see k_fused_lx) ----
-  A.o_stream = mark();
+  A.o_stream = lx_mark(w);
   const size_t stream0 = w.size();
   fwd(T_("emb.w"), 64, U * (L + 1));
   for (int k = 0; k < NL; ++k) {
@@ -788,131 +786,25 @@ template <int L, int UT> static void fusedlx_prepare_t(Model &m, FusedLxState &s
   }
   bwd(T_("emb.w"), 64, U * (L + 1));
   for (size_t i = 0; i < (size_t)RING * 256; ++i) w.push_back(w[stream0 + i]);      // wrap-around copy
-  // two-body table
-  A.tb_nk = 512;
-  A.o_tbtab = mark();
-  append_two_body_table(w, h, m.rcut_model_host, A.tb_nk);
-  // small tables: path weights (last layer: only the scalar paths, the rest zero)
-  A.o_tpl = mark();
-  for (int k = 0; k < NL; ++k) {
-    const HostTensor &tp = h.get("l" + std::to_string(k + 1) + ".tp");
-    for (int p = 0; p < S::NP; ++p)
-      for (int u = 0; u < U; ++u) w.push_back(p < tp.shape[0] ? (float)tp.data[(size_t)p * U + u] : 0.f);
-  }
-  for (int k = 0; k < NL; ++k) {
-    const HostTensor &res = h.get("l" + std::to_string(k + 1) + ".res");
-    A.o_res[k] = mark(); w.push_back((float)res.data[0]); w.push_back((float)res.data[1]);
-  }
-  A.o_out1 = mark(); for (int u = 0; u < 32; ++u) w.push_back((float)h.get("out.w1").data[u]);
-  A.o_scale = mark(); for (int t = 0; t < T; ++t) w.push_back((float)h.get("scale").data[t]);
-  A.o_shift = mark(); for (int t = 0; t < T; ++t) w.push_back((float)h.get("shift").data[t]);
-  mark();
-  st.wbuf.reserve(w.size() * sizeof(float));
-  copy_h2d(st.wbuf.p, w.data(), w.size() * sizeof(float));       // staged: see engine.h
-  A.wbase = st.wbuf.as<float>();
-  A.wbytes = (int)(w.size() * sizeof(float));
-  A.T = T; A.NL = NL; A.p = h.poly_p;
-  A.cenv = (float)(1.0 / std::sqrt(h.avg_num_neighbors));
-  {
-    const float pf = (float)h.poly_p, ca = 0.5f * (pf + 1) * (pf + 2), cb = pf * (pf + 2), cc = 0.5f * pf * (pf + 1);      // the expressions of cutoff_poly
-    A.cp[0] = ca; A.cp[1] = cb; A.cp[2] = cc; A.cp[3] = ca * pf; A.cp[4] = cb * (pf + 1); A.cp[5] = cc * (pf + 2);
-  }
-  if (st.arith == 3) {
-    arith_range_verdict(m, h_flags);                 // auto: ArithDegraded (run_model falls back to the f32 instance); explicit f16x2: an overflow is an error
-    A.err = alarm_word(m);
-  }
-  A.wave_scratch = (long long)S::R_TOTAL(NL) * ROW;
-}
-
-static void fusedlx_prepare(Model &m) {
-  if (!m.fusedlx_state) m.fusedlx_state = new FusedLxState();
-  FusedLxState &st = *(FusedLxState *)m.fusedlx_state;
-  if (st.ready) return;
-  st.L = m.hm.l_max; st.UT = fused_UF(m.hm) / 16;
-  fusedlx_prepare_t<2, 2>(m, st);
-  hipDeviceProp_t prop;
-  AHIP_CHECK(hipGetDeviceProperties(&prop, m.device));
-  st.ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  st.scratch.reserve((size_t)st.ncu * 4 * st.args.wave_scratch * sizeof(float));
-  st.args.scratch = st.scratch.as<float>();
-  st.partial.reserve((size_t)st.ncu * 7 * sizeof(double));
-  st.ntiles.reserve(64);
-  st.prof.reserve(64 * sizeof(long long));
-  const char *pe = std::getenv("AHIP_FUSED_PROF");
-  st.prof_on = pe && pe[0] == '1';
-  st.ready = true;
+  return h_flags;
 }
 
 bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
-  constexpr int NW = 4, SLOTS = 16 * NW;
-  // (counts still in flight = single-pass edge build with heavy_thresh = SLOTS: every centre with more edges is listed, gets a tile of its own that the
-  // kernel skips, and is evaluated by heavy_generic after the kernel has been enqueued -- the host reads the counts only then)
-  if (!m.counts_pending && m.last_max_deg > SLOTS && (m.heavy_thresh != SLOTS || (long long)m.nheavy * 8 > m.inum)) {
-    // centres with more than 64 edges are listed by the edge build and evaluated by the layer-at-a-time kernels; when the edge
-    // build did not list them (two-pass fallback) or they are not a small minority, the whole system goes that way
-    if (why) *why = "an atom has " + std::to_string(m.last_max_deg) + " edges (> " + std::to_string(SLOTS) + " per tile of the wide fused kernel)";
-    return false;
-  }
-  if (m.edges_T_size != 4) { if (why) *why = "edge vectors are not float32"; return false; }
-  if (fused_UF(m.hm) == 64) {
-    return fusedlx2_run(m, a, why);          // 64 tensor features: the wave-pair kernel (fused_lx2.hip)
-  }
-  fusedlx_prepare(m);
-  FusedLxState &st = *(FusedLxState *)m.fusedlx_state;
-  m.last_fused_arith = st.arith;
-  hipStream_t s = a.stream;
-  const int inum = m.inum;
-  const int maxa = ShapeX<2, 4, NW>::MAXA;
-  const int grid = std::max(1, st.ncu - (m.reserve_wgs + 1) / 2);      // see fused.hip: slots left free for the exchange kernels
-  lx_pack_tiles(m, st, a, SLOTS, maxa);
-  FusedLxArgs A = st.args;
-  A.wg_scratch = NW * A.wave_scratch;
-  A.eoff = m.b_eoff.as<int>(); A.e_ii = m.b_eii.as<int>(); A.e_j = m.b_ej.as<int>();
-  A.e_tt = m.b_ett.as<unsigned char>(); A.rvec = m.b_rvec.as<float>(); A.rcut = m.rcut_model_dev;
-  lx_tile_args(m, st, A, SLOTS, maxa);
-  // claims of TCHUNK tiles amortise the counter's round trip; with few tiles per workgroup the last claim decides the makespan
-  // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
-  A.tchunk = (lx_nedges_estimate(m) / 64 > (long long)grid * 256) ? TCHUNK : 1;
-  A.f = a.f; A.eatom = a.eatom; A.partial = st.partial.as<double>(); A.vatom = a.vatom;
-  {
-    StageTimer tm(m, "model_fused", s);
-#define LX_LAUNCH_VA(UTV, NLV, PROFV, VAV) do { if (st.arith == 3) hipLaunchKernelGGL((k_fused_lx<2, UTV, NW, NLV, PROFV, 3, VAV>), dim3(grid), dim3(NW * 64), 0, s, A); \
-                                        else hipLaunchKernelGGL((k_fused_lx<2, UTV, NW, NLV, PROFV, 0, VAV>), dim3(grid), dim3(NW * 64), 0, s, A); } while (0)
-#define LX_LAUNCH(UTV, NLV, PROFV) LX_LAUNCH_VA(UTV, NLV, PROFV, false)
-#define LX_LAUNCH_NL(UTV) do { if (A.NL == 3) LX_LAUNCH(UTV, 3, false); else if (A.NL == 2) LX_LAUNCH(UTV, 2, false); else LX_LAUNCH(UTV, 1, false); } while (0)
-    if (A.vatom) {
-      if (A.NL == 3) LX_LAUNCH_VA(2, 3, false, true); else if (A.NL == 2) LX_LAUNCH_VA(2, 2, false, true); else LX_LAUNCH_VA(2, 1, false, true);
-    } else if (st.prof_on && A.NL == 3) {
-      AHIP_CHECK(hipMemsetAsync(st.prof.p, 0, 64 * sizeof(long long), s));
-      A.prof = st.prof.as<long long>();
-      LX_LAUNCH(2, 3, true);
-    } else LX_LAUNCH_NL(2);
-#undef LX_LAUNCH_NL
-#undef LX_LAUNCH
-#undef LX_LAUNCH_VA
-  }
-  AHIP_CHECK(hipGetLastError());
-  AHIP_CHECK(prim_sum_columns_f64(m.prim, st.partial.as<double>(), grid, 7, a.engvir, s));
-  if (st.prof_on && A.NL == 3) {
-    std::vector<long long> hp(PX_N);
-    AHIP_CHECK(hipMemcpyAsync(hp.data(), st.prof.p, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
-    AHIP_CHECK(hipStreamSynchronize(s));
-    static const char *names[PX_N] = {"geom+tb", "embed", "env+reduce", "tp", "latent_mlp", "mix", "readout", "b_latent", "b_mix", "b_tp+reduce", "b_env", "b_embed", "finish"};
-    double tot = 0;
-    for (int k = 0; k < PX_N; ++k) tot += (double)hp[k];
-    std::fprintf(stderr, "[ahip fused_lx prof] wave-cycles by phase (sum over %d waves):", grid * NW);
-    for (int k = 0; k < PX_N; ++k) std::fprintf(stderr, " %s=%.1f%%", names[k], 100.0 * hp[k] / tot);
-    std::fprintf(stderr, " | total=%.3g cycles\n", tot);
-  }
+  if (!lx_list_fits(m, why)) return false;
+  FusedLxState &st = lx_prepare<ShapeX>(m, m.fusedlx_state, nullptr, false, lx_stream);
+  static_assert(PX_N == LX_NPHASE, "profile phases");
+  lx_run<ShapeX>(m, a, st, "fused_lx", [&](const FusedLxArgs &A, int grid, int var) {
+    dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants>([&](auto nl, auto ar, auto v) {
+      if constexpr (v != VAR_PROF || nl == 3)         // profiled: 3 layers only
+        hipLaunchKernelGGL((k_fused_lx<nl, v == VAR_PROF, ar, v == VAR_VA>), dim3(grid), dim3(ShapeX::NW * 64), 0, a.stream, A);
+    }, A.NL, st.arith, var);
+  });
   return true;
 }
 
 void fusedlx_free(Model &m) {
-  if (!m.fusedlx_state) return;
-  FusedLxState *st = (FusedLxState *)m.fusedlx_state;
-  for (DevBuf *b : {&st->wbuf, &st->scratch, &st->seg_count, &st->seg_base, &st->tile_a0, &st->tile_e0, &st->centre, &st->ntiles, &st->partial, &st->prof}) b->release();
-  delete st;
-  m.fusedlx_state = nullptr;
+  lx_free(m.fusedlx_state);
+  lx_free(m.fusedlx2_state);
 }
 
 }  // namespace ahip

@@ -806,22 +806,12 @@ static std::vector<double> gather_tiles(const double *W, int ldw, const std::vec
   return o;
 }
 
-static void fusedlx2_prepare(Model &m) {
+// k_fused_lx2's weight streams, one per wave half, in the order a tile consumes them (see k_fused_lx2)
+static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, int arith) {
   using S = ShapeP;
-  if (!m.fusedlx2_state) m.fusedlx2_state = new FusedLxState();
-  FusedLxState &st = *(FusedLxState *)m.fusedlx2_state;
-  if (st.ready) return;
-  st.L = 2; st.UT = 4;
-  const HostModel &h = fused_host_model(m);          // at the kernel's fixed widths (zero-padded when the model is narrower: 33..63 tensor features, ...)
-  const int T = h.num_types, NL = h.num_layers, U = S::U, D = S::D, UT = S::UT;
-  std::vector<float> w;
-  FusedLxArgs &A = st.args;
-  std::memset(&A, 0, sizeof(A));
-  auto mark = [&]() { while (w.size() % 64) w.push_back(0.f); return (int)w.size(); };
+  const int NL = h.num_layers, U = S::U, D = S::D, UT = S::UT;
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
-  st.arith = lx_arith_of(m);
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
-  // ---- one weight stream per wave half, in the order a tile consumes it (see k_fused_lx2) ----
   for (int hf = 0; hf < 2; ++hf) {
     auto own = [&](int t) { return 2 * hf + t; };
     auto par = [&](int t) { return 2 * (1 - hf) + t; };
@@ -836,14 +826,14 @@ static void fusedlx2_prepare(Model &m) {
     const std::vector<int> cat_cols = {own(0), own(1), 4 + own(0), 4 + own(1)};
     auto put = [&](const double *W, int ldw, const std::vector<int> &rt, const std::vector<int> &ct) {
       auto sub = gather_tiles(W, ldw, rt, ct);
-      if (st.arith == 3) h_flags |= append_frag_h(w, sub.data(), 16 * (int)rt.size(), 16 * (int)ct.size(), 16 * (int)ct.size()) & H_RANGE_OVERFLOW;      // (sub-blocks: the tiny-linear finding is taken per matrix below)
+      if (arith == 3) h_flags |= append_frag_h(w, sub.data(), 16 * (int)rt.size(), 16 * (int)ct.size(), 16 * (int)ct.size()) & H_RANGE_OVERFLOW;      // (sub-blocks: the tiny-linear finding is taken per matrix, lx_prepare)
       else append_frag(w, sub.data(), 16 * (int)rt.size(), 16 * (int)ct.size(), 16 * (int)ct.size());
     };
     auto putT = [&](const double *W, int K, int N, const std::vector<int> &rt, const std::vector<int> &ct) {    // tiles of W^T ([N][K])
       auto t = transpose(W, K, N);
       put(t.data(), K, rt, ct);
     };
-    const int o_stream = mark();
+    const int o_stream = lx_mark(w);
     if (hf == 0) A.o_stream = o_stream; else A.o_stream_hi = o_stream;
     const size_t stream0 = w.size();
     put(T_("emb.w"), U * 3, xo, lu);
@@ -874,111 +864,20 @@ static void fusedlx2_prepare(Model &m) {
     putT(T_("emb.w"), 64, U * 3, lu, xo);
     for (size_t i = 0; i < (size_t)RING * 256; ++i) w.push_back(w[stream0 + i]);      // wrap-around copy
   }
-  // two-body table
-  A.tb_nk = 512;
-  A.o_tbtab = mark();
-  append_two_body_table(w, h, m.rcut_model_host, A.tb_nk);
-  // small tables: path weights (last layer: only the scalar paths, the rest zero)
-  A.o_tpl = mark();
-  for (int k = 0; k < NL; ++k) {
-    const HostTensor &tp = h.get("l" + std::to_string(k + 1) + ".tp");
-    for (int p = 0; p < S::NP; ++p)
-      for (int u = 0; u < U; ++u) w.push_back(p < tp.shape[0] ? (float)(tp.data[(size_t)p * U + u] * ahip_cg_l2_cbase[p]) : 0.f);   // x the path's base |c| (tp_g)
-  }
-  for (int k = 0; k < NL; ++k) {
-    const HostTensor &res = h.get("l" + std::to_string(k + 1) + ".res");
-    A.o_res[k] = mark(); w.push_back((float)res.data[0]); w.push_back((float)res.data[1]);
-  }
-  A.o_out1 = mark(); for (int u = 0; u < 32; ++u) w.push_back((float)h.get("out.w1").data[u]);
-  A.o_scale = mark(); for (int t = 0; t < T; ++t) w.push_back((float)h.get("scale").data[t]);
-  A.o_shift = mark(); for (int t = 0; t < T; ++t) w.push_back((float)h.get("shift").data[t]);
-  mark();
-  st.wbuf.reserve(w.size() * sizeof(float));
-  copy_h2d(st.wbuf.p, w.data(), w.size() * sizeof(float));       // staged: see engine.h
-  A.wbase = st.wbuf.as<float>();
-  A.wbytes = (int)(w.size() * sizeof(float));
-  A.T = T; A.NL = NL; A.p = h.poly_p;
-  A.cenv = (float)(1.0 / std::sqrt(h.avg_num_neighbors));
-  {
-    const float pf = (float)h.poly_p, ca = 0.5f * (pf + 1) * (pf + 2), cb = pf * (pf + 2), cc = 0.5f * pf * (pf + 1);      // the expressions of cutoff_poly
-    A.cp[0] = ca; A.cp[1] = cb; A.cp[2] = cc; A.cp[3] = ca * pf; A.cp[4] = cb * (pf + 1); A.cp[5] = cc * (pf + 2);
-  }
-  if (st.arith == 3) {
-    arith_range_verdict(m, h_flags | model_tiny_linear(h));      // auto: ArithDegraded (run_model falls back to the f32 instance); explicit f16x2: an overflow is an error
-    A.err = alarm_word(m);
-  }
-  A.wave_scratch = (long long)S::R_TOTAL(NL) * ROW;
-  hipDeviceProp_t prop;
-  AHIP_CHECK(hipGetDeviceProperties(&prop, m.device));
-  st.ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  st.scratch.reserve((size_t)st.ncu * S::NW * st.args.wave_scratch * sizeof(float));
-  st.args.scratch = st.scratch.as<float>();
-  st.partial.reserve((size_t)st.ncu * 7 * sizeof(double));
-  st.ntiles.reserve(64);
-  st.prof.reserve(64 * sizeof(long long));
-  const char *pe = std::getenv("AHIP_FUSED_PROF");
-  st.prof_on = pe && pe[0] == '1';
-  st.ready = true;
+  return h_flags;
 }
 
 bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
-  using S = ShapeP;
-  constexpr int NW = S::NW, SLOTS = S::SLOTS;
-  fusedlx2_prepare(m);
-  FusedLxState &st = *(FusedLxState *)m.fusedlx2_state;
-  m.last_fused_arith = st.arith;
-  hipStream_t s = a.stream;
-  const int inum = m.inum;
-  const int grid = std::max(1, st.ncu - (m.reserve_wgs + 1) / 2);      // see fused.hip: slots left free for the exchange kernels
-  lx_pack_tiles(m, st, a, SLOTS, S::MAXA);
-  FusedLxArgs A = st.args;
-  A.wg_scratch = NW * A.wave_scratch;
-  A.eoff = m.b_eoff.as<int>(); A.e_ii = m.b_eii.as<int>(); A.e_j = m.b_ej.as<int>();
-  A.e_tt = m.b_ett.as<unsigned char>(); A.rvec = m.b_rvec.as<float>(); A.rcut = m.rcut_model_dev;
-  lx_tile_args(m, st, A, SLOTS, S::MAXA);
-  A.tchunk = (lx_nedges_estimate(m) / SLOTS > (long long)grid * 256) ? TCHUNK : 1;
-  A.f = a.f; A.eatom = a.eatom; A.partial = st.partial.as<double>(); A.vatom = a.vatom;
-  (void)inum;
-  {
-    StageTimer tm(m, "model_fused", s);
-#define LX2_LAUNCH_VA(NLV, PROFV, VAV) do { if (st.arith == 3) hipLaunchKernelGGL((k_fused_lx2<NLV, PROFV, 3, VAV>), dim3(grid), dim3(NW * 64), 0, s, A); \
-                                    else hipLaunchKernelGGL((k_fused_lx2<NLV, PROFV, 0, VAV>), dim3(grid), dim3(NW * 64), 0, s, A); } while (0)
-#define LX2_LAUNCH(NLV, PROFV) LX2_LAUNCH_VA(NLV, PROFV, false)
-    if (A.vatom) {
-      if (A.NL == 3) LX2_LAUNCH_VA(3, false, true); else if (A.NL == 2) LX2_LAUNCH_VA(2, false, true); else LX2_LAUNCH_VA(1, false, true);
-    } else if (st.prof_on && A.NL == 3) {
-      AHIP_CHECK(hipMemsetAsync(st.prof.p, 0, 64 * sizeof(long long), s));
-      A.prof = st.prof.as<long long>();
-      LX2_LAUNCH(3, true);
-    } else if (A.NL == 3) LX2_LAUNCH(3, false);
-    else if (A.NL == 2) LX2_LAUNCH(2, false);
-    else LX2_LAUNCH(1, false);
-#undef LX2_LAUNCH
-#undef LX2_LAUNCH_VA
-  }
-  AHIP_CHECK(hipGetLastError());
-  AHIP_CHECK(prim_sum_columns_f64(m.prim, st.partial.as<double>(), grid, 7, a.engvir, s));
-  if (st.prof_on && A.NL == 3) {
-    std::vector<long long> hp(PP_N);
-    AHIP_CHECK(hipMemcpyAsync(hp.data(), st.prof.p, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
-    AHIP_CHECK(hipStreamSynchronize(s));
-    static const char *names[PP_N] = {"geom+tb", "embed", "env+reduce", "tp", "latent_mlp", "mix", "readout", "b_latent", "b_mix", "b_tp+reduce", "b_env", "b_embed", "finish"};
-    double tot = 0;
-    for (int k = 0; k < PP_N; ++k) tot += (double)hp[k];
-    std::fprintf(stderr, "[ahip fused_lx2 prof] wave-cycles by phase (sum over %d waves):", grid * NW);
-    for (int k = 0; k < PP_N; ++k) std::fprintf(stderr, " %s=%.1f%%", names[k], 100.0 * hp[k] / tot);
-    std::fprintf(stderr, " | total=%.3g cycles\n", tot);
-  }
-  (void)why;
+  if (!lx_list_fits(m, why)) return false;
+  FusedLxState &st = lx_prepare<ShapeP>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream);     // path weights x the path's base |c| (tp_g)
+  static_assert(PP_N == LX_NPHASE, "profile phases");
+  lx_run<ShapeP>(m, a, st, "fused_lx2", [&](const FusedLxArgs &A, int grid, int var) {
+    dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants>([&](auto nl, auto ar, auto v) {
+      if constexpr (v != VAR_PROF || nl == 3)         // profiled: 3 layers only
+        hipLaunchKernelGGL((k_fused_lx2<nl, v == VAR_PROF, ar, v == VAR_VA>), dim3(grid), dim3(ShapeP::NW * 64), 0, a.stream, A);
+    }, A.NL, st.arith, var);
+  });
   return true;
-}
-
-void fusedlx2_free(Model &m) {
-  if (!m.fusedlx2_state) return;
-  FusedLxState *st = (FusedLxState *)m.fusedlx2_state;
-  for (DevBuf *b : {&st->wbuf, &st->scratch, &st->seg_count, &st->seg_base, &st->tile_a0, &st->tile_e0, &st->centre, &st->ntiles, &st->partial, &st->prof}) b->release();
-  delete st;
-  m.fusedlx2_state = nullptr;
 }
 
 }  // namespace ahip

@@ -8,13 +8,17 @@
 #include "fused_h.h"
 #include "prims.h"
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
 
 namespace ahip {
 
 static constexpr int LX_MAXNL = 3;
 
 template <int L> struct CgX;
-template <> struct CgX<1> { static constexpr const AhipCgEntry *tab = ahip_cg_l1; static constexpr int N = AHIP_CG_L1_N, NS = AHIP_CG_L1_NSCALAR, NP = AHIP_CG_L1_NPATHS, NPS = AHIP_CG_L1_NPATHS_SCALAR; };
 template <> struct CgX<2> { static constexpr const AhipCgEntry *tab = ahip_cg_l2; static constexpr int N = AHIP_CG_L2_N, NS = AHIP_CG_L2_NSCALAR, NP = AHIP_CG_L2_NPATHS, NPS = AHIP_CG_L2_NPATHS_SCALAR; };
 
 __host__ __device__ constexpr int l_of_lm(int lm) { return lm == 0 ? 0 : (lm < 4 ? 1 : 2); }
@@ -71,64 +75,143 @@ __device__ __forceinline__ void lx_lin(__amdgpu_buffer_rsrc_t W, int &wp, const 
   } else linear_s<KT, NT, ACC, RP, Epi>(W, wp, in, out, v16, ring.f, epi);
 }
 
-// host-side state of one wide fused kernel family
+// ---------------------------------------------------------------------------- host driver of both wide kernels
+// host-side state of one wide fused kernel
 struct FusedLxState {
-  DevBuf wbuf, scratch, seg_count, seg_base, tile_a0, tile_e0, centre, ntiles, partial, prof;
+  DevBuf wbuf, scratch, prof;
+  TileBufs tiles;
   FusedLxArgs args;
   bool ready = false, prof_on = false;
   int ncu = 256;
-  int L = 0, UT = 0;
   int arith = 0;               // 0: f32-input MFMA, 3: f16x2 (lx_arith_of)
 };
+static int lx_mark(std::vector<float> &w) { while (w.size() % 64) w.push_back(0.f); return (int)w.size(); }
 
-// edge total for the claim-size heuristic: the value itself when it is on the host, else the last one that was, else from the list's size
-static long long lx_nedges_estimate(const Model &m) {
-  return !m.counts_pending ? m.nedges : m.nedges_hint > 0 ? m.nedges_hint : (long long)(0.58 * (double)m.nneigh);
+// Prepares a wide kernel's state once (shape S).  `stream(w, A, h, arith)` appends the kernel's own weight-stream layout, sets A.o_stream (and
+// o_stream_hi) and returns its float16 range findings (engine.h: H_RANGE_*).  The rest is common: two-body table, path weights (each times
+// cbase[path] when cbase is given: the grouped tensor product of fused_lx2.hip), residual weights, read-out, scale / shift, the upload, the scalar
+// arguments, the f16x2 range verdict (tiny: with the model-wide tiny-linear finding too, fused_lx2.hip), the per-wave scratch, the device setup.
+template <class S, class Stream>
+static FusedLxState &lx_prepare(Model &m, FusedLxState *&slot, const double *cbase, bool tiny, Stream stream) {
+  if (!slot) slot = new FusedLxState();
+  FusedLxState &st = *slot;
+  if (st.ready) return st;
+  const HostModel &h = fused_host_model(m);          // at the kernel's fixed widths (zero-padded when the model is narrower)
+  const int T = h.num_types, NL = h.num_layers, U = S::U;
+  std::vector<float> w;
+  FusedLxArgs &A = st.args;
+  std::memset(&A, 0, sizeof(A));
+  st.arith = lx_arith_of(m);
+  const int h_flags = stream(w, A, h, st.arith);
+  // two-body table
+  A.tb_nk = 512;
+  A.o_tbtab = lx_mark(w);
+  append_two_body_table(w, h, m.rcut_model_host, A.tb_nk);
+  // small tables: path weights (last layer: only the scalar paths, the rest zero)
+  A.o_tpl = lx_mark(w);
+  for (int k = 0; k < NL; ++k) {
+    const HostTensor &tp = h.get("l" + std::to_string(k + 1) + ".tp");
+    for (int p = 0; p < S::NP; ++p)
+      for (int u = 0; u < U; ++u)
+        w.push_back(p < tp.shape[0] ? (float)(cbase ? tp.data[(size_t)p * U + u] * cbase[p] : tp.data[(size_t)p * U + u]) : 0.f);
+  }
+  for (int k = 0; k < NL; ++k) {
+    const HostTensor &res = h.get("l" + std::to_string(k + 1) + ".res");
+    A.o_res[k] = lx_mark(w); w.push_back((float)res.data[0]); w.push_back((float)res.data[1]);
+  }
+  A.o_out1 = lx_mark(w); for (int u = 0; u < 32; ++u) w.push_back((float)h.get("out.w1").data[u]);
+  A.o_scale = lx_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("scale").data[t]);
+  A.o_shift = lx_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("shift").data[t]);
+  lx_mark(w);
+  st.wbuf.reserve(w.size() * sizeof(float));
+  copy_h2d(st.wbuf.p, w.data(), w.size() * sizeof(float));       // staged: see engine.h
+  A.wbase = st.wbuf.as<float>();
+  A.wbytes = (int)(w.size() * sizeof(float));
+  A.T = T; A.NL = NL; A.p = h.poly_p;
+  A.cenv = (float)(1.0 / std::sqrt(h.avg_num_neighbors));
+  {
+    const float pf = (float)h.poly_p, ca = 0.5f * (pf + 1) * (pf + 2), cb = pf * (pf + 2), cc = 0.5f * pf * (pf + 1);      // the expressions of cutoff_poly
+    A.cp[0] = ca; A.cp[1] = cb; A.cp[2] = cc; A.cp[3] = ca * pf; A.cp[4] = cb * (pf + 1); A.cp[5] = cc * (pf + 2);
+  }
+  if (st.arith == 3) {
+    arith_range_verdict(m, h_flags | (tiny ? model_tiny_linear(h) : 0));      // auto: ArithDegraded (run_model falls back to the f32 instance); explicit f16x2: an overflow is an error
+    A.err = alarm_word(m);
+  }
+  A.wave_scratch = (long long)S::R_TOTAL(NL) * ROW;
+  hipDeviceProp_t prop;
+  AHIP_CHECK(hipGetDeviceProperties(&prop, m.device));
+  st.ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  st.scratch.reserve((size_t)st.ncu * S::NW * A.wave_scratch * sizeof(float));
+  A.scratch = st.scratch.as<float>();
+  st.tiles.partial.reserve((size_t)st.ncu * 7 * sizeof(double));
+  st.tiles.ntiles.reserve(64);
+  st.prof.reserve(64 * sizeof(long long));
+  const char *pe = std::getenv("AHIP_FUSED_PROF");
+  st.prof_on = pe && pe[0] == '1';
+  st.ready = true;
+  return st;
 }
-// Tile packing shared by the wide fused kernels: consecutive centres into tiles of <= slots edges and <= maxa centres
-// (k_pack_tiles, fused_common.h), per-centre {atom, type}, per-edge packed types, first edge of every tile.
-// the tile arrays the kernel reads: the edge build's (it packed them itself, edges.hip) or this state's
-static bool lx_prepacked(const Model &m, int slots, int maxa) { return m.tiles_packed && m.pack_slots == slots && m.pack_maxa == maxa; }
-static void lx_tile_args(Model &m, FusedLxState &st, FusedLxArgs &A, int slots, int maxa) {
-  const bool pre = lx_prepacked(m, slots, maxa);
-  int *const ntl = pre ? m.b_ntiles.as<int>() : st.ntiles.as<int>();
-  A.centre = pre ? m.b_centre.as<int2>() : st.centre.as<int2>();
-  A.tile_a0 = pre ? m.b_tile_a0.as<int>() : st.tile_a0.as<int>(); A.tile_e0 = pre ? m.b_tile_e0.as<int>() : st.tile_e0.as<int>(); A.ntiles = ntl;
-  A.tile_counter = (unsigned int *)(ntl + 1);
-  m.d_ntiles_last = ntl; m.last_tile_slots = slots;
+
+// What both wide kernels require of the edge list before anything is enqueued.  (Counts still in flight = single-pass edge build with
+// heavy_thresh = LX_TILE_SLOTS: every centre with more edges is listed, gets a tile of its own that the kernel skips, and is evaluated by
+// heavy_generic after the kernel has been enqueued -- the host reads the counts only then, VERDICT r03 #2.)
+static bool lx_list_fits(const Model &m, std::string *why) {
+  if (!m.counts_pending && m.last_max_deg > LX_TILE_SLOTS && (m.heavy_thresh != LX_TILE_SLOTS || (long long)m.nheavy * 8 > m.inum)) {
+    // centres with more than 64 edges are listed by the edge build and evaluated by the layer-at-a-time kernels; when the edge
+    // build did not list them (two-pass fallback) or they are not a small minority, the whole system goes that way
+    if (why) *why = "an atom has " + std::to_string(m.last_max_deg) + " edges (> " + std::to_string(LX_TILE_SLOTS) + " per tile of the wide fused kernel)";
+    return false;
+  }
+  if (m.edges_T_size != 4) { if (why) *why = "edge vectors are not float32"; return false; }
+  return true;
 }
-static void lx_pack_tiles(Model &m, FusedLxState &st, const ComputeArgs &a, int slots, int maxa) {
-  if (lx_prepacked(m, slots, maxa)) return;
+
+// phases of the profiled instances (AHIP_FUSED_PROF=1, 3 layers): the kernels' PX_* / PP_* enums
+static constexpr int LX_NPHASE = 13;
+// One evaluation on a prepared wide kernel (shape S): tile packing, arguments, `launch(A, grid, variant)` (the file's instance dispatch; variant:
+// fused_common.h, VAR_*), the energy / virial sums, and the per-phase profile printed as "[ahip <name> prof]" (tools/abprof.sh reads it)
+template <class S, class Launch>
+static void lx_run(Model &m, const ComputeArgs &a, FusedLxState &st, const char *name, Launch launch) {
+  static_assert(S::SLOTS == LX_TILE_SLOTS && S::MAXA == LX_TILE_MAXA, "allegro_hip.hip requests this tile shape from the edge build");
+  m.last_fused_arith = st.arith;
   hipStream_t s = a.stream;
-  const int inum = m.inum;
-  const int nseg = (inum + SEG - 1) / SEG;
-  st.seg_count.reserve((size_t)(nseg + 1) * sizeof(int));
-  st.seg_base.reserve((size_t)(nseg + 2) * sizeof(int));
-  st.tile_a0.reserve((size_t)(inum + nseg + 2) * sizeof(int));
-  st.tile_e0.reserve((size_t)(inum + nseg + 2) * sizeof(int));
-  StageTimer tm(m, "tile_pack", s);
-  const unsigned B = 64;
-  st.centre.reserve((size_t)std::max(inum, 1) * sizeof(int2));
-  const bool small = inum <= PACK_SMALL_ATOMS;
-  if (small)
-    hipLaunchKernelGGL(k_pack_small, dim3(1), dim3(PACK_SMALL_SEGS), 0, s, inum, m.b_eoff.as<int>(), nseg, st.tile_a0.as<int>(), st.tile_e0.as<int>(), st.ntiles.as<int>(), slots, maxa,
-                       m.d_ilist, a.mtype, st.centre.as<int2>());
-  else {
-    hipLaunchKernelGGL(k_pack_tiles<false>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, st.seg_count.as<int>(), (const int *)nullptr, (int *)nullptr, slots, maxa);
-    AHIP_CHECK(prim_exclusive_scan_i32(m.prim, st.seg_count.as<int>(), st.seg_base.as<int>(), nseg, s));
-    hipLaunchKernelGGL(k_pack_tiles<true>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, (int *)nullptr, st.seg_base.as<int>(), st.tile_a0.as<int>(), slots, maxa);
-    hipLaunchKernelGGL(k_pack_finish, dim3(1), dim3(1), 0, s, inum, nseg, st.seg_base.as<int>(), st.tile_a0.as<int>(), st.ntiles.as<int>());
-    hipLaunchKernelGGL(k_centre_info, dim3((inum + 255) / 256), dim3(256), 0, s, inum, m.d_ilist, a.mtype, st.centre.as<int2>());
+  const int grid = std::max(1, st.ncu - (m.reserve_wgs + 1) / 2);      // see fused.hip: slots left free for the exchange kernels
+  FusedLxArgs A = st.args;
+  A.wg_scratch = S::NW * A.wave_scratch;
+  fused_tile_args(m, st.tiles, a, A, S::SLOTS, S::MAXA);
+  // claims of TCHUNK tiles amortise the counter's round trip; with few tiles per workgroup the last claim decides the makespan
+  // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
+  A.tchunk = (fused_nedges_estimate(m) / S::SLOTS > (long long)grid * 256) ? TCHUNK : 1;
+  const bool prof = st.prof_on && A.NL == 3;
+  {
+    StageTimer tm(m, "model_fused", s);
+    if (prof && !A.vatom) {
+      AHIP_CHECK(hipMemsetAsync(st.prof.p, 0, 64 * sizeof(long long), s));
+      A.prof = st.prof.as<long long>();
+    }
+    launch(A, grid, fused_variant(A.vatom, prof));
   }
-  if (!m.have_ett) {
-    m.b_ett.reserve((size_t)std::max<long long>(m.nedges, 1));
-    hipLaunchKernelGGL(k_edge_types, dim3((unsigned)((m.nedges + 255) / 256)), dim3(256), 0, s, m.nedges, m.b_eii.as<int>(), m.b_ej.as<int>(), m.d_ilist, a.mtype, m.b_ett.as<unsigned char>());
-    m.have_ett = true;
+  AHIP_CHECK(hipGetLastError());
+  AHIP_CHECK(prim_sum_columns_f64(m.prim, st.tiles.partial.as<double>(), grid, 7, a.engvir, s));
+  if (prof) {
+    std::vector<long long> hp(LX_NPHASE);
+    AHIP_CHECK(hipMemcpyAsync(hp.data(), st.prof.p, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
+    AHIP_CHECK(hipStreamSynchronize(s));
+    static const char *names[LX_NPHASE] = {"geom+tb", "embed", "env+reduce", "tp", "latent_mlp", "mix", "readout", "b_latent", "b_mix", "b_tp+reduce", "b_env", "b_embed", "finish"};
+    double tot = 0;
+    for (int k = 0; k < LX_NPHASE; ++k) tot += (double)hp[k];
+    std::fprintf(stderr, "[ahip %s prof] wave-cycles by phase (sum over %d waves):", name, grid * S::NW);
+    for (int k = 0; k < LX_NPHASE; ++k) std::fprintf(stderr, " %s=%.1f%%", names[k], 100.0 * hp[k] / tot);
+    std::fprintf(stderr, " | total=%.3g cycles\n", tot);
   }
-  if (!small) {
-    const int tcap = inum + nseg + 1;
-    hipLaunchKernelGGL(k_tile_e0, dim3((tcap + 255) / 256), dim3(256), 0, s, st.ntiles.as<int>(), st.tile_a0.as<int>(), m.b_eoff.as<int>(), st.tile_e0.as<int>());
-  }
+}
+
+static void lx_free(FusedLxState *&st) {
+  if (!st) return;
+  for (DevBuf *b : {&st->wbuf, &st->scratch, &st->prof}) b->release();
+  st->tiles.release();
+  delete st;
+  st = nullptr;
 }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -256,9 +339,6 @@ __device__ __forceinline__ void tp_bwd_half(const f32x2 (&o)[(L + 1) * (L + 1)],
 // VAR 1: gradient w.r.t. the edge tensor (A = output gradient i3, B = environment i2, O over i1); VAR 2: per-edge environment gradient
 // (A = output gradient i3, B = edge tensor i1, O over i2).  SCALAR: only the paths with l3 = 0 (last layer).
 template <int L, int VAR> struct CgG;
-template <> struct CgG<1, 0> { static constexpr const AhipCgG *tab = ahip_cg_l1_f; };
-template <> struct CgG<1, 1> { static constexpr const AhipCgG *tab = ahip_cg_l1_b0; };
-template <> struct CgG<1, 2> { static constexpr const AhipCgG *tab = ahip_cg_l1_b1; };
 template <> struct CgG<2, 0> { static constexpr const AhipCgG *tab = ahip_cg_l2_f; };
 template <> struct CgG<2, 1> { static constexpr const AhipCgG *tab = ahip_cg_l2_b0; };
 template <> struct CgG<2, 2> { static constexpr const AhipCgG *tab = ahip_cg_l2_b1; };
