@@ -160,16 +160,16 @@ static void free_fused_states(Model &m) { fused_free(m); fusedlx_free(m); }
 // fused_arith=auto falls back to the f32-input MFMA instances for the rest of this model's life (engine.h): the prepared f16x2 weight streams go, the next
 // dispatch prepares the f32 ones; said once on stderr and kept for ahip_arith_note
 static void arith_degrade(Model &m, const std::string &why) {
-  m.arith_degraded = true;
-  m.arith_note = "fused_arith=auto: float32 instance (f32-input MFMA) selected: " + why;
+  m.arith.degraded = true;
+  m.arith.note = "fused_arith=auto: float32 instance (f32-input MFMA) selected: " + why;
   free_fused_states(m);
-  std::fprintf(stderr, "[allegro-hip] %s\n", m.arith_note.c_str());
+  std::fprintf(stderr, "[allegro-hip] %s\n", m.arith.note.c_str());
 }
 // An alarm found at the START of an evaluation, or by an accessor, was raised by an EARLIER device-resident evaluation that nobody waited for: its forces were
 // not finite and have been handed out.  That is reported either way; under auto the model also switches to the f32 instance, so the error is reported once.
 void fused_poll_alarm(Model &m) {
   if (!alarm_take(m)) return;
-  if (arith_option(m) == "auto" && !m.arith_degraded) {
+  if (arith_may_degrade(m)) {
     arith_degrade(m, "an earlier evaluation produced a non-finite edge gradient on the f16x2 arithmetic (an activation left float16's range)");
     throw StateError("fused_arith=auto: an EARLIER evaluation produced non-finite forces on the f16x2 arithmetic (an activation left float16's range, or the input was "
                      "not finite); this model now runs on the float32 instance -- re-evaluate from the last valid state");
@@ -239,18 +239,22 @@ int ahip_set_option(ahip_model *m, const char *key, const char *value) {
     require_model(m);
     if (!key || !value) throw ArgError("ahip_set_option: NULL key/value");
     const std::string k(key), v(value);
+    // an enumerated option: the position of the value among the option's words, which are declared beside its enum in the order of the enumerators
+    auto word = [&](const char *words) {
+      const int i = word_index(words, v);
+      if (i < 0) throw ArgError("option " + k + ": expected " + words);
+      return i;
+    };
     if (k == "path") {
-      if (v != "auto" && v != "fused" && v != "generic") throw ArgError("option path: expected auto|fused|generic");
-      m->opt_path = v;
+      m->opt_path = (Model::Path)word(Model::PATH_WORDS);
     } else if (k == "precision") {
-      if (v != "model" && v != "float64") throw ArgError("option precision: expected model|float64");
-      m->opt_precision = v;
+      m->opt_precision = (Model::Precision)word(Model::PRECISION_WORDS);
     } else if (k == "fused_arith") {
-      if (v != "bf16x3" && v != "f32" && v != "tf32eq" && v != "f16x2" && v != "auto") throw ArgError("option fused_arith: expected auto|f32|f16x2|bf16x3|tf32eq");
-      if (v != m->opt_fused_arith) { m->opt_fused_arith = v; free_fused_states(*m); }
+      const ArithOpt o = (ArithOpt)word(ARITH_OPT_WORDS);
+      if (o != m->arith.opt) { m->arith.opt = o; free_fused_states(*m); }
     } else if (k == "fused_tb") {
-      if (v != "table" && v != "mlp") throw ArgError("option fused_tb: expected table|mlp");
-      if (v != m->opt_fused_tb) { m->opt_fused_tb = v; fused_free(*m); }
+      const FusedTb o = (FusedTb)word(FUSED_TB_WORDS);
+      if (o != m->opt_fused_tb) { m->opt_fused_tb = o; fused_free(*m); }
     } else if (k == "chunk_edges") {
       long long n = std::atoll(value);
       if (n < 1) throw ArgError("option chunk_edges: expected a positive integer");
@@ -260,15 +264,12 @@ int ahip_set_option(ahip_model *m, const char *key, const char *value) {
       if (n < 0 || n > 128) throw ArgError("option reserve_wgs: expected 0..128");
       m->reserve_wgs = n;
     } else if (k == "cutoff_compare") {
-      if (v != "le" && v != "lt") throw ArgError("option cutoff_compare: expected le|lt");
-      m->cutoff_strict = v == "lt";
+      m->cutoff_strict = word("le|lt") == 1;
       m->h_cutsq_dev.clear();
     } else if (k == "edge_schedule") {
-      if (v != "auto" && v != "static" && v != "dynamic") throw ArgError("option edge_schedule: expected auto|static|dynamic");
-      m->opt_edge_schedule = v;
+      m->opt_edge_schedule = (Model::EdgeSchedule)word(Model::EDGE_SCHEDULE_WORDS);
     } else if (k == "tile_pack") {
-      if (v != "auto" && v != "separate" && v != "fused") throw ArgError("option tile_pack: expected auto|separate|fused");
-      m->opt_tile_pack = v;
+      m->opt_tile_pack = (Model::TilePack)word(Model::TILE_PACK_WORDS);
     } else if (k == "timing") {
       m->timing = (v == "1" || v == "on" || v == "true");
     } else throw ArgError("unknown option '" + k + "'");
@@ -585,7 +586,7 @@ static void heavy_generic(ahip_model *m, const ComputeArgs &a) {
 }
 
 // The fused kernel family that serves the model: k_fused (l_max = 1), k_fused_lx (l_max = 2, 32 tensor features), k_fused_lx2 (64), or none (why: the
-// reasons of both).  Not cached: it depends on arith_force / arith_degraded (fused_model_supported: MLP depth 1 / 3 need f16x2), which the
+// reasons of both).  Not cached: it depends on arith.force_f32 / arith.degraded (fused_model_supported: MLP depth 1 / 3 need f16x2), which the
 // self-check and an ArithDegraded fallback change.
 enum class FusedFamily { none, k_fused, lx32, lx64 };
 static FusedFamily fused_family(const Model &m, std::string *why) {
@@ -621,27 +622,28 @@ static __global__ void k_chk_reduce(long long n, const double *a, const double *
 // alarm was raised.  Cost: two extra evaluations and two weight-stream builds, once per model (per pair_coeff).  Energies / virial / per-atom energies are the
 // second pass's (or the fallback's); f gets the chosen pass added, as always.
 static void run_model_selfcheck(ahip_model *m, const ComputeArgs &a) {
-  m->arith_checked = true;
+  m->arith.checked = true;
   const long long nf = 3LL * (a.nlocal + a.nghost);
   m->b_chk.reserve((size_t)(2 * nf + 16) * sizeof(double));
   double *f32f = m->b_chk.as<double>(), *f16f = f32f + nf, *ev = f16f + nf;
   unsigned long long *red = (unsigned long long *)(ev + 8);
   hipStream_t s = a.stream;
+  auto add_to_f = [&]() { if (nf > 0) hipLaunchKernelGGL(k_add_n, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, nf, a.f, f16f); };      // the kept pass's forces into the caller's
   AHIP_CHECK(hipMemsetAsync(m->b_chk.p, 0, (size_t)(2 * nf + 16) * sizeof(double), s));
   ComputeArgs a1 = a;
   a1.f = f32f; a1.eatom = nullptr; a1.engvir = ev;
-  m->arith_force = 0;
+  m->arith.force_f32 = true;
   free_fused_states(*m);
-  try { run_model_dispatch(m, a1); } catch (...) { m->arith_force = -1; free_fused_states(*m); throw; }
-  m->arith_force = -1;                       // (a shape without a float32 fused instance -- MLP depth 1 / 3 -- was just evaluated by the layer-at-a-time float32 kernels)
+  try { run_model_dispatch(m, a1); } catch (...) { m->arith.force_f32 = false; free_fused_states(*m); throw; }
+  m->arith.force_f32 = false;                     // (a shape without a float32 fused instance -- MLP depth 1 / 3 -- was just evaluated by the layer-at-a-time float32 kernels)
   free_fused_states(*m);
   ComputeArgs a2 = a;
   a2.f = f16f;
   run_model_dispatch(m, a2);                 // (a prepare-time fallback inside lands on f32 as well: the comparison below is then trivially green)
-  if (m->last_path != "fused_f16x2" && !m->arith_degraded) {
+  if (m->last_path != fused_path_name(AR_F16X2) && !m->arith.degraded) {
     // this LIST went down the layer-at-a-time path (a centre with more edges than a tile holds): nothing was checked; a later list gets its chance, three times at most
-    if (++m->arith_check_attempts < 3) m->arith_checked = false;
-    if (nf > 0) hipLaunchKernelGGL(k_add_n, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, nf, a.f, f16f);
+    if (++m->arith.check_attempts < 3) m->arith.checked = false;
+    add_to_f();
     return;
   }
   hipLaunchKernelGGL(k_chk_reduce, dim3(1024), dim3(256), 0, s, nf, f32f, f16f, red);
@@ -653,15 +655,15 @@ static void run_model_selfcheck(ahip_model *m, const ComputeArgs &a) {
   const bool alarm = alarm_take(*m);
   const bool ok = !alarm && dmax <= 1.0e-5 * fmax_ + 1.0e-30;
   char buf[256];
-  if (m->arith_degraded) {                   // fell back while preparing: f16f holds the float32 result
-    if (nf > 0) hipLaunchKernelGGL(k_add_n, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, nf, a.f, f16f);
+  if (m->arith.degraded) {                   // fell back while preparing: f16f holds the float32 result
+    add_to_f();
     return;
   }
   if (ok) {
     std::snprintf(buf, sizeof(buf), "fused_arith=auto: f16x2 kept: first evaluation within %.2e max|F| of the float32 instance (max|dF| %.3e, max|F| %.3e; bar 1e-5)",
                   fmax_ > 0 ? dmax / fmax_ : 0.0, dmax, fmax_);
-    m->arith_note = buf;
-    if (nf > 0) hipLaunchKernelGGL(k_add_n, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, s, nf, a.f, f16f);
+    m->arith.note = buf;
+    add_to_f();
     return;
   }
   std::snprintf(buf, sizeof(buf), "first-evaluation self-check: f16x2 %s (max|dF| %.3e vs the float32 instance, max|F| %.3e; bar 1e-5 max|F|)",
@@ -671,32 +673,31 @@ static void run_model_selfcheck(ahip_model *m, const ComputeArgs &a) {
 }
 static void run_model(ahip_model *m, const ComputeArgs &a) {
   fused_poll_alarm(*m);                      // raised by an EARLIER device-resident evaluation (nobody waits for those kernels)
-  const bool f64 = (m->opt_precision == "float64") || (m->hm.model_dtype == "float64");
-  const bool wants_check = !m->arith_checked && !m->arith_degraded && m->inum > 0 && !f64 && m->opt_path != "generic" && arith_option(*m) == "auto" &&
+  const bool wants_check = !m->arith.checked && arith_may_degrade(*m) && m->inum > 0 && !model_runs_f64(*m) && m->opt_path != Model::Path::Generic &&
                            !m->hm.allow_tf32 && fused_family(*m, nullptr) != FusedFamily::none &&
                            std::getenv("AHIP_NO_ARITH_SELFCHECK") == nullptr;
   if (wants_check) {
     run_model_selfcheck(m, a);
-    if (m->arith_checked) m->b_chk.release();      // two force arrays of the whole system: not kept for the model's life (hipFree waits for the kernels that still read them)
+    if (m->arith.checked) m->b_chk.release();      // two force arrays of the whole system: not kept for the model's life (hipFree waits for the kernels that still read them)
   } else run_model_dispatch(m, a);
 }
 static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   m->nedges = 0;
   // W restarts with every dispatch: it always belongs to the evaluation whose forces reach f (self-check passes, ArithDegraded re-dispatch, float32 fallback)
   if (a.vatom) AHIP_CHECK(hipMemsetAsync(a.vatom, 0, (size_t)(a.nlocal + a.nghost) * 9 * sizeof(double), a.stream));
-  const bool f64 = (m->opt_precision == "float64") || (m->hm.model_dtype == "float64");
+  const bool f64 = model_runs_f64(*m);
   // the 7 energy / virial sums start from zero: the single-pass edge build clears them in its first kernel, every other way here
   if (m->inum == 0 || f64) AHIP_CHECK(hipMemsetAsync(a.engvir, 0, 7 * sizeof(double), a.stream));
   if (m->inum == 0) return;                                   // empty sub-domain (pair_nequip_allegro.cpp:340-341)
   if (f64) {
-    if (m->opt_path == "fused") throw UnsupportedError("the fused MFMA path computes in float32; use path=generic for float64");
+    if (m->opt_path == Model::Path::Fused) throw UnsupportedError("the fused MFMA path computes in float32; use path=generic for float64");
     build_edges<double>(*m, a);
     generic_run<double>(*m, a);
     m->last_path = "generic_f64";
     return;
   }
   std::string why;
-  const FusedFamily fam = m->opt_path == "generic" ? FusedFamily::none : fused_family(*m, &why);
+  const FusedFamily fam = m->opt_path == Model::Path::Generic ? FusedFamily::none : fused_family(*m, &why);
   const bool wide = fam == FusedFamily::lx32 || fam == FusedFamily::lx64;
   m->have_ett = false;
   m->nheavy = 0;
@@ -708,7 +709,7 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   // ... and up to 262 144 centres per call: the packing runs on the scanning wave of every unit, i.e. serially inside the edge build, and costs there what
   // the stand-alone kernels cost beside it once they have a chip to spread over (1 M atoms: 0.062 vs 0.064 ms); below that the six launches they need are
   // the cost (10 648 atoms: 0.026 ms, 125 000: 0.056 ms, three times per step in the overlapped multi-rank schedule)
-  if (m->opt_tile_pack != "separate" && (m->inum <= 262144 || m->opt_tile_pack == "fused")) {
+  if (m->opt_tile_pack != Model::TilePack::Separate && (m->inum <= 262144 || m->opt_tile_pack == Model::TilePack::Fused)) {
     if (fam == FusedFamily::k_fused) { if (m->max_list_row >= 0 && m->max_list_row <= FUSED_TILE_SLOTS) { m->pack_slots = FUSED_TILE_SLOTS; m->pack_maxa = FUSED_TILE_MAXA; } }
     else if (wide) { m->pack_slots = LX_TILE_SLOTS; m->pack_maxa = LX_TILE_MAXA; }
   }
@@ -719,12 +720,12 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   if (edges_only) { m->last_path = "edges_only"; return; }
 #endif
   bool fused_ok = false;
-  if (m->opt_path != "generic") {
-    m->last_fused_arith = 0;
+  if (m->opt_path != Model::Path::Generic) {
+    m->arith.last = AR_F32;
     if (fam == FusedFamily::k_fused) fused_ok = fused_run(*m, a, &why);
     else if (fam == FusedFamily::lx32) fused_ok = fusedlx_run(*m, a, &why);
     else if (fam == FusedFamily::lx64) fused_ok = fusedlx2_run(*m, a, &why);
-    if (!fused_ok && m->opt_path == "fused") throw UnsupportedError("fused path unavailable: " + why);
+    if (!fused_ok && m->opt_path == Model::Path::Fused) throw UnsupportedError("fused path unavailable: " + why);
   }
   if (fused_ok) {
     // wide kernels: the number of centres left to the layer-at-a-time kernels is read now, with the model kernel already enqueued
@@ -733,7 +734,7 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
     if (m->nheavy > 0) heavy_generic(m, a);
     // "fused_tf32eq": the two-term bf16 split the model file licensed with allow_tf32 = 1 (fused.hip); everything else is float32-exact
     // "fused_f16x2" / "fused_bf16x3": float32-equivalent splits on the f16 / bf16 matrix cores (fused_h.h, fused.hip); "fused_f32": exact fmaf chains
-    m->last_path = m->last_fused_arith == 2 ? "fused_tf32eq" : m->last_fused_arith == 3 ? "fused_f16x2" : m->last_fused_arith == 1 ? "fused_bf16x3" : "fused_f32";
+    m->last_path = fused_path_name(m->arith.last);
     return;
   }
   edges_counts(*m);
@@ -903,7 +904,7 @@ int ahip_compute(ahip_model *m, int nlocal, int nghost, const double *x, const i
     AHIP_CHECK(hipEventSynchronize(m->f_events[nfch]));
     if (alarm_take(*m)) {                    // raised by THIS evaluation: nothing of it has touched the caller's arrays yet
       (void)hipStreamSynchronize(s);         // (the copies into the page-locked vectors finish before anybody may free or refill them)
-      if (arith_option(*m) == "auto" && !m->arith_degraded && attempt == 0) {
+      if (arith_may_degrade(*m) && attempt == 0) {
         arith_degrade(*m, "an activation left float16's range (non-finite edge gradient on the f16x2 arithmetic); the evaluation was repeated");
         continue;
       }
@@ -1135,7 +1136,7 @@ extern "C" int ahip_last_tile_occupancy(ahip_model *m, long long *slots_used, lo
 // last kernel family used ("generic_f32" | "generic_f64" | "fused_f32" | "fused_tf32eq")
 extern "C" const char *ahip_last_path(ahip_model *m) { return m ? m->last_path.c_str() : ""; }
 // what fused_arith=auto decided for this model and why (empty until the first evaluation): "f16x2 kept: ..." or "float32 instance selected: ..."
-extern "C" const char *ahip_arith_note(const ahip_model *m) { return m ? m->arith_note.c_str() : ""; }
+extern "C" const char *ahip_arith_note(const ahip_model *m) { return m ? m->arith.note.c_str() : ""; }
 extern "C" int ahip_last_max_degree(ahip_model *m) {
   if (!m) return 0;
   if (guarded([&] { edges_counts(*m); }) != 0) return -1;

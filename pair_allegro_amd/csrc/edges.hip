@@ -437,7 +437,7 @@ bool edges_build_f32(Model &m, const ComputeArgs &a) {
   // the persistent model kernel of the other range run beside this one), a second model in the process, other processes on the
   // device (option edge_schedule=dynamic) -- and then units are claimed one at a time, which cannot wait on a workgroup that has not
   // started.  Launches with the fixed stride are additionally chained by an event, so that two of them never overlap in one process.
-  const bool dyn = m.opt_edge_schedule == "dynamic" || (m.opt_edge_schedule == "auto" && (m.reserve_wgs > 0 || g_models_alive.load() > 1));
+  const bool dyn = m.opt_edge_schedule == Model::EdgeSchedule::Dynamic || (m.opt_edge_schedule == Model::EdgeSchedule::Auto && (m.reserve_wgs > 0 || g_models_alive.load() > 1));
   // (one event per model, i.e. per device: ADVICE r03 -- a process-wide one belonged to whichever device ran first; with a second model alive the
   // dynamic schedule is chosen anyway)
   if (!dyn) {

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "arith_policy.h"
 #include "model_io.h"
 #include "prims.h"
 
@@ -102,20 +103,19 @@ struct Model {
   std::vector<double> rcut_model_host;      // [T*T]
 
   // options
-  std::string opt_path = "auto";            // auto | fused | generic
-  std::string opt_precision = "model";      // model | float64
-  std::string opt_fused_tb = "table";       // table | mlp: two-body embedding of the fused kernel from the spline table or as an MLP
-  std::string opt_fused_arith = "auto";     // auto | f32 | f16x2 | bf16x3 | tf32eq: arithmetic of the fused kernels' linears.  auto = f16x2 (float32-equivalent, fused_h.h); tf32eq iff the
-                                            // model file sets allow_tf32; f32 once auto has degraded (below)
-  int last_fused_arith = 0;                 // what the last fused evaluation used: 0 f32, 1 bf16x3, 2 tf32eq, 3 f16x2
-  // fused_arith=auto must never be less robust than the reference's float32: a model the f16x2 split cannot carry -- a weight beyond float16's
-  // range, a linear whose weights sit in float16's subnormals, an activation that overflows, a first evaluation that disagrees with the f32 instance -- runs on the
-  // f32-input MFMA instance for the rest of this model's life instead of failing.  Only an EXPLICIT fused_arith=f16x2 still reports those as errors.
-  bool arith_degraded = false;              // auto has fallen back to f32 (sticky)
-  bool arith_checked = false;               // the first-evaluation self-check of auto's f16x2 against the f32 instance has run (allegro_hip.hip: run_model)
-  int arith_force = -1;                     // self-check only: -1 none, 0 = resolve auto to f32 for this dispatch
-  int arith_check_attempts = 0;
-  std::string arith_note;                   // what auto decided and why, one line (ahip_arith_note)
+  // options (each enum with its words, in the order of the enumerators: arith_policy.h, word_index)
+  enum class Path { Auto, Fused, Generic };
+  static constexpr const char *PATH_WORDS = "auto|fused|generic";
+  enum class Precision { Model, Float64 };
+  static constexpr const char *PRECISION_WORDS = "model|float64";
+  enum class TilePack { Auto, Separate, Fused };
+  static constexpr const char *TILE_PACK_WORDS = "auto|separate|fused";
+  enum class EdgeSchedule { Auto, Static, Dynamic };
+  static constexpr const char *EDGE_SCHEDULE_WORDS = "auto|static|dynamic";
+  Path opt_path = Path::Auto;
+  Precision opt_precision = Precision::Model;
+  FusedTb opt_fused_tb = FusedTb::Table;    // table | mlp: two-body embedding of the fused kernel from the spline table or as an MLP
+  ArithState arith;                         // option fused_arith (auto | f32 | f16x2 | bf16x3 | tf32eq) and what auto has decided so far: arith_policy.h
   DevBuf b_chk;                             // self-check: two force arrays + the 2-word reduction
   // A model narrower than a fused kernel's fixed widths runs on it zero-padded (round 6; model_io.h: pad_host_model): S <= 64 scalars, MLP width <= 64, read-out
   // width <= 32, U <= 32 tensor features for l_max = 1, U <= 32 / <= 64 for l_max = 2.  hm stays the model as loaded (layer-at-a-time kernels, metadata).
@@ -124,8 +124,8 @@ struct Model {
   long long chunk_edges = 2000000;
   int reserve_wgs = 0;                      // workgroup slots the persistent fused kernels leave free (for kernels of other streams)
   bool timing = false;
-  std::string opt_tile_pack = "auto";       // auto | separate | fused (auto = fused up to 262 144 centres per call): tile packing inside the single-pass edge build where the tile shape is known up front, or always by the stand-alone kernels (A/B, tests)
-  std::string opt_edge_schedule = "auto";   // auto | static | dynamic: unit schedule of the single-pass edge build (edges.hip)
+  TilePack opt_tile_pack = TilePack::Auto;  // auto | separate | fused (auto = fused up to 262 144 centres per call): tile packing inside the single-pass edge build where the tile shape is known up front, or always by the stand-alone kernels (A/B, tests)
+  EdgeSchedule opt_edge_schedule = EdgeSchedule::Auto;   // auto | static | dynamic: unit schedule of the single-pass edge build (edges.hip)
   bool cutoff_strict = false;               // edge kept iff rsq < cut^2 (the KOKKOS reference path) instead of rsq <= cut^2 (the host path)
 
   // weights
@@ -265,18 +265,14 @@ inline const HostModel &fused_host_model(Model &m) {
   if (!m.hm_fused_ready) { m.hm_fused = pad_host_model(h, 64, fused_UF(h), 64, 32); m.hm_fused_ready = true; }
   return m.hm_fused;
 }
-// option fused_arith as it applies (the environment variable of the A/B tools wins)
-inline std::string arith_option(const Model &m) {
-  const char *ar = std::getenv("AHIP_FUSED_ARITH");
-  return ar ? std::string(ar) : m.opt_fused_arith;
+// the arithmetic policy (arith_policy.h) applied to a model: k_fused (wide = false) or the wide kernels
+inline bool arith_may_degrade(const Model &m) { return arith_may_degrade(m.arith); }
+inline bool fused_tb_is_table(const Model &m) { return fused_tb_is_table(m.opt_fused_tb); }
+inline Arith resolve_arith(const Model &m, bool wide) {
+  return resolve_arith(arith_effective(m.arith.opt), m.hm.allow_tf32 != 0, m.arith.degraded, m.arith.force_f32, fused_tb_is_table(m), wide);
 }
-// auto -> f16x2 unless it has degraded (or the self-check is running its f32 pass)
-inline bool arith_auto_is_f16x2(const Model &m) { return !m.arith_degraded && m.arith_force != 0; }
-// arithmetic of the wide fused kernels' linears from option fused_arith: 3 = f16x2 (auto, f16x2), 0 = f32-input MFMA (f32; the bf16 splits exist in k_fused only)
-inline int lx_arith_of(const Model &m) {
-  const std::string a = arith_option(m);
-  return (a == "f16x2" || (a == "auto" && arith_auto_is_f16x2(m))) ? 3 : 0;
-}
+// the model computes in float64 (option precision, or the model file's own dtype): layer-at-a-time kernels only
+inline bool model_runs_f64(const Model &m) { return m.opt_precision == Model::Precision::Float64 || m.hm.is_f64(); }
 // thrown by a fused kernel's prepare step when fused_arith=auto meets a model the f16x2 split cannot carry; run_model degrades the model and dispatches again
 struct ArithDegraded {
   std::string why;
@@ -305,7 +301,7 @@ inline int model_tiny_linear(const HostModel &h) {
 inline void arith_range_verdict(const Model &m, int flags) {
   if (!flags) return;
   const char *what = (flags & H_RANGE_OVERFLOW) ? "a weight of this model exceeds float16's range" : "a linear of this model has all its weights below 2^-10 (float16 subnormal territory for the split)";
-  if (arith_option(m) == "auto") throw ArithDegraded{what};
+  if (arith_may_degrade(m)) throw ArithDegraded{what};
   if (flags & H_RANGE_OVERFLOW) throw UnsupportedError(std::string("fused_arith=f16x2: ") + what + "; use fused_arith=f32 (or auto)");
 }
 // f16x2 arithmetic: the backward pass is linear in its upstream gradient scale[type] / sqrt(avg_num_neighbors) and runs scaled by the power of two that brings that

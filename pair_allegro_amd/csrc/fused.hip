@@ -1106,7 +1106,7 @@ struct FusedState {
   bool ready = false, prof_on = false, dbg_on = false, clk_on = false;
   bool tbt = true;             // two-body embedding from the spline table (default) or evaluated as an MLP (option fused_tb=mlp)
   int md = 2;                  // hidden layers of the latent MLP (template parameter MD of k_fused)
-  int arith = 0;               // 0: f32-input MFMA; 1: bf16x3 (option fused_arith=bf16x3 / AHIP_FUSED_ARITH=b3); 2: tf32eq (two-term bf16 split; fused_arith=auto picks it when the model file says allow_tf32 = 1); 3: f16x2 (fused_h.h)
+  Arith arith = AR_F32;        // arith_policy.h: resolve_arith (every arithmetic has its k_fused instances)
   DevBuf prof, dbg;
   int ncu = 256;
   int force_nw = 0;            // AHIP_FUSED_NW=4|8 pins the workgroup shape (A/B measurements)
@@ -1146,18 +1146,6 @@ static int append_frag_b(std::vector<float> &out, const double *W, int K, int N,
             }
   return 2 * nterm * KS * (NT / 2);
 }
-// arithmetic (FusedState::arith) and two-body mode that options, environment and model metadata resolve to
-static int fused_resolve_arith(const Model &m, bool &tbt) {
-  const HostModel &h = m.hm;
-  const char *tb = std::getenv("AHIP_FUSED_TB");
-  tbt = (tb ? std::string(tb) : m.opt_fused_tb) != "mlp";
-  const std::string arith = arith_option(m);
-  // auto: tf32eq iff the model file licenses it; else f16x2 -- unless the model has degraded to f32 (engine.h) or the self-check is running its f32 pass
-  int a = (arith == "b3" || arith == "bf16x3") ? 1 : (arith == "tf32eq" || (arith == "auto" && h.allow_tf32 && m.arith_force != 0)) ? 2
-          : (arith == "f16x2" || (arith == "auto" && arith_auto_is_f16x2(m))) ? 3 : 0;
-  if (a == 3 && !tbt) a = 0;        // the f16x2 instances exist with the tabulated two-body embedding only
-  return a;
-}
 bool fused_model_supported(const Model &m, std::string *why) {
   const HostModel &h = m.hm;
   auto no = [&](const char *msg) { if (why) *why = msg; return false; };
@@ -1165,16 +1153,11 @@ bool fused_model_supported(const Model &m, std::string *why) {
   if (!fused_widths_fit(h)) return no("fused kernels hold at most U=32, S=64, MLP width 64, read-out width 32 (narrower models run zero-padded)");
   if (h.mlp_depth < 1 || h.mlp_depth > 3 || h.readout_depth != 1) return no("fused kernels need MLP depth 1..3 and read-out depth 1");
   if (h.mlp_depth != 2) {           // round 5: depth 1 and 3 on the f16x2 instances with the tabulated two-body embedding
-    bool tbt;
-    if (fused_resolve_arith(m, tbt) != 3) return no("MLP depth 1 / 3 runs on the f16x2 arithmetic with the tabulated two-body embedding only (fused_arith=auto|f16x2, fused_tb=table, allow_tf32 = 0)");
+    if (resolve_arith(m, false) != AR_F16X2) return no("MLP depth 1 / 3 runs on the f16x2 arithmetic with the tabulated two-body embedding only (fused_arith=auto|f16x2, fused_tb=table, allow_tf32 = 0)");
   }
   // the radial basis only enters through the two-body embedding: tabulated (default) any number of Bessel functions will do, evaluated in the kernel
   // (fused_tb=mlp) its first linear is laid out for 8
-  {
-    const char *tb = std::getenv("AHIP_FUSED_TB");
-    const bool in_kernel = (tb ? std::string(tb) : m.opt_fused_tb) == "mlp";
-    if (h.num_bessels < 1 || (in_kernel && h.num_bessels != 8)) return no("fused_tb=mlp needs 8 Bessel functions (the tabulated two-body embedding takes any number)");
-  }
+  if (h.num_bessels < 1 || (!fused_tb_is_table(m) && h.num_bessels != 8)) return no("fused_tb=mlp needs 8 Bessel functions (the tabulated two-body embedding takes any number)");
   if (h.num_layers < 1 || h.num_layers > MAXNL) return no("fused kernels need 1..3 layers");
   if (h.num_types > 16) return no("fused kernels support at most 16 model types (4-bit packed edge types)");
   return true;
@@ -1189,29 +1172,29 @@ static void fused_prepare(Model &m) {
   std::vector<float> w;
   FusedArgs &A = st.args;
   std::memset(&A, 0, sizeof(A));
-  auto mark = [&]() { while (w.size() % 64) w.push_back(0.f); return (int)w.size(); };
   // two-body: pair table (type-type rows of the first layer)
   const HostTensor &w0 = h.get("tb.w0");          // [2T+8][64]
-  A.o_pair = mark();
+  A.o_pair = w_mark(w);
   for (int ti = 0; ti < T; ++ti)
     for (int tj = 0; tj < T; ++tj)
       for (int n = 0; n < 64; ++n) w.push_back((float)(w0.data[(size_t)ti * 64 + n] + w0.data[(size_t)(T + tj) * 64 + n]));
   // ---- the weight stream, in the order one tile consumes it ----
-  A.o_stream = mark();
+  A.o_stream = w_mark(w);
   const size_t stream0 = w.size();
-  st.arith = fused_resolve_arith(m, st.tbt);
+  st.tbt = fused_tb_is_table(m);
+  st.arith = resolve_arith(m, false);
   st.md = h.mlp_depth;
   const int MD = st.md;
-  const bool b3 = st.arith == 1 || st.arith == 2, tbt = st.tbt;
-  const int nterm = st.arith == 1 ? 3 : 2;
+  const bool b3 = st.arith == AR_BF16X3 || st.arith == AR_TF32EQ, h2 = st.arith == AR_F16X2, tbt = st.tbt;
+  const int nterm = st.arith == AR_BF16X3 ? 3 : 2;
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
   auto fwd = [&](const double *W, int K, int N) {
-    if (st.arith == 3) h_flags |= append_frag_h(w, W, K, N, N);
+    if (h2) h_flags |= append_frag_h(w, W, K, N, N);
     else if (b3) append_frag_b(w, W, K, N, N, nterm); else append_frag(w, W, K, N, N);
   };
   auto bwd = [&](const double *W, int K, int N) {
     auto t = transpose(W, K, N);
-    if (st.arith == 3) h_flags |= append_frag_h(w, t.data(), N, K, K);
+    if (h2) h_flags |= append_frag_h(w, t.data(), N, K, K);
     else if (b3) append_frag_b(w, t.data(), N, K, K, nterm); else append_frag(w, t.data(), N, K, K);
   };
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
@@ -1236,7 +1219,7 @@ static void fused_prepare(Model &m) {
     if (k < NL - 1) {
       const double *mx = T_(lk + ".mix");            // [2][32][32]; the l=1 block serves m = -1, 0, 1
       fwd(mx, 32, 32);
-      for (int c = 0; c < (st.arith == 3 ? 1 : 3); ++c) fwd(mx + 1024, 32, 32);      // f16x2: once, shared by the three components (k_fused: lin_m3)
+      for (int c = 0; c < (h2 ? 1 : 3); ++c) fwd(mx + 1024, 32, 32);      // f16x2: once, shared by the three components (k_fused: lin_m3)
     }
     fwd(T_(lk + ".lat.w0"), 96, 64);
     for (int hl = 1; hl < MD; ++hl) fwd(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64);
@@ -1256,7 +1239,7 @@ static void fused_prepare(Model &m) {
     if (k < NL - 1) {
       const double *mx = T_(lk + ".mix");
       bwd(mx, 32, 32);
-      for (int c = 0; c < (st.arith == 3 ? 1 : 3); ++c) bwd(mx + 1024, 32, 32);
+      for (int c = 0; c < (h2 ? 1 : 3); ++c) bwd(mx + 1024, 32, 32);
     }
     bwd(T_(lk + ".env"), 64, 64);
   }
@@ -1267,45 +1250,11 @@ static void fused_prepare(Model &m) {
     bwd(wc, 8, 64);
   }
   {   // wrap-around copy: the last linear of a tile prefetches the first fragments of the next tile
-    const size_t n = (size_t)(st.arith == 1 ? RINGB : st.arith == 2 ? RINGB2 : st.arith == 3 ? RINGH : RING) * 256;
+    const size_t n = (size_t)(st.arith == AR_BF16X3 ? RINGB : st.arith == AR_TF32EQ ? RINGB2 : h2 ? RINGH : RING) * 256;
     for (size_t i = 0; i < n; ++i) w.push_back(w[stream0 + i]);
   }
-  // two-body embedding table (see k_fused): per type pair, cubic Hermite in d on [0, r_c(pair)] from the float64 MLP
-  A.tb_nk = 512;
-  A.o_tbtab = mark();
-  if (tbt) append_two_body_table(w, h, m.rcut_model_host, A.tb_nk);
-  // small tables
-  A.o_tpl = mark();
-  for (int k = 0; k < NL; ++k) {
-    const HostTensor &tp = h.get("l" + std::to_string(k + 1) + ".tp");
-    for (int p = 0; p < 5; ++p)
-      for (int u = 0; u < 32; ++u) w.push_back(p < tp.shape[0] ? (float)tp.data[(size_t)p * 32 + u] : 0.f);
-  }
-  for (int k = 0; k < NL; ++k) {
-    const HostTensor &res = h.get("l" + std::to_string(k + 1) + ".res");
-    A.o_res[k] = mark(); w.push_back((float)res.data[0]); w.push_back((float)res.data[1]);
-  }
-  A.o_out1 = mark(); for (int u = 0; u < 32; ++u) w.push_back((float)h.get("out.w1").data[u]);
-  A.o_scale = mark(); for (int t = 0; t < T; ++t) w.push_back((float)h.get("scale").data[t]);
-  A.o_shift = mark(); for (int t = 0; t < T; ++t) w.push_back((float)h.get("shift").data[t]);
-  mark();
-  st.wbuf.reserve(w.size() * sizeof(float));
-  copy_h2d(st.wbuf.p, w.data(), w.size() * sizeof(float));       // staged: see engine.h
-  A.wbase = st.wbuf.as<float>();
-  A.wbytes = (int)(w.size() * sizeof(float));
-  A.T = T; A.NL = NL; A.p = h.poly_p;
-  A.cenv = (float)(1.0 / std::sqrt(h.avg_num_neighbors));
-  {
-    const float pf = (float)h.poly_p, ca = 0.5f * (pf + 1) * (pf + 2), cb = pf * (pf + 2), cc = 0.5f * pf * (pf + 1);      // the expressions of cutoff_poly
-    A.cp[0] = ca; A.cp[1] = cb; A.cp[2] = cc; A.cp[3] = ca * pf; A.cp[4] = cb * (pf + 1); A.cp[5] = cc * (pf + 2);
-  }
-  if (st.arith == 3) {
-    arith_range_verdict(m, h_flags);                 // auto: ArithDegraded (run_model falls back to the f32 instance); explicit f16x2: an overflow is an error
-    A.err = alarm_word(m);
-  }
-  hipDeviceProp_t prop;
-  AHIP_CHECK(hipGetDeviceProperties(&prop, m.device));
-  st.ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  // two-body table (see k_fused), small tables, upload, scalar arguments, float16 range verdict: fused_common.h
+  st.ncu = fused_prepare_tail(m, h, w, A, st.wbuf, tbt, 5, 32, nullptr, st.arith, h_flags);
   // Persistent workgroups, 8 waves per CU either way (two per SIMD, 256 registers each).
   A.wave_scratch = (long long)R_TOTAL(NL, MD) * ROW;
   st.scratch.reserve((size_t)st.ncu * 8 * A.wave_scratch * sizeof(float));
@@ -1342,7 +1291,7 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
   } else if (st.force_nw == 8) nw = 8;
   else if (m.max_list_row >= 0 && m.max_list_row <= 64) nw = 4;
   const int *maxdeg_sel = nw == 0 ? m.d_maxdeg : nullptr;
-  m.last_fused_arith = st.arith;
+  m.arith.last = st.arith;
   hipStream_t s = a.stream;
   const int tile_slots = nw == 8 ? 128 : 64, maxa = nw == 8 ? Lds<8>::MAXA : Lds<4>::MAXA;      // nw == 0: the packing kernels widen them themselves
   static_assert(Lds<4>::MAXA == FUSED_TILE_MAXA && FUSED_TILE_SLOTS == 64, "allegro_hip.hip requests the 4-wave tile shape from the edge build");
@@ -1374,8 +1323,8 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
       // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
       A.tchunk = (nedges_est / (16 * shape) > (long long)g * 256) ? TCHUNK : 1;
       if (const char *tc = std::getenv("AHIP_TCHUNK")) A.tchunk = std::max(1, std::atoi(tc));       // experiments
-      if (st.arith == 3) { fused_launch_f16(shape, st.prof_on, st.md, g, s, A); continue; }                        // fused_h.o
-      if (st.arith != 0) { fused_launch_bf16(shape, st.prof_on, st.arith, st.tbt, g, s, A); continue; }     // fused_bf.o
+      if (st.arith == AR_F16X2) { fused_launch_f16(shape, st.prof_on, st.md, g, s, A); continue; }                        // fused_h.o
+      if (st.arith != AR_F32) { fused_launch_bf16(shape, st.prof_on, st.arith, st.tbt, g, s, A); continue; }     // fused_bf.o
       dispatch<Choices<4, 8>, Choices<1, 0>, Choices<1, 2, 3>, Variants>([&](auto nw, auto tb, auto nl, auto var) {
         hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, 0, tb != 0, nl, 2, var == VAR_VA>), dim3(g), dim3(nw * 64), 0, s, A);
       }, shape, st.tbt, A.NL, fused_variant(A.vatom, st.prof_on));

@@ -665,4 +665,53 @@ static void append_two_body_table(std::vector<float> &w, const HostModel &h, con
             }
     }
 }
+
+// ---- weight buffer of a fused kernel (host side) ----
+// pads the buffer to a 64-float boundary and returns the offset there: every table a kernel addresses by offset starts on one
+static int w_mark(std::vector<float> &w) { while (w.size() % 64) w.push_back(0.f); return (int)w.size(); }
+// What every fused kernel's prepare step does once its own weight stream is in `w` (Args: FusedArgs / FusedLxArgs): the two-body table (tbt; k_fused with
+// fused_tb=mlp has none), the path weights [layer][NP][U] (each times cbase[path] when cbase is given: the grouped tensor product of fused_lx2.hip), residual
+// weights, read-out, scale / shift, the upload into wbuf, the scalar arguments, and on the f16x2 arithmetic the verdict on the stream's float16 range
+// findings h_flags (engine.h: H_RANGE_*) plus the alarm word.  Returns the device's CU count.
+template <class Args>
+static int fused_prepare_tail(Model &m, const HostModel &h, std::vector<float> &w, Args &A, DevBuf &wbuf, bool tbt, int NP, int U, const double *cbase, Arith arith, int h_flags) {
+  const int T = h.num_types, NL = h.num_layers;
+  // two-body embedding table: per type pair, cubic Hermite in d on [0, r_c(pair)] from the float64 MLP
+  A.tb_nk = 512;
+  A.o_tbtab = w_mark(w);
+  if (tbt) append_two_body_table(w, h, m.rcut_model_host, A.tb_nk);
+  // small tables: path weights (last layer: only the scalar paths, the rest zero)
+  A.o_tpl = w_mark(w);
+  for (int k = 0; k < NL; ++k) {
+    const HostTensor &tp = h.get("l" + std::to_string(k + 1) + ".tp");
+    for (int p = 0; p < NP; ++p)
+      for (int u = 0; u < U; ++u)
+        w.push_back(p < tp.shape[0] ? (float)(cbase ? tp.data[(size_t)p * U + u] * cbase[p] : tp.data[(size_t)p * U + u]) : 0.f);
+  }
+  for (int k = 0; k < NL; ++k) {
+    const HostTensor &res = h.get("l" + std::to_string(k + 1) + ".res");
+    A.o_res[k] = w_mark(w); w.push_back((float)res.data[0]); w.push_back((float)res.data[1]);
+  }
+  A.o_out1 = w_mark(w); for (int u = 0; u < 32; ++u) w.push_back((float)h.get("out.w1").data[u]);
+  A.o_scale = w_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("scale").data[t]);
+  A.o_shift = w_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("shift").data[t]);
+  w_mark(w);
+  wbuf.reserve(w.size() * sizeof(float));
+  copy_h2d(wbuf.p, w.data(), w.size() * sizeof(float));       // staged: see engine.h
+  A.wbase = wbuf.as<float>();
+  A.wbytes = (int)(w.size() * sizeof(float));
+  A.T = T; A.NL = NL; A.p = h.poly_p;
+  A.cenv = (float)(1.0 / std::sqrt(h.avg_num_neighbors));
+  {
+    const float pf = (float)h.poly_p, ca = 0.5f * (pf + 1) * (pf + 2), cb = pf * (pf + 2), cc = 0.5f * pf * (pf + 1);      // the expressions of cutoff_poly
+    A.cp[0] = ca; A.cp[1] = cb; A.cp[2] = cc; A.cp[3] = ca * pf; A.cp[4] = cb * (pf + 1); A.cp[5] = cc * (pf + 2);
+  }
+  if (arith == AR_F16X2) {
+    arith_range_verdict(m, h_flags);                 // auto: ArithDegraded (run_model falls back to the f32 instance); explicit f16x2: an overflow is an error
+    A.err = alarm_word(m);
+  }
+  hipDeviceProp_t prop;
+  AHIP_CHECK(hipGetDeviceProperties(&prop, m.device));
+  return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+}
 }  // namespace ahip

@@ -732,14 +732,14 @@ bool fusedlx_model_supported(const Model &m, std::string *why) {
 }
 
 // k_fused_lx's weight stream, in the order one tile consumes it: whole-matrix fragments (see k_fused_lx)
-static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, int arith) {
+static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, Arith arith) {
   using S = ShapeX;
   constexpr int L = S::L, U = S::U, D = S::D;
   const int NL = h.num_layers;
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
   auto frag = [&](const double *W, int K, int N, int ldw) {
-    if (arith == 3) h_flags |= append_frag_h(w, W, K, N, ldw);
+    if (arith == AR_F16X2) h_flags |= append_frag_h(w, W, K, N, ldw);
     else append_frag(w, W, K, N, ldw);
   };
   auto fwd = [&](const double *W, int K, int N) { frag(W, K, N, N); };
@@ -757,7 +757,7 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
       frag(pad.data(), U, 2 * U, 2 * U);
     } else frag(m2.data(), U, U, U);
   };
-  A.o_stream = lx_mark(w);
+  A.o_stream = w_mark(w);
   const size_t stream0 = w.size();
   fwd(T_("emb.w"), 64, U * (L + 1));
   for (int k = 0; k < NL; ++k) {

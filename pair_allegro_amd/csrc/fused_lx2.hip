@@ -807,7 +807,7 @@ static std::vector<double> gather_tiles(const double *W, int ldw, const std::vec
 }
 
 // k_fused_lx2's weight streams, one per wave half, in the order a tile consumes them (see k_fused_lx2)
-static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, int arith) {
+static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, Arith arith) {
   using S = ShapeP;
   const int NL = h.num_layers, U = S::U, D = S::D, UT = S::UT;
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
@@ -826,14 +826,14 @@ static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h,
     const std::vector<int> cat_cols = {own(0), own(1), 4 + own(0), 4 + own(1)};
     auto put = [&](const double *W, int ldw, const std::vector<int> &rt, const std::vector<int> &ct) {
       auto sub = gather_tiles(W, ldw, rt, ct);
-      if (arith == 3) h_flags |= append_frag_h(w, sub.data(), 16 * (int)rt.size(), 16 * (int)ct.size(), 16 * (int)ct.size()) & H_RANGE_OVERFLOW;      // (sub-blocks: the tiny-linear finding is taken per matrix, lx_prepare)
+      if (arith == AR_F16X2) h_flags |= append_frag_h(w, sub.data(), 16 * (int)rt.size(), 16 * (int)ct.size(), 16 * (int)ct.size()) & H_RANGE_OVERFLOW;      // (sub-blocks: the tiny-linear finding is taken per matrix, lx_prepare)
       else append_frag(w, sub.data(), 16 * (int)rt.size(), 16 * (int)ct.size(), 16 * (int)ct.size());
     };
     auto putT = [&](const double *W, int K, int N, const std::vector<int> &rt, const std::vector<int> &ct) {    // tiles of W^T ([N][K])
       auto t = transpose(W, K, N);
       put(t.data(), K, rt, ct);
     };
-    const int o_stream = lx_mark(w);
+    const int o_stream = w_mark(w);
     if (hf == 0) A.o_stream = o_stream; else A.o_stream_hi = o_stream;
     const size_t stream0 = w.size();
     put(T_("emb.w"), U * 3, xo, lu);

@@ -83,64 +83,27 @@ struct FusedLxState {
   FusedLxArgs args;
   bool ready = false, prof_on = false;
   int ncu = 256;
-  int arith = 0;               // 0: f32-input MFMA, 3: f16x2 (lx_arith_of)
+  Arith arith = AR_F32;        // AR_F32 or AR_F16X2 (arith_policy.h: resolve_arith, wide)
 };
-static int lx_mark(std::vector<float> &w) { while (w.size() % 64) w.push_back(0.f); return (int)w.size(); }
 
 // Prepares a wide kernel's state once (shape S).  `stream(w, A, h, arith)` appends the kernel's own weight-stream layout, sets A.o_stream (and
-// o_stream_hi) and returns its float16 range findings (engine.h: H_RANGE_*).  The rest is common: two-body table, path weights (each times
-// cbase[path] when cbase is given: the grouped tensor product of fused_lx2.hip), residual weights, read-out, scale / shift, the upload, the scalar
-// arguments, the f16x2 range verdict (tiny: with the model-wide tiny-linear finding too, fused_lx2.hip), the per-wave scratch, the device setup.
+// o_stream_hi) and returns its float16 range findings (engine.h: H_RANGE_*).  The rest is common (fused_common.h: fused_prepare_tail; cbase: the grouped
+// tensor product of fused_lx2.hip; tiny: the range verdict takes the model-wide tiny-linear finding too, fused_lx2.hip), then the per-wave scratch.
 template <class S, class Stream>
 static FusedLxState &lx_prepare(Model &m, FusedLxState *&slot, const double *cbase, bool tiny, Stream stream) {
   if (!slot) slot = new FusedLxState();
   FusedLxState &st = *slot;
   if (st.ready) return st;
   const HostModel &h = fused_host_model(m);          // at the kernel's fixed widths (zero-padded when the model is narrower)
-  const int T = h.num_types, NL = h.num_layers, U = S::U;
+  const int NL = h.num_layers;
   std::vector<float> w;
   FusedLxArgs &A = st.args;
   std::memset(&A, 0, sizeof(A));
-  st.arith = lx_arith_of(m);
-  const int h_flags = stream(w, A, h, st.arith);
-  // two-body table
-  A.tb_nk = 512;
-  A.o_tbtab = lx_mark(w);
-  append_two_body_table(w, h, m.rcut_model_host, A.tb_nk);
-  // small tables: path weights (last layer: only the scalar paths, the rest zero)
-  A.o_tpl = lx_mark(w);
-  for (int k = 0; k < NL; ++k) {
-    const HostTensor &tp = h.get("l" + std::to_string(k + 1) + ".tp");
-    for (int p = 0; p < S::NP; ++p)
-      for (int u = 0; u < U; ++u)
-        w.push_back(p < tp.shape[0] ? (float)(cbase ? tp.data[(size_t)p * U + u] * cbase[p] : tp.data[(size_t)p * U + u]) : 0.f);
-  }
-  for (int k = 0; k < NL; ++k) {
-    const HostTensor &res = h.get("l" + std::to_string(k + 1) + ".res");
-    A.o_res[k] = lx_mark(w); w.push_back((float)res.data[0]); w.push_back((float)res.data[1]);
-  }
-  A.o_out1 = lx_mark(w); for (int u = 0; u < 32; ++u) w.push_back((float)h.get("out.w1").data[u]);
-  A.o_scale = lx_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("scale").data[t]);
-  A.o_shift = lx_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("shift").data[t]);
-  lx_mark(w);
-  st.wbuf.reserve(w.size() * sizeof(float));
-  copy_h2d(st.wbuf.p, w.data(), w.size() * sizeof(float));       // staged: see engine.h
-  A.wbase = st.wbuf.as<float>();
-  A.wbytes = (int)(w.size() * sizeof(float));
-  A.T = T; A.NL = NL; A.p = h.poly_p;
-  A.cenv = (float)(1.0 / std::sqrt(h.avg_num_neighbors));
-  {
-    const float pf = (float)h.poly_p, ca = 0.5f * (pf + 1) * (pf + 2), cb = pf * (pf + 2), cc = 0.5f * pf * (pf + 1);      // the expressions of cutoff_poly
-    A.cp[0] = ca; A.cp[1] = cb; A.cp[2] = cc; A.cp[3] = ca * pf; A.cp[4] = cb * (pf + 1); A.cp[5] = cc * (pf + 2);
-  }
-  if (st.arith == 3) {
-    arith_range_verdict(m, h_flags | (tiny ? model_tiny_linear(h) : 0));      // auto: ArithDegraded (run_model falls back to the f32 instance); explicit f16x2: an overflow is an error
-    A.err = alarm_word(m);
-  }
+  st.arith = resolve_arith(m, true);
+  int h_flags = stream(w, A, h, st.arith);
+  if (st.arith == AR_F16X2 && tiny) h_flags |= model_tiny_linear(h);
+  st.ncu = fused_prepare_tail(m, h, w, A, st.wbuf, true, S::NP, S::U, cbase, st.arith, h_flags);
   A.wave_scratch = (long long)S::R_TOTAL(NL) * ROW;
-  hipDeviceProp_t prop;
-  AHIP_CHECK(hipGetDeviceProperties(&prop, m.device));
-  st.ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   st.scratch.reserve((size_t)st.ncu * S::NW * A.wave_scratch * sizeof(float));
   A.scratch = st.scratch.as<float>();
   st.tiles.partial.reserve((size_t)st.ncu * 7 * sizeof(double));
@@ -173,7 +136,7 @@ static constexpr int LX_NPHASE = 13;
 template <class S, class Launch>
 static void lx_run(Model &m, const ComputeArgs &a, FusedLxState &st, const char *name, Launch launch) {
   static_assert(S::SLOTS == LX_TILE_SLOTS && S::MAXA == LX_TILE_MAXA, "allegro_hip.hip requests this tile shape from the edge build");
-  m.last_fused_arith = st.arith;
+  m.arith.last = st.arith;
   hipStream_t s = a.stream;
   const int grid = std::max(1, st.ncu - (m.reserve_wgs + 1) / 2);      // see fused.hip: slots left free for the exchange kernels
   FusedLxArgs A = st.args;

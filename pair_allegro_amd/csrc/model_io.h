@@ -13,7 +13,8 @@ struct HostTensor {
 };
 
 struct HostModel {
-  std::string model_dtype = "float32";
+  std::string model_dtype = "float32";      // "float32" | "float64": the loader refuses anything else
+  bool is_f64() const { return model_dtype != "float32"; }
   std::vector<std::string> type_names;
   std::string type_names_joined;            // whitespace separated (reference metadata form)
   double r_max = 0;
