@@ -82,6 +82,11 @@ int ahip_model_meta(const ahip_model *m, double *r_max, int *num_types, const ch
  *   "fused_tb"  = "table" | "mlp"                two-body embedding of the fused kernels: tabulated cubic splines (default) or the MLP itself
  *   "edge_schedule" = "auto" | "static" | "dynamic"   unit schedule of the single-pass edge build (dynamic: safe beside other resident kernels)
  *   "tile_pack" = "auto" | "separate" | "fused"  tile packing of the fused kernels inside the edge build or as its own kernels
+ *   "dense_centres" = "whole" | "split"          a list in which a few centres have more edges than a tile of the fused kernel holds (128 for l_max = 1, 64 for
+ *                                                 l_max = 2) while a list row is longer than 128 entries: "whole" (default) evaluates the whole list on the
+ *                                                 layer-at-a-time kernels; "split" keeps the fused kernel for the other centres and evaluates only those few
+ *                                                 (at most one centre in eight, else as "whole") on the layer-at-a-time kernels.  ahip_last_heavy_centres
+ *                                                 reports them.  The cost of the split route has not been measured.
  *   "timing"    = "0" | "1"                      record per-stage HIP events (ahip_get_timings)
  * Unknown keys and values are errors (AHIP_ERR_ARG).
  */
@@ -150,7 +155,7 @@ int ahip_compute(ahip_model *m, int nlocal, int nghost, const double *x, const i
  * page-locked memory behind the edge build and the host waits for them only when it needs a value: never on the l_max = 1 fused path with
  * list rows of at most 128 entries (the row length measured at ahip_neigh_update* bounds every degree; tile shape and tile count are
  * decided on the device), after the model kernel has been enqueued on the wide fused paths (number of centres with more than 64 edges),
- * before the model on the layer-at-a-time path, and in the getters (ahip_get_edges, ahip_last_max_degree, ahip_last_tile_occupancy).
+ * before the model on the layer-at-a-time path, and in the getters (ahip_get_edges, ahip_last_max_degree, ahip_last_heavy_centres, ahip_last_tile_occupancy).
  * With outputs registered through ahip_output_register the call additionally keeps host copies of them
  * (pair_nequip_allegro_kokkos.cpp:342-344) and synchronises the stream. */
 int ahip_compute_dev(ahip_model *m, int nlocal, int nghost, const double *x_dev, const int *mtype_dev,
@@ -221,6 +226,10 @@ const char *ahip_last_path(ahip_model *m);
 const char *ahip_arith_note(const ahip_model *m);
 /* Largest number of edges of any centre atom in the last compute. */
 int ahip_last_max_degree(ahip_model *m);
+/* Centres, and their edges, that the last compute evaluated on the layer-at-a-time kernels BESIDE a fused kernel: the centres with more than 64 edges of the
+ * l_max = 2 kernels, and with option dense_centres=split those of every fused kernel behind list rows of more than 128 entries.  0 / 0 when there were none
+ * or the path was not a fused one.  Waits for the edge build's counters when they are still in flight, like ahip_last_max_degree. */
+int ahip_last_heavy_centres(ahip_model *m, int *ncentres, long long *nedges);
 
 /* Diagnostic: single-wave self-test of the fused path's register-chain MFMA primitive,
  * out[32][N] = in[32][K] @ W[K][N] (W row-major f64, in/out f32 host buffers). */

@@ -33,7 +33,7 @@ SYMBOLS = [
     "ahip_set_option", "ahip_get_timing_counts", "ahip_last_tile_occupancy", "ahip_neigh_update", "ahip_neigh_update_csr", "ahip_neigh_update_dev",
     "ahip_compute", "ahip_compute_dev", "ahip_output_register", "ahip_output_get", "ahip_get_edges", "ahip_debug_dump_edges", "ahip_get_timings",
     "ahip_compute_dev_range", "ahip_last_list_size", "ahip_neigh_update_dev_table", "ahip_map_types_dev", "ahip_reneighbor_flag_dev",
-    "ahip_last_path", "ahip_last_max_degree", "ahip_debug_fused_linear", "ahip_debug_fused_edges", "ahip_build_neighbors_dev", "ahip_nve_dev", "ahip_nve_first_dev",
+    "ahip_last_path", "ahip_last_max_degree", "ahip_last_heavy_centres", "ahip_debug_fused_linear", "ahip_debug_fused_edges", "ahip_build_neighbors_dev", "ahip_nve_dev", "ahip_nve_first_dev",
     "ahip_model_allow_tf32", "ahip_comm_unique_id", "ahip_comm_create_rccl", "ahip_comm_create_hosted", "ahip_comm_rccl_version", "ahip_comm_free", "ahip_comm_set_plan", "ahip_comm_set_plan_local",
     "ahip_comm_forward", "ahip_comm_reverse", "ahip_comm_allreduce", "ahip_comm_selftest", "ahip_fill_zero_dev", "ahip_borders_local_dev", "ahip_arith_note", "ahip_comm_borders", "ahip_comm_migrate",
 ]
@@ -73,6 +73,7 @@ class Library:
         L.ahip_arith_note.restype = C.c_char_p
         L.ahip_arith_note.argtypes = [C.c_void_p]
         L.ahip_last_max_degree.argtypes = [C.c_void_p]
+        L.ahip_last_heavy_centres.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         L.ahip_output_register.argtypes = [C.c_void_p, C.c_char_p]
         L.ahip_output_get.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.c_longlong, C.POINTER(C.c_longlong)]
         L.ahip_device_count.argtypes = [C.POINTER(C.c_int)]
@@ -355,6 +356,13 @@ class Model:
     @property
     def last_max_degree(self) -> int:
         return int(self.L.lib.ahip_last_max_degree(self.h))
+
+    @property
+    def last_heavy_centres(self):
+        """(centres, their edges) the last evaluation handed to the layer-at-a-time kernels beside a fused kernel; (0, 0) when none or not a fused path."""
+        n = C.c_int(0); e = C.c_longlong(0)
+        self.L.check(self.L.lib.ahip_last_heavy_centres(self.h, C.byref(n), C.byref(e)))
+        return n.value, e.value
 
     # ---- `compute allegro` outputs (pair_nequip_allegro.cpp:403-406,681-684) ---------------------
     def output_register(self, name: str) -> None:

@@ -199,7 +199,8 @@ void ahip_model_free(ahip_model *m) {
   if (m->rcut_model_dev) (void)hipFree(m->rcut_model_dev);
   for (DevBuf *b : {&m->b_flagwork, &m->b_ilist, &m->b_nloff, &m->b_nlj, &m->b_x, &m->b_ftype, &m->b_mtype, &m->b_f, &m->b_eatom,
                     &m->b_engvir, &m->b_cutsq, &m->b_cnt, &m->b_eoff, &m->b_eii, &m->b_ej, &m->b_rvec, &m->b_ett, &m->b_partial,
-                    &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom})
+                    &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom,
+                    &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist})
     b->release();
   for (auto &t : m->slots) for (auto &e : t.ring) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (hipEvent_t e : m->f_events) (void)hipEventDestroy(e);
@@ -270,6 +271,8 @@ int ahip_set_option(ahip_model *m, const char *key, const char *value) {
       m->opt_edge_schedule = (Model::EdgeSchedule)word(Model::EDGE_SCHEDULE_WORDS);
     } else if (k == "tile_pack") {
       m->opt_tile_pack = (Model::TilePack)word(Model::TILE_PACK_WORDS);
+    } else if (k == "dense_centres") {
+      m->opt_dense_centres = (Model::DenseCentres)word(Model::DENSE_CENTRES_WORDS);
     } else if (k == "timing") {
       m->timing = (v == "1" || v == "on" || v == "true");
     } else throw ArgError("unknown option '" + k + "'");
@@ -597,6 +600,42 @@ static FusedFamily fused_family(const Model &m, std::string *why) {
   return FusedFamily::none;
 }
 
+static bool fused_run_family(ahip_model *m, FusedFamily fam, const ComputeArgs &a, std::string *why) {
+  if (fam == FusedFamily::k_fused) return fused_run(*m, a, why);
+  if (fam == FusedFamily::lx32) return fusedlx_run(*m, a, why);
+  if (fam == FusedFamily::lx64) return fusedlx2_run(*m, a, why);
+  return false;
+}
+// Option dense_centres=split behind the two-pass edge build, which has listed m->nheavy > 0 heavy centres: the fused kernel runs on the compact copy of the list
+// WITHOUT them (edges.hip: edges_compact_light), swapped in for the duration of its run.  To the kernel's host driver that copy is an ordinary two-pass list with its
+// counts on the host: its largest degree is the largest LIGHT degree, so k_fused picks the 4- or 8-wave tile shape from that, the stand-alone packing kernels give
+// every slot to a light centre, and no kernel's device code knows about heavy centres.  Everything is restored before heavy_generic evaluates the listed centres.
+static bool fused_run_light(ahip_model *m, FusedFamily fam, const ComputeArgs &a, std::string *why) {
+#ifndef AHIP_HOST_EMU                        // (the host-emulation build has no fused kernel and never gets here)
+  edges_compact_light(*m, a);
+#endif
+  auto swap_in = [&]() {
+    std::swap(m->b_eoff, m->lt_eoff); std::swap(m->b_eii, m->lt_eii); std::swap(m->b_ej, m->lt_ej); std::swap(m->b_rvec, m->lt_rvec);
+  };
+  const int *il = m->d_ilist;
+  const int inum = m->inum, nheavy = m->nheavy, thresh = m->heavy_thresh, maxdeg = m->last_max_deg;
+  const long long ne = m->nedges;
+  auto restore = [&]() {
+    swap_in();
+    m->d_ilist = il; m->inum = inum; m->nedges = ne; m->nheavy = nheavy; m->heavy_thresh = thresh; m->last_max_deg = maxdeg;
+    m->have_ett = false;                     // the packed edge types written for the fused kernel belong to the copy
+  };
+  swap_in();
+  m->d_ilist = m->lt_ilist.as<int>();
+  m->inum = inum - nheavy; m->nedges = ne - m->heavy_listed_edges; m->nheavy = 0; m->heavy_thresh = 0; m->last_max_deg = m->light_max_deg;
+  bool ok = false;
+  try { ok = fused_run_family(m, fam, a, why); }
+  catch (...) { restore(); throw; }
+  m->last_tile_edges = m->nedges;
+  restore();
+  return ok;
+}
+
 static void run_model_once(ahip_model *m, const ComputeArgs &a);
 // dispatch with the auto fallback: a prepare step that finds the model outside the f16x2 split's reach (ArithDegraded) costs one more dispatch, on f32
 static void run_model_dispatch(ahip_model *m, const ComputeArgs &a) {
@@ -683,6 +722,7 @@ static void run_model(ahip_model *m, const ComputeArgs &a) {
 }
 static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   m->nedges = 0;
+  m->last_heavy_centres = 0; m->last_heavy_edges = 0; m->last_tile_edges = -1;
   // W restarts with every dispatch: it always belongs to the evaluation whose forces reach f (self-check passes, ArithDegraded re-dispatch, float32 fallback)
   if (a.vatom) AHIP_CHECK(hipMemsetAsync(a.vatom, 0, (size_t)(a.nlocal + a.nghost) * 9 * sizeof(double), a.stream));
   const bool f64 = model_runs_f64(*m);
@@ -714,7 +754,15 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
     else if (wide) { m->pack_slots = LX_TILE_SLOTS; m->pack_maxa = LX_TILE_MAXA; }
   }
   m->tiles_packed = false;
-  if (!edges_build_f32(*m, a)) { m->nheavy = 0; m->heavy_thresh = 0; AHIP_CHECK(hipMemsetAsync(a.engvir, 0, 7 * sizeof(double), a.stream)); build_edges<float>(*m, a); }
+  const bool two_pass = !edges_build_f32(*m, a);
+  if (two_pass) {
+    m->nheavy = 0; m->heavy_thresh = 0;
+    AHIP_CHECK(hipMemsetAsync(a.engvir, 0, 7 * sizeof(double), a.stream));
+    // option dense_centres=split: the two-pass build lists the heavy centres of the fused family that will run as well (k_fused: more edges than its 8-wave tile
+    // holds; the wide kernels: as on the single-pass route) and leaves heavy_thresh, nheavy and the largest light degree on the host with its own counts
+    const bool split = m->opt_dense_centres == Model::DenseCentres::Split && fam != FusedFamily::none;
+    build_edges<float>(*m, a, split ? (wide ? LX_TILE_SLOTS : FUSED_MAX_TILE_SLOTS) : 0);
+  }
 #ifdef AHIP_EXPERIMENT_SWITCHES      // never in the product build: a switch that skips the model returns no forces
   static const bool edges_only = std::getenv("AHIP_EDGES_ONLY") != nullptr;     // timing experiments on the edge build alone
   if (edges_only) { m->last_path = "edges_only"; return; }
@@ -722,16 +770,24 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   bool fused_ok = false;
   if (m->opt_path != Model::Path::Generic) {
     m->arith.last = AR_F32;
-    if (fam == FusedFamily::k_fused) fused_ok = fused_run(*m, a, &why);
-    else if (fam == FusedFamily::lx32) fused_ok = fusedlx_run(*m, a, &why);
-    else if (fam == FusedFamily::lx64) fused_ok = fusedlx2_run(*m, a, &why);
+    // heavy centres listed by the two-pass build (dense_centres=split; the single-pass build leaves its counts in flight): the give-up rule of the wide kernels
+    // (fused_lx_common.h: lx_list_fits) for every family, else the fused kernel on the list without them
+    const bool light = two_pass && m->nheavy > 0;
+    if (light && (long long)m->nheavy * 8 > m->inum)
+      why = std::to_string(m->nheavy) + " of " + std::to_string(m->inum) + " centres have more than " + std::to_string(m->heavy_thresh) +
+            " edges (dense_centres=split hands over at most one centre in eight)";
+    else if (light) fused_ok = fused_run_light(m, fam, a, &why);
+    else fused_ok = fused_run_family(m, fam, a, &why);
     if (!fused_ok && m->opt_path == Model::Path::Fused) throw UnsupportedError("fused path unavailable: " + why);
   }
   if (fused_ok) {
     // wide kernels: the number of centres left to the layer-at-a-time kernels is read now, with the model kernel already enqueued
-    // (the copy sits in front of it in the stream, so the host waits for the edge build only); k_fused (heavy_thresh = 0) never asks
+    // (the copy sits in front of it in the stream, so the host waits for the edge build only); k_fused never asks (heavy_thresh = 0, or the two-pass build's counts, which are on the host)
     if (m->heavy_thresh > 0) edges_counts(*m);
-    if (m->nheavy > 0) heavy_generic(m, a);
+    if (m->nheavy > 0) {
+      heavy_generic(m, a);
+      m->last_heavy_centres = m->nheavy; m->last_heavy_edges = m->hv_nedges;
+    }
     // "fused_tf32eq": the two-term bf16 split the model file licensed with allow_tf32 = 1 (fused.hip); everything else is float32-exact
     // "fused_f16x2" / "fused_bf16x3": float32-equivalent splits on the f16 / bf16 matrix cores (fused_h.h, fused.hip); "fused_f32": exact fmaf chains
     m->last_path = fused_path_name(m->arith.last);
@@ -1129,7 +1185,8 @@ extern "C" int ahip_last_tile_occupancy(ahip_model *m, long long *slots_used, lo
     int nt = 0;
     AHIP_CHECK(hipMemcpy(&nt, m->d_ntiles_last, sizeof(int), hipMemcpyDeviceToHost));
     const int slots = m->last_tile_slots ? m->last_tile_slots : (m->last_max_deg <= 64 ? 64 : 128);
-    *slots_used = m->nedges; *slots_total = (long long)nt * slots;
+    *slots_used = m->last_tile_edges >= 0 ? m->last_tile_edges : m->nedges;      // (dense_centres=split behind the two-pass edge build: the tiles hold the light centres only)
+    *slots_total = (long long)nt * slots;
   });
 }
 
@@ -1141,6 +1198,15 @@ extern "C" int ahip_last_max_degree(ahip_model *m) {
   if (!m) return 0;
   if (guarded([&] { edges_counts(*m); }) != 0) return -1;
   return m->last_max_deg;
+}
+
+int ahip_last_heavy_centres(ahip_model *m, int *ncentres, long long *nedges) {
+  return guarded([&] {
+    require_model(m);
+    if (!ncentres || !nedges) throw ArgError("ahip_last_heavy_centres: NULL argument");
+    edges_counts(*m);
+    *ncentres = m->last_heavy_centres; *nedges = m->last_heavy_edges;
+  });
 }
 
 int ahip_build_neighbors_dev(ahip_model *m, int nlocal, int nall, const double *x_dev, const double *lo,

@@ -322,6 +322,7 @@ __global__ void __launch_bounds__(EB_THREADS) k_build_edges(int inum, const int 
 static constexpr int BACK_N = 8;
 struct EdgeState {
   DevBuf flags, heavy, hoff, xt; int ncu = 0, occ[2] = {1, 1};
+  int *h_heavy = nullptr;                  // pinned: header words [3] .. [6] of the two-pass route's heavy list (edges_list_heavy)
   int *h_back = nullptr; hipEvent_t ev_back[BACK_N] = {}, chain = nullptr; bool unchecked[BACK_N] = {}; int cur = 0;
 };
 // Looks at slot k's overflow word once its copy has completed (wait: block until it has).  A set flag means a list row was longer than the bound measured at the
@@ -357,6 +358,110 @@ static __global__ void k_heavy_copy(int nh, const int *heavy, const int *ilist, 
     h_rvec[3 * (size_t)(o + q) + 1] = rvec[3 * (size_t)(e0 + q) + 1];
     h_rvec[3 * (size_t)(o + q) + 2] = rvec[3 * (size_t)(e0 + q) + 2];
   }
+}
+
+// ---- option dense_centres=split behind the TWO-PASS edge build (rows of more than 128 entries): the heavy list from the finished edge offsets ----
+// One workgroup; thread t owns the centres [t * per, (t + 1) * per), at least HL_MIN_PER of them (small lists walk like large ones).  It counts its heavy centres (degree > thresh) and their edges, a block scan turns the counts
+// into the thread's first position in the list, and a second walk writes the list -- so the list is in ascending centre order whatever the launch, unlike the
+// single-pass build's (an atomic counter).  Results go where the single-pass build puts them: heavy[], hdr[3] = their number; and beside them hpre[k] = edges of the
+// listed centres before the k-th (hpre[n] = their total), hdr[5] = that total, hdr[6] = the largest degree among the centres NOT listed.
+static constexpr int HL_THREADS = 1024, HL_MIN_PER = 4;
+static __global__ void __launch_bounds__(HL_THREADS) k_list_heavy(int inum, const int *__restrict__ eoff, int thresh, int *__restrict__ heavy,
+                                                                  int *__restrict__ hpre, int *__restrict__ hdr) {
+  __shared__ int s_n[HL_THREADS], s_e[HL_THREADS];
+  __shared__ int s_mx;
+  const int tid = threadIdx.x;
+  const int per = max(HL_MIN_PER, (inum + HL_THREADS - 1) / HL_THREADS);
+  const int b = (int)min((long long)inum, (long long)tid * per), e = (int)min((long long)inum, (long long)b + per);
+  if (tid == 0) s_mx = 0;
+  int n = 0, he = 0, mx = 0;
+  for (int ii = b; ii < e; ++ii) {
+    const int d = eoff[ii + 1] - eoff[ii];
+    if (d > thresh) { ++n; he += d; } else mx = max(mx, d);
+  }
+  s_n[tid] = n; s_e[tid] = he;
+  __syncthreads();
+  if (mx > 0) atomicMax(&s_mx, mx);
+  for (int off = 1; off < HL_THREADS; off <<= 1) {          // inclusive scan of both counts (Hillis-Steele over the block)
+    const int vn = tid >= off ? s_n[tid - off] : 0, ve = tid >= off ? s_e[tid - off] : 0;
+    __syncthreads();
+    s_n[tid] += vn; s_e[tid] += ve;
+    __syncthreads();
+  }
+  int kn = s_n[tid] - n, ke = s_e[tid] - he;
+  for (int ii = b; ii < e; ++ii) {
+    const int d = eoff[ii + 1] - eoff[ii];
+    if (d > thresh) { heavy[kn] = ii; hpre[kn] = ke; ++kn; ke += d; }
+  }
+  if (tid == HL_THREADS - 1) { hpre[s_n[tid]] = s_e[tid]; hdr[3] = s_n[tid]; hdr[5] = s_e[tid]; hdr[6] = s_mx; }
+}
+void edges_list_heavy(Model &m, const ComputeArgs &a, int thresh) {
+  if (!m.edge_state) m.edge_state = new EdgeState();
+  EdgeState &st = *(EdgeState *)m.edge_state;
+  if (!st.h_heavy) AHIP_CHECK(hipHostMalloc((void **)&st.h_heavy, 4 * sizeof(int), hipHostMallocDefault));
+  const int inum = m.inum;
+  st.flags.reserve(64);
+  st.heavy.reserve((size_t)std::max(inum, 1) * sizeof(int));
+  st.hoff.reserve((size_t)(inum + 1) * sizeof(int));
+  int *hdr = st.flags.as<int>();
+  hipLaunchKernelGGL(k_list_heavy, dim3(1), dim3(HL_THREADS), 0, a.stream, inum, m.b_eoff.as<int>(), thresh, st.heavy.as<int>(), st.hoff.as<int>(), hdr);
+  AHIP_CHECK(hipGetLastError());
+  AHIP_CHECK(hipMemcpyAsync(st.h_heavy, hdr + 3, 4 * sizeof(int), hipMemcpyDeviceToHost, a.stream));      // heavy centres, (unused), their edges, largest light degree
+}
+void edges_list_heavy_counts(Model &m, int thresh) {
+  const EdgeState &st = *(const EdgeState *)m.edge_state;
+  m.heavy_thresh = thresh;
+  m.nheavy = st.h_heavy[0];
+  m.heavy_listed_edges = st.h_heavy[2];
+  m.light_max_deg = st.h_heavy[3];
+}
+
+// ---- ... and the compact copy of the list WITHOUT the listed centres, the list a fused kernel then runs on: a tile is a run of consecutive centres and of
+// consecutive edges, so a centre cannot be left out of the tiles of the list it is in.  The list is ascending: position and first edge of a light centre in the
+// copy follow from the number of listed centres below it (binary search) and their edges (hpre). ----
+__device__ __forceinline__ int heavy_below(const int *__restrict__ heavy, int nh, int ii) {      // number of listed centres < ii
+  int lo = 0, hi = nh;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (heavy[mid] < ii) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+static __global__ void k_light_centres(int inum, int nh, const int *__restrict__ heavy, const int *__restrict__ hpre, const int *__restrict__ ilist,
+                                       const int *__restrict__ eoff, int *__restrict__ l_ilist, int *__restrict__ l_eoff) {
+  const int ii = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ii > inum) return;
+  const int r = heavy_below(heavy, nh, ii);
+  if (ii == inum) { l_eoff[inum - nh] = eoff[inum] - hpre[nh]; return; }
+  if (r < nh && heavy[r] == ii) return;
+  l_ilist[ii - r] = ilist[ii];
+  l_eoff[ii - r] = eoff[ii] - hpre[r];
+}
+static __global__ void k_light_edges(long long E, int nh, const int *__restrict__ heavy, const int *__restrict__ hpre, const int *__restrict__ e_ii,
+                                     const int *__restrict__ e_j, const float *__restrict__ rvec, int *__restrict__ l_eii, int *__restrict__ l_ej,
+                                     float *__restrict__ l_rvec) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  const int ii = e_ii[e], r = heavy_below(heavy, nh, ii);
+  if (r < nh && heavy[r] == ii) return;
+  const long long d = e - hpre[r];
+  l_eii[d] = ii - r;
+  l_ej[d] = e_j[e];
+  l_rvec[3 * d] = rvec[3 * e]; l_rvec[3 * d + 1] = rvec[3 * e + 1]; l_rvec[3 * d + 2] = rvec[3 * e + 2];
+}
+void edges_compact_light(Model &m, const ComputeArgs &a) {
+  EdgeState &st = *(EdgeState *)m.edge_state;
+  const int inum = m.inum, nh = m.nheavy;
+  const long long E = m.nedges;
+  const size_t El = (size_t)std::max<long long>(E - m.heavy_listed_edges, 1);
+  m.lt_ilist.reserve((size_t)std::max(inum - nh, 1) * sizeof(int));
+  m.lt_eoff.reserve((size_t)(inum - nh + 2) * sizeof(int));
+  m.lt_eii.reserve(El * sizeof(int));
+  m.lt_ej.reserve(El * sizeof(int));
+  m.lt_rvec.reserve(El * 3 * sizeof(float));
+  hipLaunchKernelGGL(k_light_centres, dim3((inum + 1 + 255) / 256), dim3(256), 0, a.stream, inum, nh, st.heavy.as<int>(), st.hoff.as<int>(), m.d_ilist,
+                     m.b_eoff.as<int>(), m.lt_ilist.as<int>(), m.lt_eoff.as<int>());
+  if (E > 0)
+    hipLaunchKernelGGL(k_light_edges, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, a.stream, E, nh, st.heavy.as<int>(), st.hoff.as<int>(), m.b_eii.as<int>(),
+                       m.b_ej.as<int>(), m.b_rvec.as<float>(), m.lt_eii.as<int>(), m.lt_ej.as<int>(), m.lt_rvec.as<float>());
+  AHIP_CHECK(hipGetLastError());
 }
 
 static __global__ void k_max_row(int inum, const int *off, int *out) {
@@ -511,6 +616,7 @@ void edges_free(Model &m) {
   st->heavy.release();
   st->hoff.release();
   if (st->h_back) (void)hipHostFree(st->h_back);
+  if (st->h_heavy) (void)hipHostFree(st->h_heavy);
   for (int k = 0; k < BACK_N; ++k) if (st->ev_back[k]) (void)hipEventDestroy(st->ev_back[k]);
   if (st->chain) (void)hipEventDestroy(st->chain);
   delete st;

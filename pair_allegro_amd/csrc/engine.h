@@ -112,6 +112,8 @@ struct Model {
   static constexpr const char *TILE_PACK_WORDS = "auto|separate|fused";
   enum class EdgeSchedule { Auto, Static, Dynamic };
   static constexpr const char *EDGE_SCHEDULE_WORDS = "auto|static|dynamic";
+  enum class DenseCentres { Whole, Split };
+  static constexpr const char *DENSE_CENTRES_WORDS = "whole|split";
   Path opt_path = Path::Auto;
   Precision opt_precision = Precision::Model;
   FusedTb opt_fused_tb = FusedTb::Table;    // table | mlp: two-body embedding of the fused kernel from the spline table or as an MLP
@@ -126,6 +128,7 @@ struct Model {
   bool timing = false;
   TilePack opt_tile_pack = TilePack::Auto;  // auto | separate | fused (auto = fused up to 262 144 centres per call): tile packing inside the single-pass edge build where the tile shape is known up front, or always by the stand-alone kernels (A/B, tests)
   EdgeSchedule opt_edge_schedule = EdgeSchedule::Auto;   // auto | static | dynamic: unit schedule of the single-pass edge build (edges.hip)
+  DenseCentres opt_dense_centres = DenseCentres::Whole;   // whole | split: a list with a few centres above a fused kernel's tile goes to the layer-at-a-time kernels as a whole, or only those centres do (allegro_hip.hip: run_model_once)
   bool cutoff_strict = false;               // edge kept iff rsq < cut^2 (the KOKKOS reference path) instead of rsq <= cut^2 (the host path)
 
   // weights
@@ -177,6 +180,15 @@ struct Model {
   int heavy_thresh = 0, nheavy = 0;
   long long hv_nedges = 0;
   DevBuf hv_eoff, hv_eii, hv_ej, hv_rvec, hv_ilist, hv_engvir;
+  // option dense_centres=split behind the two-pass edge build (edges.hip: edges_list_heavy): edge total of the listed centres and the largest degree among the
+  // others, read back with the build's own counts; lt_*: the compact copy of the list WITHOUT the listed centres that the fused kernel then runs on
+  long long heavy_listed_edges = 0;
+  int light_max_deg = 0;
+  DevBuf lt_eoff, lt_eii, lt_ej, lt_rvec, lt_ilist;
+  // what the last evaluation handed to the layer-at-a-time kernels beside a fused kernel (ahip_last_heavy_centres), and the edges its tiles held when that is
+  // not the whole list (-1: it is)
+  int last_heavy_centres = 0;
+  long long last_heavy_edges = 0, last_tile_edges = -1;
 
   // `compute allegro`: registered output names and their values from the last host-path compute
   std::vector<std::string> custom_names;
@@ -250,6 +262,7 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why);
 void fused_free(Model &m);
 // Tile shapes (edge slots, centres) the single-pass edge build packs for (allegro_hip.hip: run_model_once); the kernel files static_assert their own shapes against them
 inline constexpr int FUSED_TILE_SLOTS = 64, FUSED_TILE_MAXA = 6;     // k_fused, 4-wave tiles
+inline constexpr int FUSED_MAX_TILE_SLOTS = 128;                     // k_fused, 8-wave tiles: the edge count above which a centre is "heavy" for it (option dense_centres=split)
 inline constexpr int LX_TILE_SLOTS = 64, LX_TILE_MAXA = 4;           // k_fused_lx and k_fused_lx2; also the edge count above which a centre is "heavy"
 // f16x2 arithmetic (fused_h.h): device address of the model's alarm word (allocated on first use); fused_poll_alarm throws StateError when a kernel has
 // raised it -- the host-pointer call polls behind its own synchronisation, device-resident callers meet it at their next evaluation
@@ -332,6 +345,13 @@ int edges_max_row(Model &m, int inum, const int *offsets_dev);
 void edges_free(Model &m);
 // compact copy (m.hv_*) of the edges of the m.nheavy centres the last edges_build_f32 listed
 void edges_compact_heavy(Model &m, const ComputeArgs &a);
+// Option dense_centres=split on the two-pass route (generic_engine.h: build_edges).  edges_list_heavy enqueues, behind the scan of the edge counts, the kernel that
+// lists the centres with more than `thresh` edges -- ascending, into the buffers and header words the single-pass build fills -- and the copy of its counts;
+// edges_list_heavy_counts installs them (heavy_thresh, nheavy, heavy_listed_edges, light_max_deg) once build_edges has waited for its own read-back.
+// edges_compact_light: compact copy (m.lt_*) of the list without those centres.  (Not in the host-emulation build: no fused kernel there.)
+void edges_list_heavy(Model &m, const ComputeArgs &a, int thresh);
+void edges_list_heavy_counts(Model &m, int thresh);
+void edges_compact_light(Model &m, const ComputeArgs &a);
 
 // ---- float32 dense layers of the generic path on the matrix cores (gemm.hip; the host-emulation build links a stub
 // returning false and keeps the one-thread-per-output kernels) ----

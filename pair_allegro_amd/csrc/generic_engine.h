@@ -45,7 +45,8 @@ template <typename T> static void free_weights(DeviceWeights<T> &dw) {
 
 // ---- edge build: K1/K2/K5 of the reference's Kokkos path, a2-a4 of SURVEY section 8 -------------
 // After this: m.nedges, m.b_eoff (int[inum+1]), m.b_eii, m.b_ej, m.b_rvec (T[E][3]).
-template <typename T> static void build_edges(Model &m, const ComputeArgs &a) {
+// heavy_thresh > 0 (option dense_centres=split, allegro_hip.hip): the centres with more edges are listed as well (edges.hip), their counts ride on the read-back below.
+template <typename T> static void build_edges(Model &m, const ComputeArgs &a, int heavy_thresh = 0) {
   StageTimer tm(m, "edge_build", a.stream);
   const int inum = m.inum;
   m.b_cnt.reserve((size_t)(inum + 1) * sizeof(int));
@@ -55,6 +56,9 @@ template <typename T> static void build_edges(Model &m, const ComputeArgs &a) {
   AHIP_CHECK(prim_exclusive_scan_i32(m.prim, m.b_cnt.as<int>(), m.b_eoff.as<int>(), inum, a.stream));
   m.b_misc.reserve(64);
   AHIP_CHECK(prim_max_i32(m.b_cnt.as<int>(), inum, m.b_misc.as<int>(), a.stream));
+#ifndef AHIP_HOST_EMU
+  if (heavy_thresh > 0) edges_list_heavy(m, a, heavy_thresh);
+#endif
   int tot = 0, mx = 0;
   // the one scalar read-back per step (the Kokkos path has the same: pair_nequip_allegro_kokkos.cpp:203-206)
   AHIP_CHECK(hipMemcpyAsync(&tot, m.b_eoff.as<int>() + inum, sizeof(int), hipMemcpyDeviceToHost, a.stream));
@@ -62,6 +66,9 @@ template <typename T> static void build_edges(Model &m, const ComputeArgs &a) {
   AHIP_CHECK(hipStreamSynchronize(a.stream));
   m.nedges = tot;
   m.last_max_deg = mx;
+#ifndef AHIP_HOST_EMU
+  if (heavy_thresh > 0) edges_list_heavy_counts(m, heavy_thresh);
+#endif
   const size_t E = (size_t)std::max(tot, 1);
   m.b_eii.reserve(E * sizeof(int));
   m.b_ej.reserve(E * sizeof(int));
