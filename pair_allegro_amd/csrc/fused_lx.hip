@@ -41,11 +41,16 @@ struct ShapeX {
   static constexpr int STG_LD = D * 16 + 4;             // one K-tile of a slot: [lm][16] + pad (16-byte rows, conflict-free b128 writes)
   static constexpr int ENVA = D * U + 4;                // environment row of one centre: [lm][u] + pad
   static constexpr int NP = CgX<L>::NP;
-  // scratch rows (per wave, 1 KiB each): d x0/dd 4 | w0 EW | per layer: omega EW, silu'(z1) 4, silu'(z2) 4, u 4, V_in D*UT
-  static constexpr int R_DX0 = 0, R_W0 = 4, LSZ = EW + 12 + D * UT;
-  __host__ __device__ static constexpr int R_LAYER(int kk) { return 4 + EW + kk * LSZ; }
-  __host__ __device__ static constexpr int R_TOTAL(int NL) { return 4 + EW + NL * LSZ; }
-  static constexpr int O_OM = 0, O_Z1 = EW, O_Z2 = EW + 4, O_U = EW + 8, O_VIN = EW + 12;
+  // scratch rows (per wave, 1 KiB each): d x0/dd 4 | w0 EW | per layer: omega EW, hidden layers 1..MD 4 each, u 4, V_in D*UT  (fused_lx_rows.h; MD = latent MLP depth)
+  using R = RowsX;
+  static_assert(R::EW == EW && R::NV == D * UT, "row map of this shape");
+  static constexpr int R_DX0 = R::R_DX0, R_W0 = R::R_W0, O_OM = R::O_OM;
+  __host__ __device__ static constexpr int O_Z(int h) { return R::O_Z(h); }
+  __host__ __device__ static constexpr int O_U(int MD) { return R::O_U(MD); }
+  __host__ __device__ static constexpr int O_VIN(int MD) { return R::O_VIN(MD); }
+  __host__ __device__ static constexpr int LSZ(int MD) { return R::LSZ(MD); }
+  __host__ __device__ static constexpr int R_LAYER(int kk, int MD) { return R::R_LAYER(kk, MD); }
+  __host__ __device__ static constexpr int R_TOTAL(int NL, int MD) { return R::R_TOTAL(NL, MD); }
 };
 
 struct __attribute__((aligned(16))) LdsX {
@@ -146,12 +151,19 @@ enum { PX_GEOM = 0, PX_EMB, PX_ENV, PX_TP, PX_LAT, PX_MIX, PX_OUT, PX_BLAT, PX_B
 // NLT = number of layers: the layer loops are unrolled so that `last layer` / `first layer` are compile-time facts -- with
 // run-time branches inside them the register allocator shuffles dozens of spill slots at every join (load, wait, store).
 // VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
-template <int NLT, bool PROF, int AR, bool VA = false>
+// MD: hidden layers of the latent MLP (allegro_mlp_hidden_layers_depth; 2 in the reference test YAML).  1 and 3 exist on the f16x2 arithmetic only, as in k_fused;
+// every MD-dependent piece below is `if constexpr`, and the MD = 2 instances are what they were before the parameter existed.
+template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2>
 __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) {
   constexpr int L = ShapeX::L, UT = ShapeX::UT, NW = ShapeX::NW;
   using S = ShapeX;
   constexpr int NTHREADS = NW * 64, D = S::D, U = S::U, EW = S::EW, MAXA = S::MAXA, STG_LD = S::STG_LD, ENVA = S::ENVA, NP = S::NP;
   constexpr bool SAVEZ = AR == 3;          // f16x2: raw pre-activation rows of the last hidden layer instead of silu' rows, no u rows (see fused.hip)
+  static_assert(MD >= 1 && MD <= 3 && (MD == 2 || AR == 3), "latent MLP depth 1 / 3: f16x2 instances only");
+  static_assert(MD == 2 || !PROF, "profiled instances: depth 2");
+  // The last model layer keeps its latent-MLP rows in the staging tile: the last hidden layer in images ZIMG .. ZIMG + 3, the one below it (MD >= 2) in images 0..3.
+  // A wave's slots hold 9 images; depth 3 would need 12, so the silu' rows of its hidden layer 1 go to the per-wave scratch like a non-last layer's.
+  constexpr int ZIMG = MD == 1 ? 0 : 4;
   // last-layer rows in LDS (LdsX::rowsl, stage[0] images): LDS rows [0, NOML) = omega l >= 1, [NOML, NLROW) = the first NVL rows of the input tensor
   constexpr int NLROW = LdsX::NLROW, NOML = L * UT, NVL = (NLROW - NOML) < D * UT ? (NLROW - NOML) : D * UT;
   static_assert(NOML <= NLROW, "omega rows of the last layer fit the LDS rows");
@@ -285,7 +297,7 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
 #pragma unroll
     for (int kk = 0; kk < NL; ++kk) {
       const bool last = (kk == NL - 1);
-      const int RL = S::R_LAYER(kk);
+      const int RL = S::R_LAYER(kk, MD);
       float *const envk = lds.env[kk];
       {
         f32x4 om[EW];
@@ -360,19 +372,37 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
         for (int t = 0; t < 4; ++t) cat[t] = x[t];
 #pragma unroll
         for (int t = 0; t < UT; ++t) cat[4 + t] = sc[t];
-        if (last) {          // the last layer's rows: images 0..3 / 4..7 of the wave's own slots of stage[0] (idle until this layer's backward tensor product)
-          lx_lin<AR, 4 + UT, 4, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveDL{STQ(0), 0});
-          if constexpr (SAVEZ) lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveZL{STQ(0), 4});
-          else lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveDL{STQ(0), 4});
+        if constexpr (MD == 2) {
+          if (last) {          // the last layer's rows: images 0..3 / 4..7 of the wave's own slots of stage[0] (idle until this layer's backward tensor product)
+            lx_lin<AR, 4 + UT, 4, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveDL{STQ(0), 0});
+            if constexpr (SAVEZ) lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveZL{STQ(0), 4});
+            else lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveDL{STQ(0), 4});
+          } else {
+            lx_lin<AR, 4 + UT, 4, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveD{SB, RL + S::O_Z(1), v16});
+            if constexpr (SAVEZ) lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveZ{SB, RL + S::O_Z(2), v16});
+            else lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveD{SB, RL + S::O_Z(2), v16});
+          }
+        } else if constexpr (MD == 1) {
+          // the only hidden layer is the last one: raw z rows (images 0..3 in the last model layer)
+          if (last) lx_lin<AR, 4 + UT, 4, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveZL{STQ(0), ZIMG});
+          else lx_lin<AR, 4 + UT, 4, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveZ{SB, RL + S::O_Z(1), v16});
         } else {
-          lx_lin<AR, 4 + UT, 4, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveD{SB, RL + S::O_Z1, v16});
-          if constexpr (SAVEZ) lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveZ{SB, RL + S::O_Z2, v16});
-          else lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveD{SB, RL + S::O_Z2, v16});
+          // hidden layer 1: silu' rows to scratch in every model layer (see ZIMG); 2: silu' rows, 3: raw z rows -- in the last model layer images 0..3 / 4..7.
+          // The chain ping-pongs z / z2: hidden layer 3's output is back in z.
+          lx_lin<AR, 4 + UT, 4, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveD{SB, RL + S::O_Z(1), v16});
+          if (last) {
+            lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveDL{STQ(0), 0});
+            lx_lin<AR, 4, 4, false>(WB, wp, z2, z, v16, ring, EpiSiluSaveZL{STQ(0), ZIMG});
+          } else {
+            lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveD{SB, RL + S::O_Z(2), v16});
+            lx_lin<AR, 4, 4, false>(WB, wp, z2, z, v16, ring, EpiSiluSaveZ{SB, RL + S::O_Z(3), v16});
+          }
         }
+        f32x4 (&zl)[4] = MD == 2 ? z2 : z;              // output of the last hidden layer
         const float ra = lds.res[kk][0], rbf = lds.res[kk][1] * fc;
         f32x4 xn[4];
-        if constexpr (SAVEZ) lx_lin<AR, 4, 4, false>(WB, wp, z2, xn, v16, ring, EpiResidualNS<4>{x, ra, rbf});
-        else lx_lin<AR, 4, 4, false>(WB, wp, z2, xn, v16, ring, EpiResidual<4>{{SB, RL + S::O_U, v16}, x, ra, rbf});
+        if constexpr (SAVEZ) lx_lin<AR, 4, 4, false>(WB, wp, zl, xn, v16, ring, EpiResidualNS<4>{x, ra, rbf});
+        else lx_lin<AR, 4, 4, false>(WB, wp, zl, xn, v16, ring, EpiResidual<4>{{SB, RL + S::O_U(MD), v16}, x, ra, rbf});
 #pragma unroll
         for (int t = 0; t < 4; ++t) x[t] = xn[t];
       }
@@ -383,8 +413,8 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
       // channel mixing, in place per (l, m) row -> V^{kk+1}, saved as the next layer's V_in rows
 #ifndef ABL_NO_MIX
       if (!last) {
-        if (kk + 1 == NL - 1) mix_rows<0, D, UT, true, AR, true>(V, WB, wp, v16, ring, SB, S::R_LAYER(kk + 1) + S::O_VIN, sc, lds.rowsl[uwave], NOML, NVL);
-        else mix_rows<0, D, UT, true, AR>(V, WB, wp, v16, ring, SB, S::R_LAYER(kk + 1) + S::O_VIN, sc);
+        if (kk + 1 == NL - 1) mix_rows<0, D, UT, true, AR, true>(V, WB, wp, v16, ring, SB, S::R_LAYER(kk + 1, MD) + S::O_VIN(MD), sc, lds.rowsl[uwave], NOML, NVL);
+        else mix_rows<0, D, UT, true, AR>(V, WB, wp, v16, ring, SB, S::R_LAYER(kk + 1, MD) + S::O_VIN(MD), sc);
       }
 #endif
       PHASEX(PX_MIX);
@@ -394,7 +424,7 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
     // saved rows are requested well ahead of their first use all through the backward pass (their round trip is an L2 miss:
     // 1-2 us, and with one wave per SIMD nothing else covers it): u and silu'(z2) of the last layer under the read-out MFMAs
     f32x4 upre[4], zt[4], w0pre[L * UT];
-    if constexpr (!SAVEZ) load_rows<4>(SB, S::R_LAYER(NL - 1) + S::O_U, upre, v16);
+    if constexpr (!SAVEZ) load_rows<4>(SB, S::R_LAYER(NL - 1, MD) + S::O_U(MD), upre, v16);
     __builtin_amdgcn_sched_barrier(0);
     f32x4 zr[2];
     lx_lin<AR, 4, 2, false>(WB, wp, x, zr, v16, ring, EpiNone{});
@@ -431,7 +461,7 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
       lx_lin<AR, 2, 4, false>(WB, wp, dzr, dx, v16, ring, EpiNone{});
     }
 #pragma unroll
-    for (int t = 0; t < 4; ++t) zt[t] = stg_load(STQ(0), 4 + t);            // the last layer's second hidden layer rows, from the staging tile
+    for (int t = 0; t < 4; ++t) zt[t] = stg_load(STQ(0), ZIMG + t);         // the last layer's last hidden layer rows, from the staging tile
     float dfc_part = 0.f;
     float dY[D];
 #pragma unroll
@@ -441,15 +471,17 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
 #pragma unroll
     for (int kk = NL - 1; kk >= 0; --kk) {
       const bool last = (kk == NL - 1);
-      const int RL = S::R_LAYER(kk);
+      const int RL = S::R_LAYER(kk, MD);
       f32x4 ds[UT];
       {
         f32x4 du[4], dh[4];
-        f32x4 rows1[4];
-        if (last) {
+        f32x4 rows1[4];          // silu' of the hidden layer below the last (MD >= 2): first used one linear from here
+        if constexpr (MD >= 2) {
+          if (last) {
 #pragma unroll
-          for (int t = 0; t < 4; ++t) rows1[t] = stg_load(STQ(0), t);
-        } else load_rows<4>(SB, RL + S::O_Z1, rows1, v16);     // silu'(z1): first used one linear from here
+            for (int t = 0; t < 4; ++t) rows1[t] = stg_load(STQ(0), t);
+          } else load_rows<4>(SB, RL + S::O_Z(MD - 1), rows1, v16);
+        }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (SAVEZ) {
           // the u rows are not saved (fused.hip: SAVEZ): <u, g> falls out of the epilogue of the first backward linear, fed with the unscaled gradient
@@ -472,9 +504,22 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
           pin(dfc_part);
           lx_lin<AR, 4, 4, false>(WB, wp, du, dh, v16, ring, EpiMulRows<4>{zt});
         }
-        lx_lin<AR, 4, 4, false>(WB, wp, dh, du, v16, ring, EpiMulRows<4>{rows1});
+        // down the hidden layers: g_{h-1} = (g_h W_h^T) * silu'(z_{h-1}), then dcat = g_1 W_0^T
         f32x4 dcat[4 + UT];
-        lx_lin<AR, 4, 4 + UT, false>(WB, wp, du, dcat, v16, ring, EpiNone{});
+        if constexpr (MD == 2) {
+          lx_lin<AR, 4, 4, false>(WB, wp, dh, du, v16, ring, EpiMulRows<4>{rows1});
+          lx_lin<AR, 4, 4 + UT, false>(WB, wp, du, dcat, v16, ring, EpiNone{});
+        } else if constexpr (MD == 1) {
+          lx_lin<AR, 4, 4 + UT, false>(WB, wp, dh, dcat, v16, ring, EpiNone{});
+        } else {
+          // silu' of hidden layer 1 (scratch in every model layer): requested one linear ahead, after the stage reads of rows1 above
+          f32x4 rows0[4];
+          load_rows<4>(SB, RL + S::O_Z(1), rows0, v16);
+          __builtin_amdgcn_sched_barrier(0);
+          lx_lin<AR, 4, 4, false>(WB, wp, dh, du, v16, ring, EpiMulRows<4>{rows1});
+          lx_lin<AR, 4, 4, false>(WB, wp, du, dh, v16, ring, EpiMulRows<4>{rows0});
+          lx_lin<AR, 4, 4 + UT, false>(WB, wp, dh, dcat, v16, ring, EpiNone{});
+        }
 #pragma unroll
         for (int t = 0; t < 4; ++t) dx[t] += dcat[t];
 #pragma unroll
@@ -500,7 +545,7 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
 #pragma unroll
             for (int lm = 0; lm < D; ++lm) {
               if (last && lm * UT + t < NVL) vpre2[i & 1][lm] = *(const f32x2 *)(lds.rowsl[uwave] + (NOML + lm * UT + t) * ROW + fresh_lane() * 4 + 2 * h);
-              else vpre2[i & 1][lm] = bload_half(SB, v16 + 8 * h, (RL + S::O_VIN + lm * UT + t) * ROW * 4);
+              else vpre2[i & 1][lm] = bload_half(SB, v16 + 8 * h, (RL + S::O_VIN(MD) + lm * UT + t) * ROW * 4);
             }
           } else {
 #pragma unroll
@@ -593,8 +638,8 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
         lx_prime<AR>(WB, wp, v16, ring);          // RING_DROP: requested again only now -- the d omega / dY arithmetic above needs the registers
         // next iteration's u / silu'(z2) rows (or the l >= 1 embedding weights for the last step) under this linear
         if (kk > 0) {
-          if constexpr (!SAVEZ) load_rows<4>(SB, S::R_LAYER(kk - 1) + S::O_U, upre, v16);
-          load_rows<4>(SB, S::R_LAYER(kk - 1) + S::O_Z2, zt, v16);
+          if constexpr (!SAVEZ) load_rows<4>(SB, S::R_LAYER(kk - 1, MD) + S::O_U(MD), upre, v16);
+          load_rows<4>(SB, S::R_LAYER(kk - 1, MD) + S::O_Z(MD), zt, v16);
         } else load_rows<L * UT>(SB, S::R_W0 + UT, w0pre, v16);
         __builtin_amdgcn_sched_barrier(0);
         lx_lin<AR, EW, 4, true>(WB, wp, dom, dx, v16, ring, EpiNone{});
@@ -724,7 +769,10 @@ bool fusedlx_model_supported(const Model &m, std::string *why) {
   auto no = [&](const char *msg) { if (why) *why = msg; return false; };
   if (h.l_max != 2) return no("wide fused kernels are built for l_max = 2");
   if (!fused_widths_fit(h)) return no("wide fused kernels hold at most 64 tensor features, S=64, MLP width 64, read-out width 32 (narrower models run zero-padded)");
-  if (h.mlp_depth != 2 || h.readout_depth != 1) return no("fused kernels need MLP depth 2 and read-out depth 1");
+  if (h.mlp_depth < 1 || h.mlp_depth > 3 || h.readout_depth != 1) return no("fused kernels need MLP depth 1..3 and read-out depth 1");
+  if (h.mlp_depth != 2) {           // depth 1 and 3 on the f16x2 instances (template parameter MD of both wide kernels)
+    if (resolve_arith(m, true) != AR_F16X2) return no("MLP depth 1 / 3 runs on the f16x2 arithmetic only on the wide fused kernels (fused_arith=auto|f16x2)");
+  }
   if (h.num_bessels < 1) return no("no radial basis");      // any number of Bessel functions: the two-body embedding is always tabulated here
   if (h.num_layers < 1 || h.num_layers > LX_MAXNL) return no("fused kernels need 1..3 layers");
   if (h.num_types > 16) return no("fused kernels support at most 16 model types (4-bit packed edge types)");
@@ -735,7 +783,7 @@ bool fusedlx_model_supported(const Model &m, std::string *why) {
 static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, Arith arith) {
   using S = ShapeX;
   constexpr int L = S::L, U = S::U, D = S::D;
-  const int NL = h.num_layers;
+  const int NL = h.num_layers, MD = h.mlp_depth;      // latent MLP: lat.w0 ([x, scalars] -> 64), lat.w1 .. lat.w{MD-1} (64 -> 64), output linear lat.w{MD}
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
   auto frag = [&](const double *W, int K, int N, int ldw) {
@@ -764,8 +812,7 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
     const std::string lk = "l" + std::to_string(k + 1);
     fwd(T_(lk + ".env"), 64, U * (L + 1));
     fwd(T_(lk + ".lat.w0"), 64 + U, 64);
-    fwd(T_(lk + ".lat.w1"), 64, 64);
-    fwd(T_(lk + ".lat.w2"), 64, 64);
+    for (int hl = 1; hl <= MD; ++hl) fwd(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64);
     if (k < NL - 1) {
       const double *mx = T_(lk + ".mix");            // [L+1][U][U]; block l serves its 2l+1 components
       for (int lm = 0; lm < D; ++lm) mixfrag(mx + (size_t)l_of_lm(lm) * U * U, lm, false);
@@ -775,8 +822,7 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
   bwd(T_("out.w0"), 64, 32);
   for (int k = NL - 1; k >= 0; --k) {
     const std::string lk = "l" + std::to_string(k + 1);
-    bwd(T_(lk + ".lat.w2"), 64, 64);
-    bwd(T_(lk + ".lat.w1"), 64, 64);
+    for (int hl = MD; hl >= 1; --hl) bwd(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64);
     bwd(T_(lk + ".lat.w0"), 64 + U, 64);
     if (k < NL - 1) {
       const double *mx = T_(lk + ".mix");
@@ -793,11 +839,12 @@ bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
   if (!lx_list_fits(m, why)) return false;
   FusedLxState &st = lx_prepare<ShapeX>(m, m.fusedlx_state, nullptr, false, lx_stream);
   static_assert(PX_N == LX_NPHASE, "profile phases");
+  if (st.md != 2 && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 has no float32 instance");      // (fusedlx_model_supported keeps such a model away)
   lx_run<ShapeX>(m, a, st, "fused_lx", [&](const FusedLxArgs &A, int grid, int var) {
-    dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants>([&](auto nl, auto ar, auto v) {
-      if constexpr (v != VAR_PROF || nl == 3)         // profiled: 3 layers only
-        hipLaunchKernelGGL((k_fused_lx<nl, v == VAR_PROF, ar, v == VAR_VA>), dim3(grid), dim3(ShapeX::NW * 64), 0, a.stream, A);
-    }, A.NL, st.arith, var);
+    dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
+      if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)
+        hipLaunchKernelGGL((k_fused_lx<nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(ShapeX::NW * 64), 0, a.stream, A);
+    }, A.NL, st.arith, var, st.md);
   });
   return true;
 }

@@ -55,11 +55,16 @@ struct ShapeP {
   static constexpr int ENVA = D * U + 16;               // environment row of one centre: [lm][u] + pad.  ENVA = 16 (mod 64): the rows of the (<= 4) centres of a tile and the four lane groups (+ 4 g)
                                                         // start in 16 distinct 4-bank groups (round 6; with + 4 centre 1 / group 0 met centre 0 / group 1: 229.1 -> 227.7 ms on config 5)
   static constexpr int NP = CgX<2>::NP;
-  // scratch rows (per wave, 1 KiB each): d x0/dd 4 | w0 EWH | per layer: omega EWH, silu'(z1) 2, silu'(z2) 2, u 2, V_in D*HT
-  static constexpr int R_DX0 = 0, R_W0 = 4, LSZ = EWH + 6 + D * HT;
-  __host__ __device__ static constexpr int R_LAYER(int kk) { return 4 + EWH + kk * LSZ; }
-  __host__ __device__ static constexpr int R_TOTAL(int NL) { return 4 + EWH + NL * LSZ; }
-  static constexpr int O_OM = 0, O_Z1 = EWH, O_Z2 = EWH + 2, O_U = EWH + 4, O_VIN = EWH + 6;
+  // scratch rows (per wave, 1 KiB each): d x0/dd 4 | w0 EWH | per layer: omega EWH, hidden layers 1..MD 2 each (own tiles), u 2, V_in D*HT  (fused_lx_rows.h; MD = latent MLP depth)
+  using R = RowsP;
+  static_assert(R::EW == EWH && R::HR == HT && R::NV == D * HT, "row map of this shape");
+  static constexpr int R_DX0 = R::R_DX0, R_W0 = R::R_W0, O_OM = R::O_OM;
+  __host__ __device__ static constexpr int O_Z(int h) { return R::O_Z(h); }
+  __host__ __device__ static constexpr int O_U(int MD) { return R::O_U(MD); }
+  __host__ __device__ static constexpr int O_VIN(int MD) { return R::O_VIN(MD); }
+  __host__ __device__ static constexpr int LSZ(int MD) { return R::LSZ(MD); }
+  __host__ __device__ static constexpr int R_LAYER(int kk, int MD) { return R::R_LAYER(kk, MD); }
+  __host__ __device__ static constexpr int R_TOTAL(int NL, int MD) { return R::R_TOTAL(NL, MD); }
 };
 
 struct __attribute__((aligned(16))) LdsP {
@@ -207,11 +212,15 @@ enum { PP_GEOM = 0, PP_EMB, PP_ENV, PP_TP, PP_LAT, PP_MIX, PP_OUT, PP_BLAT, PP_B
 
 // ---------------------------------------------------------------------------- the kernel
 // VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
-template <int NLT, bool PROF, int AR, bool VA = false>
+// MD: hidden layers of the latent MLP (1..3; 1 and 3 on the f16x2 arithmetic only, as in k_fused and k_fused_lx).  Every hidden layer is split by output tile, so each
+// one beyond the first costs one more pair hand-over forward and one more backward; MD is a compile-time fact, so all eight waves still meet the same barriers.
+template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2>
 __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
   using S = ShapeP;
   constexpr int NTHREADS = 512, D = S::D, U = S::U, HT = S::HT, EWH = S::EWH, MAXA = S::MAXA, STG_LD = S::STG_LD, ENVA = S::ENVA, NP = S::NP, L = S::L;
   constexpr bool SAVEZ = AR == 3;          // f16x2: raw pre-activation rows of the last hidden layer instead of silu' rows, no u rows (see fused.hip)
+  static_assert(MD >= 1 && MD <= 3 && (MD == 2 || AR == 3), "latent MLP depth 1 / 3: f16x2 instances only");
+  static_assert(MD == 2 || !PROF, "profiled instances: depth 2");
   __shared__ LdsP lds;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
@@ -350,7 +359,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
 #pragma unroll
     for (int kk = 0; kk < NL; ++kk) {
       const bool last = (kk == NL - 1);
-      const int RL = S::R_LAYER(kk);
+      const int RL = S::R_LAYER(kk, MD);
       float *const envk = lds.env[kk];
       {
         f32x4 om[EWH];
@@ -421,30 +430,48 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
         for (int t = 0; t < 4; ++t) cat[t] = x[t];
         x_swap<2>(X, xb, sc, pr);
         cat[4] = sc[0]; cat[5] = sc[1]; cat[6] = pr[0]; cat[7] = pr[1];
-        lx_lin<AR, 8, 2, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z1, V16()});
-        x_swap<2>(X, xb, z, pr);
-        zin[0] = z[0]; zin[1] = z[1]; zin[2] = pr[0]; zin[3] = pr[1];
-        if constexpr (SAVEZ) lx_lin<AR, 4, 2, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z2, V16()});
-        else lx_lin<AR, 4, 2, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z2, V16()});
-        x_swap<2>(X, xb, z2, pr);
-        zin[0] = z2[0]; zin[1] = z2[1]; zin[2] = pr[0]; zin[3] = pr[1];
+        if constexpr (MD == 2) {
+          lx_lin<AR, 8, 2, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(1), V16()});
+          x_swap<2>(X, xb, z, pr);
+          zin[0] = z[0]; zin[1] = z[1]; zin[2] = pr[0]; zin[3] = pr[1];
+          if constexpr (SAVEZ) lx_lin<AR, 4, 2, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z(2), V16()});
+          else lx_lin<AR, 4, 2, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(2), V16()});
+          x_swap<2>(X, xb, z2, pr);
+          zin[0] = z2[0]; zin[1] = z2[1]; zin[2] = pr[0]; zin[3] = pr[1];
+        } else if constexpr (MD == 1) {
+          // the only hidden layer is the last one: raw z rows; one hand-over fewer
+          lx_lin<AR, 8, 2, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z(1), V16()});
+          x_swap<2>(X, xb, z, pr);
+          zin[0] = z[0]; zin[1] = z[1]; zin[2] = pr[0]; zin[3] = pr[1];
+        } else {
+          // hidden layers 1, 2: silu' rows; 3: raw z rows.  z / z2 ping-pong; one hand-over more
+          lx_lin<AR, 8, 2, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(1), V16()});
+          x_swap<2>(X, xb, z, pr);
+          zin[0] = z[0]; zin[1] = z[1]; zin[2] = pr[0]; zin[3] = pr[1];
+          lx_lin<AR, 4, 2, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(2), V16()});
+          x_swap<2>(X, xb, z2, pr);
+          zin[0] = z2[0]; zin[1] = z2[1]; zin[2] = pr[0]; zin[3] = pr[1];
+          lx_lin<AR, 4, 2, false>(WB, wp, zin, z, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z(3), V16()});
+          x_swap<2>(X, xb, z, pr);
+          zin[0] = z[0]; zin[1] = z[1]; zin[2] = pr[0]; zin[3] = pr[1];
+        }
         const float ra = lds.res[kk][0], rbf = lds.res[kk][1] * fc;
         f32x4 xo[2] = {x[0], x[1]};
         if constexpr (SAVEZ) lx_lin<AR, 4, 2, false>(WB, wp, zin, xn, V16(), ring, EpiResidualNS<2>{xo, ra, rbf});
-        else lx_lin<AR, 4, 2, false>(WB, wp, zin, xn, V16(), ring, EpiResidual<2>{{SB, RL + S::O_U, V16()}, xo, ra, rbf});
+        else lx_lin<AR, 4, 2, false>(WB, wp, zin, xn, V16(), ring, EpiResidual<2>{{SB, RL + S::O_U(MD), V16()}, xo, ra, rbf});
         x_swap<2>(X, xb, xn, pr);
         x[0] = xn[0]; x[1] = xn[1]; x[2] = pr[0]; x[3] = pr[1];
       }
       PHASEP(PP_LAT);
       // channel mixing, in place per (l, m) row -> V^{kk+1}, saved as the next layer's V_in rows
-      if (!last) mix_rows_p<0, true, AR>(V, WB, wp, ring, SB, S::R_LAYER(kk + 1) + S::O_VIN, sc, X, xb);
+      if (!last) mix_rows_p<0, true, AR>(V, WB, wp, ring, SB, S::R_LAYER(kk + 1, MD) + S::O_VIN(MD), sc, X, xb);
       PHASEP(PP_MIX);
     }
 
     // ---------------- read-out (both waves of a pair evaluate it) ----------------
     f32x4 upre[2], zt[2], w0pre[L * HT];
-    if constexpr (!SAVEZ) load_rows<2>(SB, S::R_LAYER(NL - 1) + S::O_U, upre, V16());
-    load_rows<2>(SB, S::R_LAYER(NL - 1) + S::O_Z2, zt, V16());
+    if constexpr (!SAVEZ) load_rows<2>(SB, S::R_LAYER(NL - 1, MD) + S::O_U(MD), upre, V16());
+    load_rows<2>(SB, S::R_LAYER(NL - 1, MD) + S::O_Z(MD), zt, V16());
     __builtin_amdgcn_sched_barrier(0);
     f32x4 zr[2];
     lx_lin<AR, 4, 2, false>(WB, wp, x, zr, V16(), ring, EpiNone{});
@@ -489,13 +516,13 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
 #pragma unroll
     for (int kk = NL - 1; kk >= 0; --kk) {
       const bool last = (kk == NL - 1);
-      const int RL = S::R_LAYER(kk);
+      const int RL = S::R_LAYER(kk, MD);
       f32x4 ds[HT];
       f32x4 P[4];            // partial latent gradient: dE/dx^{kk-1} = P(this wave) + P(partner)
       {
         f32x4 du[4], dh[2], din[4], pr[2];
-        f32x4 rows1[2];
-        load_rows<2>(SB, RL + S::O_Z1, rows1, V16());            // silu'(z1), own tiles: first used one linear from here
+        f32x4 rows1[2];          // silu' of the hidden layer below the last (MD >= 2), own tiles: first used one linear from here
+        if constexpr (MD >= 2) load_rows<2>(SB, RL + S::O_Z(MD - 1), rows1, V16());
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (SAVEZ) {
           // the u rows are not saved (fused.hip: SAVEZ): <u, g> over this wave's hidden tiles falls out of the epilogue of the first backward linear, fed with the unscaled gradient
@@ -518,11 +545,29 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
           pin(dfc_part);
           lx_lin<AR, 4, 2, false>(WB, wp, du, dh, V16(), ring, EpiMulRows<2>{zt});
         }
-        x_swap<2>(X, xb, dh, pr);
-        din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
-        lx_lin<AR, 4, 2, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<2>{rows1});
-        x_swap<2>(X, xb, dh, pr);
-        din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+        // down the hidden layers, each split by output tile: hand-over, g_{h-1} = (g_h W_h^T) * silu'(z_{h-1}) on the own tiles
+        if constexpr (MD == 2) {
+          x_swap<2>(X, xb, dh, pr);
+          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+          lx_lin<AR, 4, 2, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<2>{rows1});
+          x_swap<2>(X, xb, dh, pr);
+          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+        } else if constexpr (MD == 1) {
+          x_swap<2>(X, xb, dh, pr);
+          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+        } else {
+          f32x4 rows0[2];      // silu' of hidden layer 1, own tiles: requested one linear ahead
+          load_rows<2>(SB, RL + S::O_Z(1), rows0, V16());
+          __builtin_amdgcn_sched_barrier(0);
+          x_swap<2>(X, xb, dh, pr);
+          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+          lx_lin<AR, 4, 2, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<2>{rows1});
+          x_swap<2>(X, xb, dh, pr);
+          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+          lx_lin<AR, 4, 2, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<2>{rows0});
+          x_swap<2>(X, xb, dh, pr);
+          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+        }
         f32x4 dcat[4];       // own x tiles (2), own scalar tiles (2)
         lx_lin<AR, 4, 4, false>(WB, wp, din, dcat, V16(), ring, EpiNone{});
         P[0] += dcat[0]; P[1] += dcat[1];
@@ -546,7 +591,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
           const int t = i >> 1, h = i & 1;
           if (kk > 0) {
 #pragma unroll
-            for (int lm = 0; lm < D; ++lm) vnext[lm] = bload_half(SB, V16() + 8 * h, (RL + S::O_VIN + lm * HT + t) * ROW * 4);
+            for (int lm = 0; lm < D; ++lm) vnext[lm] = bload_half(SB, V16() + 8 * h, (RL + S::O_VIN(MD) + lm * HT + t) * ROW * 4);
           } else {
 #pragma unroll
             for (int l = 0; l <= L; ++l) vnext[l] = bload_half(SB, V16() + 8 * h, (S::R_W0 + l * HT + t) * ROW * 4);
@@ -642,8 +687,8 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
         }
         lx_prime<AR>(WB, wp, V16(), ring);
         if (kk > 0) {
-          if constexpr (!SAVEZ) load_rows<2>(SB, S::R_LAYER(kk - 1) + S::O_U, upre, V16());
-          load_rows<2>(SB, S::R_LAYER(kk - 1) + S::O_Z2, zt, V16());
+          if constexpr (!SAVEZ) load_rows<2>(SB, S::R_LAYER(kk - 1, MD) + S::O_U(MD), upre, V16());
+          load_rows<2>(SB, S::R_LAYER(kk - 1, MD) + S::O_Z(MD), zt, V16());
         } else load_rows<L * HT>(SB, S::R_W0 + HT, w0pre, V16());
         __builtin_amdgcn_sched_barrier(0);
         lx_lin<AR, EWH, 4, true>(WB, wp, dom, P, V16(), ring, EpiNone{});      // split by input tile: partial sums over the own channels
@@ -809,7 +854,7 @@ static std::vector<double> gather_tiles(const double *W, int ldw, const std::vec
 // k_fused_lx2's weight streams, one per wave half, in the order a tile consumes them (see k_fused_lx2)
 static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, Arith arith) {
   using S = ShapeP;
-  const int NL = h.num_layers, U = S::U, D = S::D, UT = S::UT;
+  const int NL = h.num_layers, MD = h.mlp_depth, U = S::U, D = S::D, UT = S::UT;      // latent MLP: lat.w0, hidden lat.w1 .. lat.w{MD-1}, output linear lat.w{MD}
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
   for (int hf = 0; hf < 2; ++hf) {
@@ -841,8 +886,7 @@ static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h,
       const std::string lk = "l" + std::to_string(k + 1);
       put(T_(lk + ".env"), U * 3, xo, lu);
       put(T_(lk + ".lat.w0"), 64, cat_rows, ownt);
-      put(T_(lk + ".lat.w1"), 64, xo, ownt);
-      put(T_(lk + ".lat.w2"), 64, xo, ownt);
+      for (int hl = 1; hl <= MD; ++hl) put(T_(lk + ".lat.w" + std::to_string(hl)), 64, xo, ownt);      // every 64 -> 64 linear: inputs own tiles first, own output tiles
       if (k < NL - 1) {
         const double *mx = T_(lk + ".mix");            // [L+1][U][U]; block l serves its 2l+1 components
         for (int lm = 0; lm < D; ++lm) put(mx + (size_t)l_of_lm(lm) * U * U, U, xo, ownt);
@@ -852,8 +896,7 @@ static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h,
     putT(T_("out.w0"), 64, 32, {0, 1}, xo);
     for (int k = NL - 1; k >= 0; --k) {
       const std::string lk = "l" + std::to_string(k + 1);
-      putT(T_(lk + ".lat.w2"), 64, 64, xo, ownt);
-      putT(T_(lk + ".lat.w1"), 64, 64, xo, ownt);
+      for (int hl = MD; hl >= 1; --hl) putT(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64, xo, ownt);
       putT(T_(lk + ".lat.w0"), 64 + U, 64, xo, cat_cols);
       if (k < NL - 1) {
         const double *mx = T_(lk + ".mix");
@@ -871,11 +914,12 @@ bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
   if (!lx_list_fits(m, why)) return false;
   FusedLxState &st = lx_prepare<ShapeP>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream);     // path weights x the path's base |c| (tp_g)
   static_assert(PP_N == LX_NPHASE, "profile phases");
+  if (st.md != 2 && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 has no float32 instance");      // (fusedlx_model_supported keeps such a model away)
   lx_run<ShapeP>(m, a, st, "fused_lx2", [&](const FusedLxArgs &A, int grid, int var) {
-    dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants>([&](auto nl, auto ar, auto v) {
-      if constexpr (v != VAR_PROF || nl == 3)         // profiled: 3 layers only
-        hipLaunchKernelGGL((k_fused_lx2<nl, v == VAR_PROF, ar, v == VAR_VA>), dim3(grid), dim3(ShapeP::NW * 64), 0, a.stream, A);
-    }, A.NL, st.arith, var);
+    dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
+      if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)
+        hipLaunchKernelGGL((k_fused_lx2<nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(ShapeP::NW * 64), 0, a.stream, A);
+    }, A.NL, st.arith, var, st.md);
   });
   return true;
 }
