@@ -235,6 +235,23 @@ int ahip_last_heavy_centres(ahip_model *m, int *ncentres, long long *nedges);
  * out[32][N] = in[32][K] @ W[K][N] (W row-major f64, in/out f32 host buffers). */
 int ahip_debug_fused_linear(int K, int N, const double *W, const float *in, float *out);
 
+/* Diagnostics of the device-wide primitives (csrc/prims.hip) and of the layer-at-a-time path's float32 GEMM (csrc/gemm.hip): host buffers in, host
+ * buffers out, no model.  Each call owns its scratch and synchronises the device.
+ *   ahip_debug_scan_i32        : out[0..n] = exclusive prefix sum of in[0..n), out[n] = total.  warm_n > 0: in[0..warm_n) is scanned first on the same
+ *                                scratch and the result discarded, so that the scan of n re-grows the scratch.
+ *   ahip_debug_sum_columns_f64 : out[c] = sum_r in[r * ncol + c]; 1 <= ncol <= 8, anything else is an error before any launch.
+ *   ahip_debug_max_i32         : out[0] = max(0, max(in[0..n))).
+ *   ahip_debug_gemm_f32        : C[e][n] (+)= sum_k A'[e][k] * (transB ? W[n][k] : W[k][n]),  A' = A + a_off with row stride lda (A is uploaded whole,
+ *                                [a_off + (E - 1) lda + K] floats, so a_off makes views that are not 16-byte aligned); C [E][ldc] is uploaded first
+ *                                (accumulate, and the columns beyond N stay as they were).  silu_out / dsilu_z (either may be NULL) are the fused epilogues
+ *                                of the model's dense layers, [E][ldc] like C: C *= silu'(dsilu_z), then silu_out = silu(C); silu_out is uploaded first, too.
+ *                                AHIP_ERR_UNSUPPORTED in a build without the MFMA kernel. */
+int ahip_debug_scan_i32(const int *in, int n, int warm_n, int *out);
+int ahip_debug_sum_columns_f64(const double *in, long long nrow, int ncol, double *out);
+int ahip_debug_max_i32(const int *in, int n, int *out);
+int ahip_debug_gemm_f32(long long E, int K, int N, const float *A, int lda, int a_off, const float *W, int ldw, int transB, float *C, int ldc,
+                        int accumulate, float *silu_out, const float *dsilu_z);
+
 /* Diagnostic (environment AHIP_FUSED_DBG=1): per-edge {g[3], dE/dd, dE/dfc, dE/dY1..3} of the last fused
  * compute, [nedges][8] floats, edge order = ahip_get_edges. */
 int ahip_debug_fused_edges(ahip_model *m, float *out, long long nedges);

@@ -36,6 +36,7 @@ SYMBOLS = [
     "ahip_last_path", "ahip_last_max_degree", "ahip_last_heavy_centres", "ahip_debug_fused_linear", "ahip_debug_fused_edges", "ahip_build_neighbors_dev", "ahip_nve_dev", "ahip_nve_first_dev",
     "ahip_model_allow_tf32", "ahip_comm_unique_id", "ahip_comm_create_rccl", "ahip_comm_create_hosted", "ahip_comm_rccl_version", "ahip_comm_free", "ahip_comm_set_plan", "ahip_comm_set_plan_local",
     "ahip_comm_forward", "ahip_comm_reverse", "ahip_comm_allreduce", "ahip_comm_selftest", "ahip_fill_zero_dev", "ahip_borders_local_dev", "ahip_arith_note", "ahip_comm_borders", "ahip_comm_migrate",
+    "ahip_debug_scan_i32", "ahip_debug_sum_columns_f64", "ahip_debug_max_i32", "ahip_debug_gemm_f32",
 ]
 
 
@@ -113,6 +114,11 @@ class Library:
                                    C.POINTER(C.c_double), C.c_double, C.c_double, C.c_void_p]
 
         L.ahip_debug_fused_linear.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.ahip_debug_scan_i32.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int)]
+        L.ahip_debug_sum_columns_f64.argtypes = [C.POINTER(C.c_double), C.c_longlong, C.c_int, C.POINTER(C.c_double)]
+        L.ahip_debug_max_i32.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+        L.ahip_debug_gemm_f32.argtypes = [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int,
+                                          C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.ahip_comm_unique_id.argtypes = [C.c_char_p]
         L.ahip_comm_create_rccl.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         L.ahip_comm_create_hosted.argtypes = [C.c_int, C.c_int, XFER_FN, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -139,6 +145,36 @@ class Library:
         out = np.zeros((32, N), dtype=np.float32)
         self.check(self.lib.ahip_debug_fused_linear(K, N, _p(W, C.c_double), _p(x, C.c_float), _p(out, C.c_float)))
         return out
+
+    def debug_scan_i32(self, v: np.ndarray, warm_n: int = 0) -> np.ndarray:
+        """exclusive prefix sum of v through prim_exclusive_scan_i32, [n + 1] (the last entry is the total); warm_n: a small scan first (scratch re-grow)"""
+        v = np.ascontiguousarray(v, dtype=np.int32)
+        out = np.full(len(v) + 1, -1, dtype=np.int32)
+        self.check(self.lib.ahip_debug_scan_i32(_p(v, C.c_int), len(v), warm_n, _p(out, C.c_int)))
+        return out
+
+    def debug_sum_columns_f64(self, a: np.ndarray, ncol: Optional[int] = None) -> np.ndarray:
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        nrow, ncol = (a.shape[0], a.shape[1]) if ncol is None else (a.size // ncol, ncol)
+        out = np.full(ncol, np.nan)
+        self.check(self.lib.ahip_debug_sum_columns_f64(_p(a, C.c_double), nrow, ncol, _p(out, C.c_double)))
+        return out
+
+    def debug_max_i32(self, v: np.ndarray) -> int:
+        v = np.ascontiguousarray(v, dtype=np.int32)
+        out = np.full(1, -1, dtype=np.int32)
+        self.check(self.lib.ahip_debug_max_i32(_p(v, C.c_int), len(v), _p(out, C.c_int)))
+        return int(out[0])
+
+    def debug_gemm_f32(self, E: int, K: int, N: int, A: np.ndarray, lda: int, a_off: int, W: np.ndarray, ldw: int, transB: bool, Cbuf: np.ndarray, ldc: int,
+                       accumulate: bool, silu_out: Optional[np.ndarray] = None, dsilu_z: Optional[np.ndarray] = None) -> None:
+        """gemm_f32 of the layer-at-a-time path on flat float32 buffers; Cbuf [E * ldc] and silu_out are updated in place"""
+        for a in (A, W, Cbuf, silu_out, dsilu_z):
+            assert a is None or (a.dtype == np.float32 and a.flags.c_contiguous)
+        assert A.size >= a_off + (E - 1) * lda + K and W.size >= ((N if transB else K) - 1) * ldw + (K if transB else N)
+        assert Cbuf.size == E * ldc and (silu_out is None or silu_out.size == E * ldc) and (dsilu_z is None or dsilu_z.size == E * ldc)
+        self.check(self.lib.ahip_debug_gemm_f32(E, K, N, _p(A, C.c_float), lda, a_off, _p(W, C.c_float), ldw, int(transB), _p(Cbuf, C.c_float), ldc,
+                                                int(accumulate), _p(silu_out, C.c_float), _p(dsilu_z, C.c_float)))
 
     def check(self, rc: int) -> None:
         if rc != 0:

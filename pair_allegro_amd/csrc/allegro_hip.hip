@@ -1285,3 +1285,86 @@ int ahip_nve_dev(ahip_model *m, int mode, int n, double *x_dev, double *v_dev, c
     nve_step(mode, n, x_dev, v_dev, f_dev, mtype_dev, mass_by_mtype, m->hm.num_types, dt, ftm2v, (hipStream_t)stream);
   });
 }
+
+// ---- diagnostics of the device-wide primitives and the generic path's GEMM: host buffers in, host buffers out, no model ----
+namespace {
+struct DebugBufs {                    // device buffers of one diagnostic call
+  std::vector<void *> p;
+  void *get(size_t bytes) {
+    void *q = nullptr;
+    AHIP_CHECK(hipMalloc(&q, bytes ? bytes : 1));
+    p.push_back(q);
+    return q;
+  }
+  void *upload(const void *host, size_t bytes) {
+    void *q = get(bytes);
+    if (bytes) copy_h2d(q, host, bytes);
+    return q;
+  }
+  ~DebugBufs() { for (void *q : p) (void)hipFree(q); }
+};
+struct DebugScratch {
+  PrimScratch ps;
+  ~DebugScratch() { ps.release(); }
+};
+}  // namespace
+
+int ahip_debug_scan_i32(const int *in, int n, int warm_n, int *out) {
+  return guarded([&] {
+    if (n < 0 || warm_n < 0 || warm_n > n || !out || (n > 0 && !in)) throw ArgError("ahip_debug_scan_i32: bad argument");
+    DebugBufs b;
+    DebugScratch sc;
+    int *din = (int *)b.upload(in, (size_t)n * sizeof(int));
+    int *dout = (int *)b.get(((size_t)n + 1) * sizeof(int));
+    if (warm_n > 0) AHIP_CHECK(prim_exclusive_scan_i32(sc.ps, din, dout, warm_n, nullptr));      // a small scan first: the next one re-grows the scratch
+    AHIP_CHECK(prim_exclusive_scan_i32(sc.ps, din, dout, n, nullptr));
+    AHIP_CHECK(hipStreamSynchronize(nullptr));
+    copy_d2h(out, dout, ((size_t)n + 1) * sizeof(int));
+  });
+}
+
+int ahip_debug_sum_columns_f64(const double *in, long long nrow, int ncol, double *out) {
+  return guarded([&] {
+    if (nrow < 0 || ncol < 1 || !out || (nrow > 0 && !in)) throw ArgError("ahip_debug_sum_columns_f64: bad argument");
+    DebugBufs b;
+    DebugScratch sc;
+    double *din = (double *)b.upload(in, (size_t)nrow * ncol * sizeof(double));
+    double *dout = (double *)b.get((size_t)ncol * sizeof(double));
+    AHIP_CHECK(prim_sum_columns_f64(sc.ps, din, nrow, ncol, dout, nullptr));
+    AHIP_CHECK(hipStreamSynchronize(nullptr));
+    copy_d2h(out, dout, (size_t)ncol * sizeof(double));
+  });
+}
+
+int ahip_debug_max_i32(const int *in, int n, int *out) {
+  return guarded([&] {
+    if (n < 0 || !out || (n > 0 && !in)) throw ArgError("ahip_debug_max_i32: bad argument");
+    DebugBufs b;
+    int *din = (int *)b.upload(in, (size_t)n * sizeof(int));
+    int *dout = (int *)b.get(sizeof(int));
+    AHIP_CHECK(prim_max_i32(din, n, dout, nullptr));
+    AHIP_CHECK(hipStreamSynchronize(nullptr));
+    copy_d2h(out, dout, sizeof(int));
+  });
+}
+
+int ahip_debug_gemm_f32(long long E, int K, int N, const float *A, int lda, int a_off, const float *W, int ldw, int transB, float *C, int ldc,
+                        int accumulate, float *silu_out, const float *dsilu_z) {
+  return guarded([&] {
+    if (E < 1 || K < 1 || N < 1 || !A || !W || !C || a_off < 0 || lda < K || ldw < (transB ? K : N) || ldc < N)
+      throw ArgError("ahip_debug_gemm_f32: bad argument");
+    DebugBufs b;
+    const size_t nC = (size_t)E * ldc * sizeof(float);
+    const float *dA = (const float *)b.upload(A, ((size_t)a_off + (size_t)(E - 1) * lda + K) * sizeof(float));
+    const float *dW = (const float *)b.upload(W, ((size_t)((transB ? N : K) - 1) * ldw + (transB ? K : N)) * sizeof(float));
+    float *dC = (float *)b.upload(C, nC);
+    float *dS = silu_out ? (float *)b.upload(silu_out, nC) : nullptr;
+    const float *dZ = dsilu_z ? (const float *)b.upload(dsilu_z, nC) : nullptr;
+    if (!gemm_f32(nullptr, E, K, N, dA + a_off, lda, dW, ldw, transB != 0, dC, ldc, accumulate != 0, dS, dZ))
+      throw UnsupportedError("ahip_debug_gemm_f32: this build has no MFMA GEMM");
+    AHIP_CHECK(hipGetLastError());
+    AHIP_CHECK(hipStreamSynchronize(nullptr));
+    copy_d2h(C, dC, nC);
+    if (silu_out) copy_d2h(silu_out, dS, nC);
+  });
+}

@@ -138,6 +138,7 @@ __global__ void __launch_bounds__(64) k_colsum_stage2(const double *part, int nb
 }
 
 hipError_t prim_sum_columns_f64(PrimScratch &ps, const double *in, long long nrow, int ncol, double *out, hipStream_t s) {
+  if (ncol < 1 || ncol > 8) return hipErrorInvalidValue;      // the kernels keep 8 columns in registers and LDS
   if (!ps.part) {
     hipError_t e = hipMalloc((void **)&ps.part, RED_BLOCKS * 8 * sizeof(double));
     if (e != hipSuccess) { ps.part = nullptr; return e; }

@@ -18,6 +18,7 @@ hipError_t prim_exclusive_scan_i32(PrimScratch &, const int *in, int *out, int n
   return hipSuccess;
 }
 hipError_t prim_sum_columns_f64(PrimScratch &, const double *in, long long nrow, int ncol, double *out, hipStream_t) {
+  if (ncol < 1 || ncol > 8) return hipErrorInvalidValue;
   for (int c = 0; c < ncol; ++c) {
     double s = 0;
     for (long long r = 0; r < nrow; ++r) s += in[r * ncol + c];

@@ -28,7 +28,7 @@ struct dim3 {
 extern dim3 threadIdx, blockIdx, blockDim, gridDim;
 
 typedef int hipError_t;
-enum { hipSuccess = 0, hipErrorUnknown = 999 };
+enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorUnknown = 999 };
 typedef struct ihipStream_t *hipStream_t;
 struct EmuEvent { std::chrono::steady_clock::time_point t; };
 typedef EmuEvent *hipEvent_t;

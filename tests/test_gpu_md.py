@@ -39,6 +39,18 @@ def test_device_neighbor_list_equals_host_list(hip_lib, model_dir):
     # edge multiset of the device-built list == brute force at r_max
     ei, rij = model.get_edges()
     assert ei.shape[1] == 28 * len(pos)
+    x = sim.x.cpu().numpy()
+    nall = len(x)
+    want = []
+    for i0 in range(0, sim.nlocal, 256):                           # all (i local, j != i) with dx^2 + dy^2 + dz^2 <= r_max^2 over the materialised rows, float64
+        d = x[None, :, :] - x[i0: i0 + 256, None, :]
+        i, j = np.nonzero(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2] <= cfg["r_max"] ** 2)
+        keep = i + i0 != j
+        want.append((i[keep] + i0) * nall + j[keep])
+    want = np.concatenate(want)
+    got = ei[0] * nall + ei[1]
+    assert len(np.unique(got)) == len(got), "an edge appears twice"
+    assert np.array_equal(np.sort(got), np.sort(want))
     model.close()
 
 

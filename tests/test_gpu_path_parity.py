@@ -94,6 +94,21 @@ def test_every_path_on_the_layer_kernels_l_max_3(hip_lib, model_dir, dtype):
     print(f"\nlayer kernels l_max 3 {dtype}: worst error / bar {worst:.3f}")
 
 
+def test_every_path_on_the_layer_kernels_odd_widths_l_max_2(hip_lib, model_dir):
+    """l_max = 2, 2 layers, S 30 / U 6 / MLP 37 / read-out 10: no width is a multiple of 4, so the GEMM takes its scalar-load instances and the sub-block views
+    V + lm U are not 16-byte aligned; the unrolled tensor product and the row reductions run with an odd U.  Per path, not only in the sum."""
+    if "odd_l2" not in _cases:
+        g = util.load_golden("Cu2AgO4_r5")
+        cfg = dict(model_file.DEFAULT_CFG, type_names=["Ag", "Cu", "O"], l_max=2, num_layers=2, num_scalar_features=30, num_tensor_features=6,
+                   mlp_width=37, readout_width=10, avg_num_neighbors=float(g["nedges"]) / len(g["pos"]))
+        _cases["odd_l2"] = pp.PathCase(model_dir, "paths_odd_l2", cfg, g["cell"], g["pos"], g["symbols"])
+    case = _cases["odd_l2"]
+    worst = 0.0
+    for k, p, lll in pp.paths(case.cfg):
+        worst = max(worst, case.check(hip_lib, k, p, "float32", "generic_f32", options={"path": "generic"}))
+    print(f"\nlayer kernels l_max 2 odd widths: worst error / bar {worst:.3f} ({len(pp.paths(case.cfg))} paths)")
+
+
 # ---- per-edge gradients of k_fused (AHIP_FUSED_DBG=1: the kernel dumps {g[3], dd, dfc, dY[3]} per edge) --------------------------------
 @pytest.mark.parametrize("arith", ["f32", "f16x2"])
 @pytest.mark.parametrize("tag", ["Si64_r5", "Cu2AgO4_r5"])
