@@ -71,8 +71,8 @@ int ahip_model_meta(const ahip_model *m, double *r_max, int *num_types, const ch
  *   "fused_arith" = "auto" | "f32" | "f16x2" | "bf16x3" | "tf32eq"   arithmetic of the dense contractions of the fused kernels: f32-input MFMA (exact float32
  *                                                 fmaf chains); two float16 terms per operand, three f16-MFMA products (float32-equivalent inside float16's exponent
  *                                                 range; an evaluation that leaves it returns AHIP_ERR_STATE: host-pointer calls at once, _dev calls at the next
- *                                                 evaluation); three-term bf16 split (float32-equivalent; l_max = 1 kernel); two-term bf16 split (TF32-class; l_max = 1
- *                                                 kernel).  auto = f16x2 unless the model file says allow_tf32 = 1 (pair_nequip_allegro.cpp:267-270), then tf32eq.
+ *                                                 evaluation); three-term bf16 split (float32-equivalent; k_fused, i.e. l_max = 1 with up to 32 tensor features);
+ *                                                 two-term bf16 split (TF32-class; k_fused).  auto = f16x2 unless the model file says allow_tf32 = 1 (pair_nequip_allegro.cpp:267-270), then tf32eq.
  *                                                 auto is never less robust than the reference's float32 (which only ever RELAXES precision, :267-270): a model the split
  *                                                 cannot carry (a weight beyond float16's range, a linear inside its subnormals), a first evaluation that disagrees with
  *                                                 the float32 instance by more than 1e-5 max|F|, or a float16-range alarm switch the model to the f32 instance for the
@@ -82,8 +82,8 @@ int ahip_model_meta(const ahip_model *m, double *r_max, int *num_types, const ch
  *   "fused_tb"  = "table" | "mlp"                two-body embedding of the fused kernels: tabulated cubic splines (default) or the MLP itself
  *   "edge_schedule" = "auto" | "static" | "dynamic"   unit schedule of the single-pass edge build (dynamic: safe beside other resident kernels)
  *   "tile_pack" = "auto" | "separate" | "fused"  tile packing of the fused kernels inside the edge build or as its own kernels
- *   "dense_centres" = "whole" | "split"          a list in which a few centres have more edges than a tile of the fused kernel holds (128 for l_max = 1, 64 for
- *                                                 l_max = 2) while a list row is longer than 128 entries: "whole" (default) evaluates the whole list on the
+ *   "dense_centres" = "whole" | "split"          a list in which a few centres have more edges than a tile of the fused kernel holds (128 for l_max = 1 with up to 32
+ *                                                 tensor features, 64 for every other fused shape) while a list row is longer than 128 entries: "whole" (default) evaluates the whole list on the
  *                                                 layer-at-a-time kernels; "split" keeps the fused kernel for the other centres and evaluates only those few
  *                                                 (at most one centre in eight, else as "whole") on the layer-at-a-time kernels.  ahip_last_heavy_centres
  *                                                 reports them.  The cost of the split route has not been measured.

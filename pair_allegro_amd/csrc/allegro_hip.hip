@@ -588,14 +588,13 @@ static void heavy_generic(ahip_model *m, const ComputeArgs &a) {
   hipLaunchKernelGGL(k_add7, dim3(1), dim3(64), 0, a.stream, a.engvir, a2.engvir);
 }
 
-// The fused kernel family that serves the model: k_fused (l_max = 1), k_fused_lx (l_max = 2, 32 tensor features), k_fused_lx2 (64), or none (why: the
-// reasons of both).  Not cached: it depends on arith.force_f32 / arith.degraded (fused_model_supported: MLP depth 1 / 3 need f16x2), which the
-// self-check and an ArithDegraded fallback change.
-enum class FusedFamily { none, k_fused, lx32, lx64 };
+// The fused kernel family that serves the model (fused_shapes.h): k_fused (l_max = 1, up to 32 tensor features), k_fused_lx (l_max = 2, up to 32), k_fused_lx2
+// (up to 64, l_max = 2 or an l_max = 1 model lifted), or none (why: the reasons of both gates).  Not cached: it depends on arith.force_f32 / arith.degraded
+// (MLP depth 1 / 3 and read-out depth 2 need f16x2), which the self-check and an ArithDegraded fallback change.
 static FusedFamily fused_family(const Model &m, std::string *why) {
   std::string why1, why2;
   if (fused_model_supported(m, &why1)) return FusedFamily::k_fused;
-  if (fusedlx_model_supported(m, &why2)) return fused_UF(m.hm) == 64 ? FusedFamily::lx64 : FusedFamily::lx32;
+  if (fusedlx_model_supported(m, &why2)) return fused_shape_class(m.hm);
   if (why) *why = why1 + "; " + why2;
   return FusedFamily::none;
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "arith_policy.h"
+#include "fused_shapes.h"
 #include "model_io.h"
 #include "prims.h"
 
@@ -120,7 +121,8 @@ struct Model {
   ArithState arith;                         // option fused_arith (auto | f32 | f16x2 | bf16x3 | tf32eq) and what auto has decided so far: arith_policy.h
   DevBuf b_chk;                             // self-check: two force arrays + the 2-word reduction
   // A model narrower than a fused kernel's fixed widths runs on it zero-padded (round 6; model_io.h: pad_host_model): S <= 64 scalars, MLP width <= 64, read-out
-  // width <= 32, U <= 32 tensor features for l_max = 1, U <= 32 / <= 64 for l_max = 2.  hm stays the model as loaded (layer-at-a-time kernels, metadata).
+  // width <= 32, U <= 32 tensor features on k_fused / k_fused_lx, <= 64 on k_fused_lx2 (an l_max = 1 model with 33..64 features lifted to l_max = 2 as well:
+  // fused_shapes.h).  hm stays the model as loaded (layer-at-a-time kernels, metadata).
   HostModel hm_fused;
   bool hm_fused_ready = false;
   long long chunk_edges = 2000000;
@@ -269,13 +271,13 @@ inline constexpr int LX_TILE_SLOTS = 64, LX_TILE_MAXA = 4;           // k_fused_
 int *alarm_word(Model &m);
 bool alarm_take(Model &m);                  // true (and cleared) when a kernel has raised the word since the last call
 void fused_poll_alarm(Model &m);            // alarm_take + the policy: auto -> degrade to f32 and report once; explicit f16x2 -> StateError
-// the fused kernels' fixed widths and whether a model fits them (exactly, or narrower: then padded)
-inline int fused_UF(const HostModel &h) { return h.l_max == 1 ? 32 : (h.U <= 32 ? 32 : 64); }
-inline bool fused_widths_fit(const HostModel &h) { return h.S >= 1 && h.S <= 64 && h.mlp_width >= 1 && h.mlp_width <= 64 && h.readout_width >= 1 && h.readout_width <= 32 && h.U >= 1 && h.U <= (h.l_max == 1 ? 32 : 64); }
+// the model at the fixed shape of the fused kernel family its l_max and tensor features belong to (fused_shapes.h: the model itself when it is exactly that shape,
+// else zero-padded, and an l_max = 1 model with more than 32 tensor features lifted to l_max = 2)
 inline const HostModel &fused_host_model(Model &m) {
   const HostModel &h = m.hm;
-  if (h.S == 64 && h.mlp_width == 64 && h.readout_width == 32 && h.U == fused_UF(h)) return h;
-  if (!m.hm_fused_ready) { m.hm_fused = pad_host_model(h, 64, fused_UF(h), 64, 32); m.hm_fused_ready = true; }
+  const FusedFamily cls = fused_shape_class(h);
+  if (fused_shape_exact(h, cls)) return h;
+  if (!m.hm_fused_ready) { m.hm_fused = fused_shaped_model(h, cls); m.hm_fused_ready = true; }
   return m.hm_fused;
 }
 // the arithmetic policy (arith_policy.h) applied to a model: k_fused (wide = false) or the wide kernels
@@ -299,7 +301,7 @@ inline int model_tiny_linear(const HostModel &h) {
     const HostTensor &t = kv.second;
     const std::string &n = kv.first;
     const bool dense = n.find(".lat.w") != std::string::npos || n.find(".env") != std::string::npos || n.find(".mix") != std::string::npos || n == "emb.w" || n == "out.w0" ||
-                       (n.rfind("tb.w", 0) == 0);
+                       (n == "out.w1" && h.readout_depth == 2) || (n.rfind("tb.w", 0) == 0);      // (out.w1 of a depth-1 read-out is the final 32 -> 1 vector, read in float32)
     if (!dense || t.shape.size() < 2) continue;
     const long long blk = (long long)t.shape[t.shape.size() - 2] * t.shape[t.shape.size() - 1], nb = blk > 0 ? t.numel() / blk : 0;
     for (long long b = 0; b < nb; ++b) {

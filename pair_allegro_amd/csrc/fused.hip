@@ -24,10 +24,10 @@
 //            products, f32 accumulate: fused_h.h); bf16x3 (exact 3-way bf16 split, six bf16-MFMA terms); tf32eq (two bf16 terms,
 //            only for model files that set allow_tf32).
 //
-// Supported model shape (others run the generic path): l_max = 1, up to 32 tensor features, up to 64 scalars, MLP width up to 64, read-out width up to 32 (narrower than
-// the kernel's fixed 32 / 64 / 64 / 32: zero-padded by the host, model_io.cpp: pad_host_model),
+// Supported model shape (fused_shapes.h decides; others run the wide kernels or the generic path): l_max = 1, up to 32 tensor features (33..64: k_fused_lx2 on the lifted
+// model), up to 64 scalars, MLP width up to 64, read-out width up to 32 (narrower than the kernel's fixed 32 / 64 / 64 / 32: zero-padded by the host, model_io.cpp: pad_host_model),
 // MLPs of 2 hidden layers x 64 (1 or 3 hidden layers on the f16x2 instances with the tabulated two-body embedding: template parameter MD, round 5),
-// read-out 1 x 32, <= 3 layers, <= 16 types; any number of Bessel functions and any cutoff-polynomial order (the radial basis only
+// read-out 1 x 32 (2 x 32 on the same f16x2 instances: template parameter RD), <= 3 layers, <= 16 types; any number of Bessel functions and any cutoff-polynomial order (the radial basis only
 // enters through the tabulated two-body embedding; fused_tb=mlp needs 8).  Reference graph:
 // the TorchScript model executed at /root/reference/pair_nequip_allegro.cpp:409-430.
 #include <hip/hip_runtime.h>
@@ -48,8 +48,8 @@
 #include "fused_h.h"
 #include "prims.h"
 
-// This file is compiled in two parts (Makefile; same options, halves the build time): AHIP_FUSED_PART 0 = the host side + the f32-input MFMA
-// instances of k_fused, AHIP_FUSED_PART 1 = the bf16-split instances.  (Rounds 2-3 gave part 1 other compiler options because it computed wrong
+// This file is compiled in four parts (Makefile; same options, divides the build time): AHIP_FUSED_PART 0 = the host side + the f32-input MFMA
+// instances of k_fused, AHIP_FUSED_PART 1 = the bf16-split instances, 2 = the f16x2 instances, 3 = their read-out-depth-2 twins.  (Rounds 2-3 gave part 1 other compiler options because it computed wrong
 // forces with part 0's: that was the store-data hazard described at fused_common.h: bstore, not the options.)
 #ifndef AHIP_FUSED_PART
 #define AHIP_FUSED_PART 0
@@ -361,8 +361,8 @@ __device__ __forceinline__ void tile_fetch(const FusedArgs &A, int tile, int nti
   if (tid <= na) n.eoff = A.eoff[n.a0 + tid];
 }
 
-// VA: also the per-atom virial (output "atomic_virial"); instances launched only while that output is registered, so the default ones keep their code
-template <int NW, bool PROF, int AR, bool TBT, int NLT, int MD = 2, bool VA = false>
+// VA: also the per-atom virial (output "atomic_virial"); instances launched only while that output is registered, so the default ones keep their code.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 + table only, built in fused_hr.o)
+template <int NW, bool PROF, int AR, bool TBT, int NLT, int MD = 2, bool VA = false, int RD = 1>
 __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   constexpr int NTHREADS = NW * 64, MAXA = Lds<NW>::MAXA;
   // f16x2 instances (round 5): the last hidden layer of the latent MLP saves its RAW pre-activation rows and the layer's output rows u are not saved at all: the backward
@@ -375,6 +375,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   constexpr bool STGROWS = true;           // (36.0 -> 34.3 ms)
   constexpr int OZL = 4 + 4 * (MD - 1), OU = 4 + 4 * MD, OVIN = 8 + 4 * MD;      // row offsets inside a layer: silu' of the LAST hidden layer, u, V_in (MD = 2: 8, 12, 16)
   static_assert(MD >= 1 && MD <= 3 && (MD == 2 || (AR == 3 && TBT)), "latent MLP depth 1 / 3: f16x2 instances with the two-body table only");
+  static_assert(RD == 1 || (RD == 2 && AR == 3 && TBT && !PROF), "read-out depth 2: f16x2 instances with the two-body table only, not profiled");
   __shared__ Lds<NW, NLT> lds;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
   const int v16 = lane * 16;
@@ -674,14 +675,24 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     for (int t = 0; t < 2; ++t) if (!SAVEZ) upre[t] = bload(SB, v16t, (R_LAYER(NL - 1, MD) + OU + t) * ROW * 4);       // the last layer saved two rows: z2 (W3 Wr)
     if (!STGROWS) load_rows<4>(SB, R_LAYER(NL - 1, MD) + OZL, zt, v16t);
     __builtin_amdgcn_sched_barrier(0);
-    f32x4 wo1[2];
+    f32x4 zr2[2];              // RD = 2: pre-activations of the read-out's second hidden layer
+    if constexpr (RD == 2) {
+      f32x4 hr[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) hr[t][r] = silu1(zr[t][r]);
+      lin<AR, 2, 2, false, 0>(WB, wp, hr, zr2, v16t, ring, EpiNone{});
+    }
+    f32x4 (&zo)[2] = RD == 2 ? zr2 : zr;        // pre-activations of the last hidden layer
+    f32x4 wo1[2];              // the read-out's final 32 -> 1 vector (out.w1, or out.w2 of a depth-2 read-out)
 #pragma unroll
     for (int t = 0; t < 2; ++t) wo1[t] = *(const f32x4 *)(Wb + A.o_out1 + 16 * t + 4 * g);
     float eps = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) eps += silu1(zr[t][r]) * wo1[t][r];
+      for (int r = 0; r < 4; ++r) eps += silu1(zo[t][r]) * wo1[t][r];
     eps = gsum(eps);
     asm volatile("" : "+v"(eps));            // computed here, not sunk to its use at the end of the tile (keeps the read-out rows alive until then)
 
@@ -704,7 +715,16 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) dzr[t][r] = deps * wo1[t][r] * dsilu1(zr[t][r]);
+      for (int r = 0; r < 4; ++r) dzr[t][r] = deps * wo1[t][r] * dsilu1(zo[t][r]);
+    if constexpr (RD == 2) {
+      // dzr holds the gradient of zr2: back through out.w1^T (the second half-ring block) and the first hidden layer's SiLU; linear in deps, so the f16x2 scale passes through
+      f32x4 dhr[2];
+      lin<AR, 2, 2, false, 1>(WB, wp, dzr, dhr, v16t, ring, EpiNone{});
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dzr[t][r] = dhr[t][r] * dsilu1(zr[t][r]);
+    }
     lin<AR, 2, 4, false, 0>(WB, wp, dzr, dx, v16t, ring, EpiNone{});               // dzr Wr^T = the gradient w.r.t. x' of the last layer
     if (STGROWS) {                                                                 // the last layer's rows of its last hidden layer, from the staging tile
 #pragma unroll
@@ -1074,6 +1094,15 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
 // ---------------------------------------------------------------------------- the bf16-split instances (fused_bf.o)
 void fused_launch_bf16(int nw, bool prof, int arith, bool tbt, int grid, hipStream_t s, const FusedArgs &A);
 void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const FusedArgs &A);
+void fused_launch_f16_rd2(int nw, int md, int grid, hipStream_t s, const FusedArgs &A);
+#if AHIP_FUSED_PART == 3
+// the read-out-depth-2 f16x2 instances (fused_hr.o): two-body table only, latent MLP depth 1..3, plain and per-atom virial, not profiled
+void fused_launch_f16_rd2(int nw, int md, int grid, hipStream_t s, const FusedArgs &A) {
+  dispatch<Choices<4, 8>, Choices<1, 2, 3>, Choices<1, 3, 2>, Choices<VAR_VA, VAR_PLAIN>>([&](auto nw, auto nl, auto md, auto var) {
+    hipLaunchKernelGGL((k_fused<nw, false, 3, true, nl, md, var == VAR_VA, 2>), dim3(grid), dim3(nw * 64), 0, s, A);
+  }, nw, A.NL, md, fused_variant(A.vatom, false));
+}
+#endif
 #if AHIP_FUSED_PART == 2
 // the f16x2 instances (fused_h.o): two-body table only; latent MLP depth 1..3 (profiling build for depth 2 only)
 void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const FusedArgs &A) {
@@ -1106,6 +1135,7 @@ struct FusedState {
   bool ready = false, prof_on = false, dbg_on = false, clk_on = false;
   bool tbt = true;             // two-body embedding from the spline table (default) or evaluated as an MLP (option fused_tb=mlp)
   int md = 2;                  // hidden layers of the latent MLP (template parameter MD of k_fused)
+  int rd = 1;                  // hidden layers of the read-out MLP (template parameter RD)
   Arith arith = AR_F32;        // arith_policy.h: resolve_arith (every arithmetic has its k_fused instances)
   DevBuf prof, dbg;
   int ncu = 256;
@@ -1146,22 +1176,9 @@ static int append_frag_b(std::vector<float> &out, const double *W, int K, int N,
             }
   return 2 * nterm * KS * (NT / 2);
 }
-bool fused_model_supported(const Model &m, std::string *why) {
-  const HostModel &h = m.hm;
-  auto no = [&](const char *msg) { if (why) *why = msg; return false; };
-  if (h.l_max != 1) return no("fused kernels need l_max = 1");
-  if (!fused_widths_fit(h)) return no("fused kernels hold at most U=32, S=64, MLP width 64, read-out width 32 (narrower models run zero-padded)");
-  if (h.mlp_depth < 1 || h.mlp_depth > 3 || h.readout_depth != 1) return no("fused kernels need MLP depth 1..3 and read-out depth 1");
-  if (h.mlp_depth != 2) {           // round 5: depth 1 and 3 on the f16x2 instances with the tabulated two-body embedding
-    if (resolve_arith(m, false) != AR_F16X2) return no("MLP depth 1 / 3 runs on the f16x2 arithmetic with the tabulated two-body embedding only (fused_arith=auto|f16x2, fused_tb=table, allow_tf32 = 0)");
-  }
-  // the radial basis only enters through the two-body embedding: tabulated (default) any number of Bessel functions will do, evaluated in the kernel
-  // (fused_tb=mlp) its first linear is laid out for 8
-  if (h.num_bessels < 1 || (!fused_tb_is_table(m) && h.num_bessels != 8)) return no("fused_tb=mlp needs 8 Bessel functions (the tabulated two-body embedding takes any number)");
-  if (h.num_layers < 1 || h.num_layers > MAXNL) return no("fused kernels need 1..3 layers");
-  if (h.num_types > 16) return no("fused kernels support at most 16 model types (4-bit packed edge types)");
-  return true;
-}
+// the gate itself: fused_shapes.h
+bool fused_model_supported(const Model &m, std::string *why) { return fused_narrow_supported(m.hm, resolve_arith(m, false), fused_tb_is_table(m), why); }
+static_assert(MAXNL == 3, "fused_shapes.h: 1..3 layers");
 
 static void fused_prepare(Model &m) {
   if (!m.fused_state) m.fused_state = new FusedState();
@@ -1184,7 +1201,8 @@ static void fused_prepare(Model &m) {
   st.tbt = fused_tb_is_table(m);
   st.arith = resolve_arith(m, false);
   st.md = h.mlp_depth;
-  const int MD = st.md;
+  st.rd = h.readout_depth;
+  const int MD = st.md, RD = st.rd;
   const bool b3 = st.arith == AR_BF16X3 || st.arith == AR_TF32EQ, h2 = st.arith == AR_F16X2, tbt = st.tbt;
   const int nterm = st.arith == AR_BF16X3 ? 3 : 2;
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
@@ -1207,6 +1225,7 @@ static void fused_prepare(Model &m) {
         for (int n = 0; n < 32; ++n) w3r[(size_t)i * 32 + n] += W3[(size_t)i * 64 + q] * Wr[(size_t)q * 32 + n];
   }
   if (!tbt && MD != 2) throw UnsupportedError("fused_tb=mlp needs MLP depth 2");
+  if (RD != 1 && !h2) throw UnsupportedError("fused kernels: read-out depth 2 has f16x2 instances only");      // (fused_model_supported keeps such a model away)
   if (!tbt) {
     fwd(wc, 8, 64);
     fwd(T_("tb.w1"), 64, 64);
@@ -1228,6 +1247,10 @@ static void fused_prepare(Model &m) {
       fwd(w3r.data(), 64, 32);
       fwd(T_("out.w0"), 64, 32);
     }
+  }
+  if (RD == 2) {      // the read-out's second hidden layer, forward and transposed: two half-ring blocks (k_fused: RD)
+    fwd(T_("out.w1"), 32, 32);
+    bwd(T_("out.w1"), 32, 32);
   }
   bwd(T_("out.w0"), 64, 32);
   for (int k = NL - 1; k >= 0; --k) {
@@ -1323,6 +1346,7 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
       // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
       A.tchunk = (nedges_est / (16 * shape) > (long long)g * 256) ? TCHUNK : 1;
       if (const char *tc = std::getenv("AHIP_TCHUNK")) A.tchunk = std::max(1, std::atoi(tc));       // experiments
+      if (st.arith == AR_F16X2 && st.rd == 2) { fused_launch_f16_rd2(shape, st.md, g, s, A); continue; }                     // fused_hr.o
       if (st.arith == AR_F16X2) { fused_launch_f16(shape, st.prof_on, st.md, g, s, A); continue; }                        // fused_h.o
       if (st.arith != AR_F32) { fused_launch_bf16(shape, st.prof_on, st.arith, st.tbt, g, s, A); continue; }     // fused_bf.o
       dispatch<Choices<4, 8>, Choices<1, 0>, Choices<1, 2, 3>, Variants>([&](auto nw, auto tb, auto nl, auto var) {

@@ -671,7 +671,7 @@ static void append_two_body_table(std::vector<float> &w, const HostModel &h, con
 static int w_mark(std::vector<float> &w) { while (w.size() % 64) w.push_back(0.f); return (int)w.size(); }
 // What every fused kernel's prepare step does once its own weight stream is in `w` (Args: FusedArgs / FusedLxArgs): the two-body table (tbt; k_fused with
 // fused_tb=mlp has none), the path weights [layer][NP][U] (each times cbase[path] when cbase is given: the grouped tensor product of fused_lx2.hip), residual
-// weights, read-out, scale / shift, the upload into wbuf, the scalar arguments, and on the f16x2 arithmetic the verdict on the stream's float16 range
+// weights, the read-out's final vector, scale / shift, the upload into wbuf, the scalar arguments, and on the f16x2 arithmetic the verdict on the stream's float16 range
 // findings h_flags (engine.h: H_RANGE_*) plus the alarm word.  Returns the device's CU count.
 template <class Args>
 static int fused_prepare_tail(Model &m, const HostModel &h, std::vector<float> &w, Args &A, DevBuf &wbuf, bool tbt, int NP, int U, const double *cbase, Arith arith, int h_flags) {
@@ -692,7 +692,7 @@ static int fused_prepare_tail(Model &m, const HostModel &h, std::vector<float> &
     const HostTensor &res = h.get("l" + std::to_string(k + 1) + ".res");
     A.o_res[k] = w_mark(w); w.push_back((float)res.data[0]); w.push_back((float)res.data[1]);
   }
-  A.o_out1 = w_mark(w); for (int u = 0; u < 32; ++u) w.push_back((float)h.get("out.w1").data[u]);
+  A.o_out1 = w_mark(w); for (int u = 0; u < 32; ++u) w.push_back((float)h.get("out.w" + std::to_string(h.readout_depth)).data[u]);      // the read-out's final 32 -> 1 vector
   A.o_scale = w_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("scale").data[t]);
   A.o_shift = w_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("shift").data[t]);
   w_mark(w);

@@ -152,8 +152,8 @@ enum { PX_GEOM = 0, PX_EMB, PX_ENV, PX_TP, PX_LAT, PX_MIX, PX_OUT, PX_BLAT, PX_B
 // run-time branches inside them the register allocator shuffles dozens of spill slots at every join (load, wait, store).
 // VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
 // MD: hidden layers of the latent MLP (allegro_mlp_hidden_layers_depth; 2 in the reference test YAML).  1 and 3 exist on the f16x2 arithmetic only, as in k_fused;
-// every MD-dependent piece below is `if constexpr`, and the MD = 2 instances are what they were before the parameter existed.
-template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2>
+// every MD-dependent piece below is `if constexpr`, and the MD = 2 instances are what they were before the parameter existed.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 only, built in fused_lx_r.o).
+template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1>
 __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) {
   constexpr int L = ShapeX::L, UT = ShapeX::UT, NW = ShapeX::NW;
   using S = ShapeX;
@@ -161,6 +161,7 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
   constexpr bool SAVEZ = AR == 3;          // f16x2: raw pre-activation rows of the last hidden layer instead of silu' rows, no u rows (see fused.hip)
   static_assert(MD >= 1 && MD <= 3 && (MD == 2 || AR == 3), "latent MLP depth 1 / 3: f16x2 instances only");
   static_assert(MD == 2 || !PROF, "profiled instances: depth 2");
+  static_assert(RD == 1 || (RD == 2 && AR == 3 && !PROF), "read-out depth 2: f16x2 instances only, not profiled");
   // The last model layer keeps its latent-MLP rows in the staging tile: the last hidden layer in images ZIMG .. ZIMG + 3, the one below it (MD >= 2) in images 0..3.
   // A wave's slots hold 9 images; depth 3 would need 12, so the silu' rows of its hidden layer 1 go to the per-wave scratch like a non-last layer's.
   constexpr int ZIMG = MD == 1 ? 0 : 4;
@@ -428,14 +429,24 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
     __builtin_amdgcn_sched_barrier(0);
     f32x4 zr[2];
     lx_lin<AR, 4, 2, false>(WB, wp, x, zr, v16, ring, EpiNone{});
-    f32x4 wo1[2];
+    f32x4 zr2[2];            // RD = 2: pre-activations of the read-out's second hidden layer
+    if constexpr (RD == 2) {
+      f32x4 hr[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) hr[t][r] = silu1(zr[t][r]);
+      lx_lin<AR, 2, 2, false, 0>(WB, wp, hr, zr2, v16, ring, EpiNone{});
+    }
+    f32x4 (&zo)[2] = RD == 2 ? zr2 : zr;        // pre-activations of the last hidden layer
+    f32x4 wo1[2];            // the read-out's final 32 -> 1 vector (out.w1, or out.w2 of a depth-2 read-out)
 #pragma unroll
     for (int t = 0; t < 2; ++t) wo1[t] = *(const f32x4 *)(Wb + A.o_out1 + 16 * t + 4 * g);
     float eps = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) eps += silu1(zr[t][r]) * wo1[t][r];
+      for (int r = 0; r < 4; ++r) eps += silu1(zo[t][r]) * wo1[t][r];
     eps = gsum(eps);
     pin(eps);
 
@@ -457,7 +468,16 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) dzr[t][r] = deps * wo1[t][r] * dsilu1(zr[t][r]);
+        for (int r = 0; r < 4; ++r) dzr[t][r] = deps * wo1[t][r] * dsilu1(zo[t][r]);
+      if constexpr (RD == 2) {
+        // dzr holds the gradient of zr2: back through out.w1^T and the first hidden layer's SiLU (linear in deps, so the f16x2 power-of-two scale passes through)
+        f32x4 dhr[2];
+        lx_lin<AR, 2, 2, false, 4>(WB, wp, dzr, dhr, v16, ring, EpiNone{});
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dzr[t][r] = dhr[t][r] * dsilu1(zr[t][r]);
+      }
       lx_lin<AR, 2, 4, false>(WB, wp, dzr, dx, v16, ring, EpiNone{});
     }
 #pragma unroll
@@ -763,21 +783,22 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
 }
 
 // ---------------------------------------------------------------------------- host side
-
-bool fusedlx_model_supported(const Model &m, std::string *why) {
-  const HostModel &h = m.hm;
-  auto no = [&](const char *msg) { if (why) *why = msg; return false; };
-  if (h.l_max != 2) return no("wide fused kernels are built for l_max = 2");
-  if (!fused_widths_fit(h)) return no("wide fused kernels hold at most 64 tensor features, S=64, MLP width 64, read-out width 32 (narrower models run zero-padded)");
-  if (h.mlp_depth < 1 || h.mlp_depth > 3 || h.readout_depth != 1) return no("fused kernels need MLP depth 1..3 and read-out depth 1");
-  if (h.mlp_depth != 2) {           // depth 1 and 3 on the f16x2 instances (template parameter MD of both wide kernels)
-    if (resolve_arith(m, true) != AR_F16X2) return no("MLP depth 1 / 3 runs on the f16x2 arithmetic only on the wide fused kernels (fused_arith=auto|f16x2)");
-  }
-  if (h.num_bessels < 1) return no("no radial basis");      // any number of Bessel functions: the two-body embedding is always tabulated here
-  if (h.num_layers < 1 || h.num_layers > LX_MAXNL) return no("fused kernels need 1..3 layers");
-  if (h.num_types > 16) return no("fused kernels support at most 16 model types (4-bit packed edge types)");
-  return true;
+// This file is compiled twice (Makefile): AHIP_LX_PART 0 = the host side and the read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone (fused_lx_r.o)
+#ifndef AHIP_LX_PART
+#define AHIP_LX_PART 0
+#endif
+void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
+#if AHIP_LX_PART == 1
+void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // f16x2 only, plain and per-atom virial, not profiled
+  dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    hipLaunchKernelGGL((k_fused_lx<nl, false, 3, v == VAR_VA, md, 2>), dim3(grid), dim3(ShapeX::NW * 64), 0, s, A);
+  }, nl, var, md);
 }
+#else
+
+// the gate itself: fused_shapes.h
+bool fusedlx_model_supported(const Model &m, std::string *why) { return fused_wide_supported(m.hm, resolve_arith(m, true), why); }
+static_assert(LX_MAXNL == 3, "fused_shapes.h: 1..3 layers");
 
 // k_fused_lx's weight stream, in the order one tile consumes it: whole-matrix fragments (see k_fused_lx)
 static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, Arith arith) {
@@ -819,6 +840,10 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
     }
   }
   fwd(T_("out.w0"), 64, 32);
+  if (h.readout_depth == 2) {      // the read-out's second hidden layer, forward and transposed: half a ring each (k_fused_lx: RD)
+    fwd(T_("out.w1"), 32, 32);
+    bwd(T_("out.w1"), 32, 32);
+  }
   bwd(T_("out.w0"), 64, 32);
   for (int k = NL - 1; k >= 0; --k) {
     const std::string lk = "l" + std::to_string(k + 1);
@@ -839,8 +864,9 @@ bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
   if (!lx_list_fits(m, why)) return false;
   FusedLxState &st = lx_prepare<ShapeX>(m, m.fusedlx_state, nullptr, false, lx_stream);
   static_assert(PX_N == LX_NPHASE, "profile phases");
-  if (st.md != 2 && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 has no float32 instance");      // (fusedlx_model_supported keeps such a model away)
+  if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
   lx_run<ShapeX>(m, a, st, "fused_lx", [&](const FusedLxArgs &A, int grid, int var) {
+    if (st.rd == 2) { fusedlx_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_r.o
     dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
       if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)
         hipLaunchKernelGGL((k_fused_lx<nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(ShapeX::NW * 64), 0, a.stream, A);
@@ -854,4 +880,5 @@ void fusedlx_free(Model &m) {
   lx_free(m.fusedlx2_state);
 }
 
+#endif   // AHIP_LX_PART
 }  // namespace ahip

@@ -213,14 +213,15 @@ enum { PP_GEOM = 0, PP_EMB, PP_ENV, PP_TP, PP_LAT, PP_MIX, PP_OUT, PP_BLAT, PP_B
 // ---------------------------------------------------------------------------- the kernel
 // VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
 // MD: hidden layers of the latent MLP (1..3; 1 and 3 on the f16x2 arithmetic only, as in k_fused and k_fused_lx).  Every hidden layer is split by output tile, so each
-// one beyond the first costs one more pair hand-over forward and one more backward; MD is a compile-time fact, so all eight waves still meet the same barriers.
-template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2>
+// one beyond the first costs one more pair hand-over forward and one more backward; MD is a compile-time fact, so all eight waves still meet the same barriers.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 only, built in fused_lx2_r.o).
+template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1>
 __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
   using S = ShapeP;
   constexpr int NTHREADS = 512, D = S::D, U = S::U, HT = S::HT, EWH = S::EWH, MAXA = S::MAXA, STG_LD = S::STG_LD, ENVA = S::ENVA, NP = S::NP, L = S::L;
   constexpr bool SAVEZ = AR == 3;          // f16x2: raw pre-activation rows of the last hidden layer instead of silu' rows, no u rows (see fused.hip)
   static_assert(MD >= 1 && MD <= 3 && (MD == 2 || AR == 3), "latent MLP depth 1 / 3: f16x2 instances only");
   static_assert(MD == 2 || !PROF, "profiled instances: depth 2");
+  static_assert(RD == 1 || (RD == 2 && AR == 3 && !PROF), "read-out depth 2: f16x2 instances only, not profiled");
   __shared__ LdsP lds;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
@@ -475,14 +476,24 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
     __builtin_amdgcn_sched_barrier(0);
     f32x4 zr[2];
     lx_lin<AR, 4, 2, false>(WB, wp, x, zr, V16(), ring, EpiNone{});
-    f32x4 wo1[2];
+    f32x4 zr2[2];            // RD = 2: pre-activations of the read-out's second hidden layer
+    if constexpr (RD == 2) {
+      f32x4 hr[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) hr[t][r] = silu1(zr[t][r]);
+      lx_lin<AR, 2, 2, false, 0>(WB, wp, hr, zr2, V16(), ring, EpiNone{});
+    }
+    f32x4 (&zo)[2] = RD == 2 ? zr2 : zr;        // pre-activations of the last hidden layer
+    f32x4 wo1[2];            // the read-out's final 32 -> 1 vector (out.w1, or out.w2 of a depth-2 read-out)
 #pragma unroll
     for (int t = 0; t < 2; ++t) wo1[t] = *(const f32x4 *)(Wb + A.o_out1 + 16 * t + 4 * g);
     float eps = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) eps += silu1(zr[t][r]) * wo1[t][r];
+      for (int r = 0; r < 4; ++r) eps += silu1(zo[t][r]) * wo1[t][r];
     eps = gsum(eps);
     pin(eps);
 
@@ -504,7 +515,16 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) dzr[t][r] = deps * wo1[t][r] * dsilu1(zr[t][r]);
+        for (int r = 0; r < 4; ++r) dzr[t][r] = deps * wo1[t][r] * dsilu1(zo[t][r]);
+      if constexpr (RD == 2) {
+        // dzr holds the gradient of zr2: back through out.w1^T and the first hidden layer's SiLU (linear in deps, so the f16x2 power-of-two scale passes through)
+        f32x4 dhr[2];
+        lx_lin<AR, 2, 2, false, 4>(WB, wp, dzr, dhr, V16(), ring, EpiNone{});
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dzr[t][r] = dhr[t][r] * dsilu1(zr[t][r]);
+      }
       lx_lin<AR, 2, 4, false>(WB, wp, dzr, dx, V16(), ring, EpiNone{});
     }
     float dfc_part = 0.f;    // partial sums over the own channels / own latent tiles: they meet in lds.ych at the end of the tile
@@ -840,6 +860,18 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
 }
 
 // ---------------------------------------------------------------------------- host side
+// This file is compiled twice (Makefile): AHIP_LX_PART 0 = the host side and the read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone (fused_lx2_r.o)
+#ifndef AHIP_LX_PART
+#define AHIP_LX_PART 0
+#endif
+void fusedlx2_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
+#if AHIP_LX_PART == 1
+void fusedlx2_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // f16x2 only, plain and per-atom virial, not profiled
+  dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    hipLaunchKernelGGL((k_fused_lx2<nl, false, 3, v == VAR_VA, md, 2>), dim3(grid), dim3(ShapeP::NW * 64), 0, s, A);
+  }, nl, var, md);
+}
+#else
 // dense copy of 16 x 16 tiles of W (row-major, leading dimension ldw): rows rt[], columns ct[]
 static std::vector<double> gather_tiles(const double *W, int ldw, const std::vector<int> &rt, const std::vector<int> &ct) {
   const int K = 16 * (int)rt.size(), N = 16 * (int)ct.size();
@@ -893,6 +925,10 @@ static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h,
       }
     }
     put(T_("out.w0"), 32, xo, {0, 1});
+    if (h.readout_depth == 2) {      // the read-out's second hidden layer, forward and transposed, whole in both halves' streams: half a ring each (k_fused_lx2: RD)
+      put(T_("out.w1"), 32, {0, 1}, {0, 1});
+      putT(T_("out.w1"), 32, 32, {0, 1}, {0, 1});
+    }
     putT(T_("out.w0"), 64, 32, {0, 1}, xo);
     for (int k = NL - 1; k >= 0; --k) {
       const std::string lk = "l" + std::to_string(k + 1);
@@ -914,8 +950,9 @@ bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
   if (!lx_list_fits(m, why)) return false;
   FusedLxState &st = lx_prepare<ShapeP>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream);     // path weights x the path's base |c| (tp_g)
   static_assert(PP_N == LX_NPHASE, "profile phases");
-  if (st.md != 2 && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 has no float32 instance");      // (fusedlx_model_supported keeps such a model away)
+  if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
   lx_run<ShapeP>(m, a, st, "fused_lx2", [&](const FusedLxArgs &A, int grid, int var) {
+    if (st.rd == 2) { fusedlx2_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_r.o
     dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
       if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)
         hipLaunchKernelGGL((k_fused_lx2<nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(ShapeP::NW * 64), 0, a.stream, A);
@@ -924,4 +961,5 @@ bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
   return true;
 }
 
+#endif   // AHIP_LX_PART
 }  // namespace ahip

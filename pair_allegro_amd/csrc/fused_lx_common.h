@@ -84,7 +84,7 @@ struct FusedLxState {
   FusedLxArgs args;
   bool ready = false, prof_on = false;
   int ncu = 256;
-  int md = 2;                  // hidden layers of the latent MLP (template parameter MD of the kernels)
+  int md = 2, rd = 1;          // hidden layers of the latent MLP and of the read-out MLP (template parameters MD, RD of the kernels)
   Arith arith = AR_F32;        // AR_F32 or AR_F16X2 (arith_policy.h: resolve_arith, wide)
 };
 
@@ -105,7 +105,7 @@ static FusedLxState &lx_prepare(Model &m, FusedLxState *&slot, const double *cba
   int h_flags = stream(w, A, h, st.arith);
   if (st.arith == AR_F16X2 && tiny) h_flags |= model_tiny_linear(h);
   st.ncu = fused_prepare_tail(m, h, w, A, st.wbuf, true, S::NP, S::U, cbase, st.arith, h_flags);
-  st.md = h.mlp_depth;
+  st.md = h.mlp_depth; st.rd = h.readout_depth;
   A.wave_scratch = (long long)S::R_TOTAL(NL, st.md) * ROW;
   st.scratch.reserve((size_t)st.ncu * S::NW * A.wave_scratch * sizeof(float));
   A.scratch = st.scratch.as<float>();
@@ -132,7 +132,7 @@ static bool lx_list_fits(const Model &m, std::string *why) {
   return true;
 }
 
-// phases of the profiled instances (AHIP_FUSED_PROF=1, 3 layers, MLP depth 2): the kernels' PX_* / PP_* enums
+// phases of the profiled instances (AHIP_FUSED_PROF=1, 3 layers, MLP depth 2, read-out depth 1): the kernels' PX_* / PP_* enums
 static constexpr int LX_NPHASE = 13;
 // One evaluation on a prepared wide kernel (shape S): tile packing, arguments, `launch(A, grid, variant)` (the file's instance dispatch; variant:
 // fused_common.h, VAR_*), the energy / virial sums, and the per-phase profile printed as "[ahip <name> prof]" (tools/abprof.sh reads it)
@@ -148,7 +148,7 @@ static void lx_run(Model &m, const ComputeArgs &a, FusedLxState &st, const char 
   // claims of TCHUNK tiles amortise the counter's round trip; with few tiles per workgroup the last claim decides the makespan
   // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
   A.tchunk = (fused_nedges_estimate(m) / S::SLOTS > (long long)grid * 256) ? TCHUNK : 1;
-  const bool prof = st.prof_on && A.NL == 3 && st.md == 2;
+  const bool prof = st.prof_on && A.NL == 3 && st.md == 2 && st.rd == 1;
   {
     StageTimer tm(m, "model_fused", s);
     if (prof && !A.vatom) {

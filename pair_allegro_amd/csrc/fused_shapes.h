@@ -1,0 +1,125 @@
+// Which fused kernel serves a model, at which shape, and why not: the shape rule of the fused side in one place.  Host-only and free of HIP and of the
+// engine's Model (like arith_policy.h and fused_lx_rows.h): the gates of the kernel files (fused_model_supported, fusedlx_model_supported), the dispatch of
+// the C-ABI (allegro_hip.hip: fused_family, run_model_once), the padding of engine.h (fused_host_model) and a stand-alone CPU test (tests/test_fused_shapes.py)
+// read the same rules.
+//
+//   family    kernel        runs at                   serves
+//   k_fused   k_fused       l_max 1, 32 features      l_max = 1, U <= 32
+//   lx32      k_fused_lx    l_max 2, 32 features      l_max = 2, U <= 32
+//   lx64      k_fused_lx2   l_max 2, 64 features      l_max = 2, 33 <= U <= 64;  l_max = 1, 33 <= U <= 64 (lifted: model_io.h, lift_host_model)
+// all with S <= 64 scalars, MLP width <= 64, read-out width <= 32 (narrower models run zero-padded: pad_host_model), 1..3 layers, <= 16 types.
+//
+// Instances by (MD, RD) = (latent MLP depth, read-out depth): (2, 1) on every arithmetic the family has; every other pair of MD in 1..3, RD in 1..2 on the
+// f16x2 arithmetic only (k_fused: with the tabulated two-body embedding).  Read-out depth 0 (a linear read-out) would need a different fold of the last
+// layer's output linear into the read-out and has no instance.
+#pragma once
+#include <string>
+
+#include "arith_policy.h"
+#include "model_io.h"
+
+namespace ahip {
+
+enum class FusedFamily { none, k_fused, lx32, lx64 };
+inline const char *fused_family_name(FusedFamily f) {
+  return f == FusedFamily::k_fused ? "k_fused" : f == FusedFamily::lx32 ? "lx32" : f == FusedFamily::lx64 ? "lx64" : "none";
+}
+inline bool fused_is_wide(FusedFamily f) { return f == FusedFamily::lx32 || f == FusedFamily::lx64; }
+
+// the kernels' fixed widths: scalars, MLP width, read-out width (all families); tensor features and l_max per family
+inline constexpr int FUSED_SF = 64, FUSED_WF = 64, FUSED_RF = 32;
+inline int fused_UF(FusedFamily f) { return f == FusedFamily::lx64 ? 64 : 32; }
+inline int fused_l_run(FusedFamily f) { return f == FusedFamily::k_fused ? 1 : 2; }
+
+// The family whose SHAPE (l_max, tensor features) the model has, whatever its depths and the arithmetic: it decides the padded / lifted model, the tile
+// shape and the heavy-centre threshold.  none: no fused kernel holds this l_max / this many tensor features.
+inline FusedFamily fused_shape_class(const HostModel &h) {
+  if (h.U < 1 || h.U > 64) return FusedFamily::none;
+  if (h.l_max == 1) return h.U <= 32 ? FusedFamily::k_fused : FusedFamily::lx64;
+  if (h.l_max == 2) return h.U <= 32 ? FusedFamily::lx32 : FusedFamily::lx64;
+  return FusedFamily::none;
+}
+// S, MLP width, read-out width and tensor features within the fixed widths of k_fused (wide = false) or of the wide kernels
+inline bool fused_widths_fit(const HostModel &h, bool wide) {
+  return h.S >= 1 && h.S <= FUSED_SF && h.mlp_width >= 1 && h.mlp_width <= FUSED_WF && h.readout_width >= 1 && h.readout_width <= FUSED_RF && h.U >= 1 &&
+         h.U <= (wide ? 64 : 32);
+}
+// the model is already at family f's shape: nothing to pad or lift
+inline bool fused_shape_exact(const HostModel &h, FusedFamily f) {
+  return h.S == FUSED_SF && h.mlp_width == FUSED_WF && h.readout_width == FUSED_RF && h.U == fused_UF(f) && h.l_max == fused_l_run(f);
+}
+// the model at family f's shape: lifted to the family's l_max where it is lower, then zero-padded
+inline HostModel fused_shaped_model(const HostModel &h, FusedFamily f) {
+  return pad_host_model(lift_host_model(h, fused_l_run(f)), FUSED_SF, fused_UF(f), FUSED_WF, FUSED_RF);
+}
+
+// a compiled instance of family f exists for this arithmetic (k_fused: and two-body mode) and these depths
+inline bool fused_instance_exists(FusedFamily f, Arith ar, bool tb_table, int MD, int RD) {
+  if (f == FusedFamily::none || MD < 1 || MD > 3 || RD < 1 || RD > 2) return false;
+  if (MD == 2 && RD == 1) return fused_is_wide(f) ? (ar == AR_F32 || ar == AR_F16X2) : (ar != AR_F16X2 || tb_table);
+  return ar == AR_F16X2 && (fused_is_wide(f) || tb_table);
+}
+
+inline constexpr const char *FUSED_WHY_DEPTHS =
+    "fused kernels need MLP depth 1..3 and read-out depth 1..2 (a linear read-out, depth 0, needs a different fold of the last layer and has no instance)";
+
+// k_fused's gate: `arith` is the arithmetic the model's options resolve to on k_fused (resolve_arith, wide = false)
+inline bool fused_narrow_supported(const HostModel &h, Arith arith, bool tb_table, std::string *why) {
+  auto no = [&](const char *msg) { if (why) *why = msg; return false; };
+  if (h.l_max != 1) return no("fused kernels need l_max = 1");
+  if (!fused_widths_fit(h, false)) return no("fused kernels hold at most U=32, S=64, MLP width 64, read-out width 32 (narrower models run zero-padded)");
+  if (h.mlp_depth < 1 || h.mlp_depth > 3 || h.readout_depth < 1 || h.readout_depth > 2) return no(FUSED_WHY_DEPTHS);
+  if (h.mlp_depth != 2) {           // depth 1 and 3 on the f16x2 instances with the tabulated two-body embedding
+    if (arith != AR_F16X2) return no("MLP depth 1 / 3 runs on the f16x2 arithmetic with the tabulated two-body embedding only (fused_arith=auto|f16x2, fused_tb=table, allow_tf32 = 0)");
+  }
+  if (h.readout_depth == 2) {       // likewise (template parameter RD of k_fused)
+    if (arith != AR_F16X2) return no("read-out depth 2 runs on the f16x2 arithmetic with the tabulated two-body embedding only (fused_arith=auto|f16x2, fused_tb=table, allow_tf32 = 0)");
+  }
+  // the radial basis only enters through the two-body embedding: tabulated (default) any number of Bessel functions will do, evaluated in the kernel
+  // (fused_tb=mlp) its first linear is laid out for 8
+  if (h.num_bessels < 1 || (!tb_table && h.num_bessels != 8)) return no("fused_tb=mlp needs 8 Bessel functions (the tabulated two-body embedding takes any number)");
+  if (h.num_layers < 1 || h.num_layers > 3) return no("fused kernels need 1..3 layers");
+  if (h.num_types > 16) return no("fused kernels support at most 16 model types (4-bit packed edge types)");
+  return true;
+}
+
+// the wide kernels' gate: `arith` is what the options resolve to on them (resolve_arith, wide = true)
+inline bool fused_wide_supported(const HostModel &h, Arith arith, std::string *why) {
+  auto no = [&](const char *msg) { if (why) *why = msg; return false; };
+  if (h.l_max != 2 && !(h.l_max == 1 && h.U > 32)) return no("wide fused kernels are built for l_max = 2 (an l_max = 1 model runs on them lifted when it has 33..64 tensor features)");
+  if (!fused_widths_fit(h, true)) return no("wide fused kernels hold at most 64 tensor features, S=64, MLP width 64, read-out width 32 (narrower models run zero-padded)");
+  if (h.mlp_depth < 1 || h.mlp_depth > 3 || h.readout_depth < 1 || h.readout_depth > 2) return no(FUSED_WHY_DEPTHS);
+  if (h.mlp_depth != 2) {           // depth 1 and 3 on the f16x2 instances (template parameter MD of both wide kernels)
+    if (arith != AR_F16X2) return no("MLP depth 1 / 3 runs on the f16x2 arithmetic only on the wide fused kernels (fused_arith=auto|f16x2)");
+  }
+  if (h.readout_depth == 2) {       // likewise (template parameter RD)
+    if (arith != AR_F16X2) return no("read-out depth 2 runs on the f16x2 arithmetic only on the wide fused kernels (fused_arith=auto|f16x2)");
+  }
+  if (h.num_bessels < 1) return no("no radial basis");      // any number of Bessel functions: the two-body embedding is always tabulated here
+  if (h.num_layers < 1 || h.num_layers > 3) return no("fused kernels need 1..3 layers");
+  if (h.num_types > 16) return no("fused kernels support at most 16 model types (4-bit packed edge types)");
+  return true;
+}
+
+// The decision for a model: the family that serves it (none: `why` holds the reasons of both gates), the shape it runs at and the arithmetic of its instance.
+struct FusedDecision {
+  FusedFamily family = FusedFamily::none;
+  int l_run = 0, UF = 0;            // l_max and tensor features of the kernel (the model runs lifted / zero-padded to them)
+  Arith arith = AR_F32;
+  std::string why;
+};
+inline FusedDecision fused_decide(const HostModel &h, Arith arith_narrow, Arith arith_wide, bool tb_table) {
+  FusedDecision d;
+  std::string why1, why2;
+  if (fused_narrow_supported(h, arith_narrow, tb_table, &why1)) { d.family = FusedFamily::k_fused; d.arith = arith_narrow; }
+  else if (fused_wide_supported(h, arith_wide, &why2)) { d.family = fused_shape_class(h); d.arith = arith_wide; }
+  else { d.why = why1 + "; " + why2; return d; }
+  d.l_run = fused_l_run(d.family); d.UF = fused_UF(d.family);
+  return d;
+}
+// the same from an effective option (arith_effective) and the state of fused_arith=auto
+inline FusedDecision fused_decide(const HostModel &h, ArithOpt opt, bool degraded, bool force_f32, bool tb_table) {
+  return fused_decide(h, resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, false), resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, true), tb_table);
+}
+
+}  // namespace ahip

@@ -4,7 +4,10 @@
 // but the weights come from the blob instead of a pickled module.
 #include "model_io.h"
 
+#include <algorithm>
+#include <array>
 #include <cstdint>
+#include <cstdlib>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -63,6 +66,67 @@ HostModel pad_host_model(const HostModel &h, int SF, int UF, int WF, int RF) {
     pad("out.w0", S, R, SF, RF, id, id);
     for (int k = 1; k < h.readout_depth; ++k) pad("out.w" + std::to_string(k), R, R, RF, RF, id, id);
     pad("out.w" + std::to_string(h.readout_depth), R, 1, RF, 1, id, id);
+  }
+  return p;
+}
+
+// (l1, l2, l3) paths of the tensor product in the order of the `tp` rows (pair_allegro_amd/cg.py: tp_paths): l3-major, then l1, then l2
+static std::vector<std::array<int, 3>> tp_path_list(int lmax, bool scalar_only) {
+  std::vector<std::array<int, 3>> paths;
+  for (int l3 = 0; l3 <= (scalar_only ? 0 : lmax); ++l3)
+    for (int l1 = 0; l1 <= lmax; ++l1)
+      for (int l2 = 0; l2 <= lmax; ++l2)
+        if (std::abs(l1 - l2) <= l3 && l3 <= l1 + l2) paths.push_back({l1, l2, l3});
+  return paths;
+}
+
+HostModel lift_host_model(const HostModel &h, int LF) {
+  const int L = h.l_max, U = h.U, NL = h.num_layers;
+  if (LF < L) throw std::runtime_error("lift_host_model: the model has a larger l_max than the target");
+  if (LF == L) return h;
+  HostModel p = h;
+  p.l_max = LF;
+  // (l, u) weight vectors [rows][U (L + 1)]: the columns stay where they are, U (LF - L) zero columns behind them
+  auto widen = [&](const std::string &name) {
+    const HostTensor &t = h.get(name);
+    const int C0 = U * (L + 1), C1 = U * (LF + 1);
+    if (t.shape.size() != 2 || t.shape[1] != C0) throw std::runtime_error("lift_host_model: unexpected shape of '" + name + "'");
+    HostTensor o;
+    o.shape = {t.shape[0], C1};
+    o.data.assign((size_t)t.shape[0] * C1, 0.0);
+    for (int r = 0; r < t.shape[0]; ++r)
+      for (int c = 0; c < C0; ++c) o.data[(size_t)r * C1 + c] = t.data[(size_t)r * C0 + c];
+    p.tensors[name] = o;
+  };
+  widen("emb.w");
+  for (int k = 1; k <= NL; ++k) {
+    const std::string lk = "l" + std::to_string(k);
+    widen(lk + ".env");
+    {   // path weights: every row to the row of the same (l1, l2, l3) in the larger list, the new paths zero
+      const bool scalar_only = k == NL;
+      const auto src = tp_path_list(L, scalar_only), dst = tp_path_list(LF, scalar_only);
+      const HostTensor &t = h.get(lk + ".tp");
+      if (t.shape.size() != 2 || t.shape[0] != (int)src.size() || t.shape[1] != U) throw std::runtime_error("lift_host_model: unexpected shape of '" + lk + ".tp'");
+      HostTensor o;
+      o.shape = {(int)dst.size(), U};
+      o.data.assign(dst.size() * (size_t)U, 0.0);
+      for (size_t a = 0; a < src.size(); ++a) {
+        size_t b = 0;
+        while (b < dst.size() && dst[b] != src[a]) ++b;
+        if (b == dst.size()) throw std::runtime_error("lift_host_model: a path of the model is missing from the target list");
+        for (int u = 0; u < U; ++u) o.data[b * U + u] = t.data[a * U + u];
+      }
+      p.tensors[lk + ".tp"] = o;
+    }
+    if (k < NL) {   // channel mixing [L + 1][U][U]: zero blocks for the new l
+      const HostTensor &t = h.get(lk + ".mix");
+      if (t.numel() != (long long)(L + 1) * U * U) throw std::runtime_error("lift_host_model: unexpected shape of '" + lk + ".mix'");
+      HostTensor o;
+      o.shape = {LF + 1, U, U};
+      o.data.assign((size_t)(LF + 1) * U * U, 0.0);
+      std::copy(t.data.begin(), t.data.end(), o.data.begin());
+      p.tensors[lk + ".mix"] = o;
+    }
   }
   return p;
 }

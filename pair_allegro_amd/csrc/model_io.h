@@ -38,6 +38,12 @@ HostModel load_model_file(const std::string &path);
 // zero path weights, zero rows / columns in every linear), so the padded model computes the same energies and forces; needs S <= SF, U <= UF, W <= WF, R <= RF.
 HostModel pad_host_model(const HostModel &h, int SF, int UF, int WF, int RF);
 
+// The same model written as an l_max = LF model (LF >= l_max): zero columns for the new l in the embedding / environment weight vectors (column l U + u does not move),
+// the `tp` rows moved to the rows of the same (l1, l2, l3) in the larger path list (every new path zero), zero channel-mixing blocks for the new l.  The new tensor
+// components are exact zeros through embedding, environment sum, tensor product and mixing, so the lifted model computes the same energies and forces bit for bit in
+// float64; it is what lets an l_max = 1 model with more than 32 tensor features run on the 64-feature l_max = 2 kernel (fused_shapes.h).
+HostModel lift_host_model(const HostModel &h, int LF);
+
 // Parses an in-memory blob.
 HostModel parse_blob(const unsigned char *p, size_t n, const std::string &origin);
 
