@@ -87,6 +87,15 @@ int ahip_model_meta(const ahip_model *m, double *r_max, int *num_types, const ch
  *                                                 layer-at-a-time kernels; "split" keeps the fused kernel for the other centres and evaluates only those few
  *                                                 (at most one centre in eight, else as "whole") on the layer-at-a-time kernels.  ahip_last_heavy_centres
  *                                                 reports them.  The cost of the split route has not been measured.
+ *   "wide_tile" = "64" | "auto"                  tile shape of the l_max = 2 kernel with up to 32 tensor features (k_fused_lx): "64" (default) keeps its 64-slot tiles, so a
+ *                                                 centre with more than 64 edges is one of the few above ("heavy"); "auto" lets the list's largest degree pick a second
+ *                                                 shape of 128 slots (8 waves) as the l_max = 1 kernel does, so centres with 65..128 edges stay on the fused kernel and only
+ *                                                 centres above 128 are heavy (the one-in-eight rule of "dense_centres" counts against 128 as well).  The second shape exists
+ *                                                 for MLP depth 2 and read-out depth 1 on the f32 and f16x2 arithmetics; for every other model (64 tensor features,
+ *                                                 l_max = 1, other depths) "auto" behaves as "64" and is not an error.  Measured on one MI355X, 108 000-atom
+ *                                                 fcc box with 78 edges per centre, 3 layers, 32 tensor features (tools/wide_tile_cost.py): 79.5 ms per evaluation
+ *                                                 with "auto" against 265 ms with "64" (every centre heavy), the latter equal to the release before the option.  Not
+ *                                                 measured on other lists, which is why the default stays "64".
  *   "timing"    = "0" | "1"                      record per-stage HIP events (ahip_get_timings)
  * Unknown keys and values are errors (AHIP_ERR_ARG).
  */

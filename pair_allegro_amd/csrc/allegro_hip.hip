@@ -273,6 +273,9 @@ int ahip_set_option(ahip_model *m, const char *key, const char *value) {
       m->opt_tile_pack = (Model::TilePack)word(Model::TILE_PACK_WORDS);
     } else if (k == "dense_centres") {
       m->opt_dense_centres = (Model::DenseCentres)word(Model::DENSE_CENTRES_WORDS);
+    } else if (k == "wide_tile") {
+      const Model::WideTile o = (Model::WideTile)word(Model::WIDE_TILE_WORDS);
+      if (o != m->opt_wide_tile) { m->opt_wide_tile = o; fusedlx_free(*m); }      // the per-wave scratch is sized for the shapes the option admits (lx_prepare)
     } else if (k == "timing") {
       m->timing = (v == "1" || v == "on" || v == "true");
     } else throw ArgError("unknown option '" + k + "'");
@@ -740,9 +743,11 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   const bool wide = fam == FusedFamily::lx32 || fam == FusedFamily::lx64;
   m->have_ett = false;
   m->nheavy = 0;
-  m->heavy_thresh = wide ? LX_TILE_SLOTS : 0;
+  // the largest tile of the wide kernel that will run: 64 slots, or 128 under wide_tile=auto where k_fused_lx has its 8-wave shape for this model
+  const int lx_slots = wide ? lx_max_tile_slots(*m, fam) : 0;
+  m->heavy_thresh = lx_slots;
   // Tile packing rides on the edge build when the tile shape is known before it runs: k_fused with every list row <= 64 entries (4-wave tiles:
-  // 64 slots, 6 centres), the wide kernels always (64 slots, 4 centres).  Otherwise (shape chosen on the device, two-pass edge build) the
+  // 64 slots, 6 centres), the wide kernels always (64 slots, 4 centres) unless the 128-slot shape of k_fused_lx may be needed (wide_tile=auto and list rows above 64).  Otherwise (shape chosen on the device, two-pass edge build) the
   // stand-alone packing kernels run after it, as before.
   m->pack_slots = m->pack_maxa = 0;
   // ... and up to 262 144 centres per call: the packing runs on the scanning wave of every unit, i.e. serially inside the edge build, and costs there what
@@ -750,7 +755,7 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   // the cost (10 648 atoms: 0.026 ms, 125 000: 0.056 ms, three times per step in the overlapped multi-rank schedule)
   if (m->opt_tile_pack != Model::TilePack::Separate && (m->inum <= 262144 || m->opt_tile_pack == Model::TilePack::Fused)) {
     if (fam == FusedFamily::k_fused) { if (m->max_list_row >= 0 && m->max_list_row <= FUSED_TILE_SLOTS) { m->pack_slots = FUSED_TILE_SLOTS; m->pack_maxa = FUSED_TILE_MAXA; } }
-    else if (wide) { m->pack_slots = LX_TILE_SLOTS; m->pack_maxa = LX_TILE_MAXA; }
+    else if (wide && (lx_slots == LX_TILE_SLOTS || (m->max_list_row >= 0 && m->max_list_row <= LX_TILE_SLOTS))) { m->pack_slots = LX_TILE_SLOTS; m->pack_maxa = LX_TILE_MAXA; }
   }
   m->tiles_packed = false;
   const bool two_pass = !edges_build_f32(*m, a);
@@ -760,7 +765,7 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
     // option dense_centres=split: the two-pass build lists the heavy centres of the fused family that will run as well (k_fused: more edges than its 8-wave tile
     // holds; the wide kernels: as on the single-pass route) and leaves heavy_thresh, nheavy and the largest light degree on the host with its own counts
     const bool split = m->opt_dense_centres == Model::DenseCentres::Split && fam != FusedFamily::none;
-    build_edges<float>(*m, a, split ? (wide ? LX_TILE_SLOTS : FUSED_MAX_TILE_SLOTS) : 0);
+    build_edges<float>(*m, a, split ? (wide ? lx_slots : FUSED_MAX_TILE_SLOTS) : 0);
   }
 #ifdef AHIP_EXPERIMENT_SWITCHES      // never in the product build: a switch that skips the model returns no forces
   static const bool edges_only = std::getenv("AHIP_EDGES_ONLY") != nullptr;     // timing experiments on the edge build alone

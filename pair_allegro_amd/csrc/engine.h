@@ -115,6 +115,8 @@ struct Model {
   static constexpr const char *EDGE_SCHEDULE_WORDS = "auto|static|dynamic";
   enum class DenseCentres { Whole, Split };
   static constexpr const char *DENSE_CENTRES_WORDS = "whole|split";
+  enum class WideTile { S64, Auto };
+  static constexpr const char *WIDE_TILE_WORDS = "64|auto";
   Path opt_path = Path::Auto;
   Precision opt_precision = Precision::Model;
   FusedTb opt_fused_tb = FusedTb::Table;    // table | mlp: two-body embedding of the fused kernel from the spline table or as an MLP
@@ -131,6 +133,7 @@ struct Model {
   TilePack opt_tile_pack = TilePack::Auto;  // auto | separate | fused (auto = fused up to 262 144 centres per call): tile packing inside the single-pass edge build where the tile shape is known up front, or always by the stand-alone kernels (A/B, tests)
   EdgeSchedule opt_edge_schedule = EdgeSchedule::Auto;   // auto | static | dynamic: unit schedule of the single-pass edge build (edges.hip)
   DenseCentres opt_dense_centres = DenseCentres::Whole;   // whole | split: a list with a few centres above a fused kernel's tile goes to the layer-at-a-time kernels as a whole, or only those centres do (allegro_hip.hip: run_model_once)
+  WideTile opt_wide_tile = WideTile::S64;                 // 64 | auto: k_fused_lx on 64-slot tiles only, or on its 128-slot shape when the list's largest degree asks for it (fused_shapes.h: fused_has_wide_tile)
   bool cutoff_strict = false;               // edge kept iff rsq < cut^2 (the KOKKOS reference path) instead of rsq <= cut^2 (the host path)
 
   // weights
@@ -265,7 +268,7 @@ void fused_free(Model &m);
 // Tile shapes (edge slots, centres) the single-pass edge build packs for (allegro_hip.hip: run_model_once); the kernel files static_assert their own shapes against them
 inline constexpr int FUSED_TILE_SLOTS = 64, FUSED_TILE_MAXA = 6;     // k_fused, 4-wave tiles
 inline constexpr int FUSED_MAX_TILE_SLOTS = 128;                     // k_fused, 8-wave tiles: the edge count above which a centre is "heavy" for it (option dense_centres=split)
-inline constexpr int LX_TILE_SLOTS = 64, LX_TILE_MAXA = 4;           // k_fused_lx and k_fused_lx2; also the edge count above which a centre is "heavy"
+inline constexpr int LX_TILE_SLOTS = lx_tile_slots(false), LX_TILE_MAXA = lx_tile_maxa(false);      // k_fused_lx2 and the 4-wave shape of k_fused_lx (fused_shapes.h); the largest shape a model may run on: lx_max_tile_slots below
 // f16x2 arithmetic (fused_h.h): device address of the model's alarm word (allocated on first use); fused_poll_alarm throws StateError when a kernel has
 // raised it -- the host-pointer call polls behind its own synchronisation, device-resident callers meet it at their next evaluation
 int *alarm_word(Model &m);
@@ -285,6 +288,12 @@ inline bool arith_may_degrade(const Model &m) { return arith_may_degrade(m.arith
 inline bool fused_tb_is_table(const Model &m) { return fused_tb_is_table(m.opt_fused_tb); }
 inline Arith resolve_arith(const Model &m, bool wide) {
   return resolve_arith(arith_effective(m.arith.opt), m.hm.allow_tf32 != 0, m.arith.degraded, m.arith.force_f32, fused_tb_is_table(m), wide);
+}
+// Edge slots of the largest tile the wide kernel of family `fam` may use for this model: the edge count above which a centre is "heavy" (listed by the edge build,
+// skipped by the kernel, evaluated by heavy_generic) and against which the one-in-eight give-up rule counts.  128 under option wide_tile=auto where the 8-wave shape
+// of k_fused_lx exists for the model's arithmetic and depths, else 64.
+inline int lx_max_tile_slots(const Model &m, FusedFamily fam) {
+  return lx_tile_slots(m.opt_wide_tile == Model::WideTile::Auto && fused_has_wide_tile(fam, resolve_arith(m, true), m.hm.mlp_depth, m.hm.readout_depth));
 }
 // the model computes in float64 (option precision, or the model file's own dtype): layer-at-a-time kernels only
 inline bool model_runs_f64(const Model &m) { return m.opt_precision == Model::Precision::Float64 || m.hm.is_f64(); }

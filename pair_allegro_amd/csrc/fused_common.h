@@ -350,14 +350,15 @@ __device__ __forceinline__ void vatom_scatter(double *W, int jat, int g, bool va
 // maxdeg != null: the tile shape is chosen HERE from the largest degree of the current edge list, which the host has not read back
 // (k_fused: 64 slots / 6 centres while every centre has <= 64 edges, else 128 / 12; the host launches both shapes of the model kernel and the one
 // that does not match returns at once).
-__device__ __forceinline__ void pack_shape(const int *maxdeg, int &tile_slots, int &maxa) {
-  if (maxdeg && *maxdeg > 64) { tile_slots = 128; maxa = 12; }
+// maxa_wide: centres of the 128-slot shape (12: k_fused; 8: k_fused_lx, fused_shapes.h)
+__device__ __forceinline__ void pack_shape(const int *maxdeg, int &tile_slots, int &maxa, int maxa_wide) {
+  if (maxdeg && *maxdeg > 64) { tile_slots = 128; maxa = maxa_wide; }
 }
 template <bool FILL>
-static __global__ void k_pack_tiles(int inum, const int *eoff, int nseg, int *seg_count, const int *seg_base, int *tile_a0, int tile_slots, int maxa, const int *maxdeg = nullptr) {
+static __global__ void k_pack_tiles(int inum, const int *eoff, int nseg, int *seg_count, const int *seg_base, int *tile_a0, int tile_slots, int maxa, const int *maxdeg = nullptr, int maxa_wide = 12) {
   int sg = blockIdx.x * blockDim.x + threadIdx.x;
   if (sg >= nseg) return;
-  pack_shape(maxdeg, tile_slots, maxa);
+  pack_shape(maxdeg, tile_slots, maxa, maxa_wide);
   int a = sg * SEG, end = min(inum, a + SEG);
   int nt = 0, cur_e = 0, cur_a = 0;
   int base = FILL ? seg_base[sg] : 0;
@@ -397,12 +398,12 @@ static constexpr int PACK_CH = 32768;          // atoms per LDS chunk of k_pack_
 // walkers of a chunk then hit different banks), the walks, the tiles' first edges and the tile bounds come from there.
 __device__ __forceinline__ int pack_lds_pos(int k) { return k + (k >> 7); }
 static __global__ void __launch_bounds__(PACK_SMALL_SEGS) k_pack_small(int inum, const int *eoff, int nseg, int *tile_a0, int *tile_e0, int *ntiles, int tile_slots, int maxa,
-                                                                       const int *ilist, const int *mtype, int2 *centre, const int *maxdeg = nullptr) {
+                                                                       const int *ilist, const int *mtype, int2 *centre, const int *maxdeg = nullptr, int maxa_wide = 12) {
   __shared__ int cnt[PACK_SMALL_SEGS];
   __shared__ int se[PACK_CH + PACK_CH / SEG + 2];
   __shared__ int total;
   const int sg = threadIdx.x;
-  pack_shape(maxdeg, tile_slots, maxa);
+  pack_shape(maxdeg, tile_slots, maxa, maxa_wide);
   // per-centre {atom, type} records: independent of everything below, their two dependent loads run under the first chunk's staging
   // (eight independent load chains in flight per thread: one at a time, a 125 k-atom call spent 0.17 ms in this loop alone)
   for (int i0 = sg; i0 < inum; i0 += 8 * PACK_SMALL_SEGS) {
@@ -495,9 +496,10 @@ static long long fused_nedges_estimate(const Model &m) {
 }
 // Packs the tiles unless the edge build already did at this shape (edges.hip; can_prepack: the caller's shape admits it) -- consecutive centres into
 // tiles of <= slots edges and <= maxa centres (k_pack_tiles), per-centre {atom, type}, per-edge packed types, first edge of every tile -- and points
-// A's edge, tile and output fields at the result.  maxdeg_sel (k_fused): device word of the largest degree, from which the packing kernels widen the shape themselves.
+// A's edge, tile and output fields at the result.  maxdeg_sel (k_fused, k_fused_lx): device word of the largest degree, from which the packing kernels widen the shape
+// themselves, to 128 slots and maxa_wide centres.
 template <class Args>
-static void fused_tile_args(Model &m, TileBufs &tb, const ComputeArgs &a, Args &A, int slots, int maxa, const int *maxdeg_sel = nullptr, bool can_prepack = true) {
+static void fused_tile_args(Model &m, TileBufs &tb, const ComputeArgs &a, Args &A, int slots, int maxa, const int *maxdeg_sel = nullptr, bool can_prepack = true, int maxa_wide = 12) {
   const bool pre = can_prepack && m.tiles_packed && m.pack_slots == slots && m.pack_maxa == maxa;
   hipStream_t s = a.stream;
   const int inum = m.inum;
@@ -513,11 +515,11 @@ static void fused_tile_args(Model &m, TileBufs &tb, const ComputeArgs &a, Args &
     const bool small = inum <= PACK_SMALL_ATOMS;
     if (small)
       hipLaunchKernelGGL(k_pack_small, dim3(1), dim3(PACK_SMALL_SEGS), 0, s, inum, m.b_eoff.as<int>(), nseg, tb.tile_a0.as<int>(), tb.tile_e0.as<int>(), tb.ntiles.as<int>(), slots, maxa,
-                         m.d_ilist, a.mtype, tb.centre.as<int2>(), maxdeg_sel);
+                         m.d_ilist, a.mtype, tb.centre.as<int2>(), maxdeg_sel, maxa_wide);
     else {
-      hipLaunchKernelGGL(k_pack_tiles<false>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, tb.seg_count.as<int>(), (const int *)nullptr, (int *)nullptr, slots, maxa, maxdeg_sel);
+      hipLaunchKernelGGL(k_pack_tiles<false>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, tb.seg_count.as<int>(), (const int *)nullptr, (int *)nullptr, slots, maxa, maxdeg_sel, maxa_wide);
       AHIP_CHECK(prim_exclusive_scan_i32(m.prim, tb.seg_count.as<int>(), tb.seg_base.as<int>(), nseg, s));
-      hipLaunchKernelGGL(k_pack_tiles<true>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, (int *)nullptr, tb.seg_base.as<int>(), tb.tile_a0.as<int>(), slots, maxa, maxdeg_sel);
+      hipLaunchKernelGGL(k_pack_tiles<true>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, (int *)nullptr, tb.seg_base.as<int>(), tb.tile_a0.as<int>(), slots, maxa, maxdeg_sel, maxa_wide);
       hipLaunchKernelGGL(k_pack_finish, dim3(1), dim3(1), 0, s, inum, nseg, tb.seg_base.as<int>(), tb.tile_a0.as<int>(), tb.ntiles.as<int>());
       hipLaunchKernelGGL(k_centre_info, dim3((inum + 255) / 256), dim3(256), 0, s, inum, m.d_ilist, a.mtype, tb.centre.as<int2>());
     }

@@ -32,12 +32,15 @@
 
 namespace ahip {
 
-// The shape of k_fused_lx: l_max = 2, 2 16-feature tiles (32 tensor features), 4 waves
-struct ShapeX {
-  static constexpr int L = 2, UT = 2, NW = 4;
+// The shape of k_fused_lx: l_max = 2, 2 16-feature tiles (32 tensor features); NW = 4 waves (one per SIMD, 64 edge slots) or 8 (two per SIMD, 128 slots:
+// centres with 65..128 edges, option wide_tile=auto)
+template <int NW_> struct ShapeX {
+  static_assert(NW_ == 4 || NW_ == 8, "4- or 8-wave tiles");
+  static constexpr int L = 2, UT = 2, NW = NW_;
   static constexpr int D = (L + 1) * (L + 1), NLP = L + 1, U = 16 * UT, EW = NLP * UT;   // EW: 16-feature tiles of an (l, u) weight vector
   static constexpr int SLOTS = 16 * NW;
-  static constexpr int MAXA = 4;                        // centre atoms per tile (LDS budget of the environment rows)
+  static constexpr int MAXA = lx_tile_maxa(NW == 8);    // centre atoms per tile: 4 / 8 (LDS budget of the environment rows; fused_shapes.h)
+  static_assert(SLOTS == lx_tile_slots(NW == 8), "fused_shapes.h: the tile shapes the dispatch asks the packing for");
   static constexpr int STG_LD = D * 16 + 4;             // one K-tile of a slot: [lm][16] + pad (16-byte rows, conflict-free b128 writes)
   static constexpr int ENVA = D * U + 4;                // environment row of one centre: [lm][u] + pad
   static constexpr int NP = CgX<L>::NP;
@@ -53,10 +56,13 @@ struct ShapeX {
   __host__ __device__ static constexpr int R_TOTAL(int NL, int MD) { return R::R_TOTAL(NL, MD); }
 };
 
-struct __attribute__((aligned(16))) LdsX {
-  using S = ShapeX;
+template <int NW_> struct __attribute__((aligned(16))) LdsX {
+  using S = ShapeX<NW_>;
   static constexpr int NW = S::NW;
-  float stage[2][S::SLOTS * S::STG_LD];
+  // 4 waves: double-buffered (one barrier per K-tile).  8 waves: two buffers of 128 slots alone would be 151 KB, so ONE, and a second barrier per K-tile
+  // (every wave has read K-tile t before t + 1 is written) that the other wave of the SIMD covers
+  static constexpr int NSTG = NW == 4 ? 2 : 1;
+  float stage[NSTG][S::SLOTS * S::STG_LD];
   float env[LX_MAXNL][S::MAXA * S::ENVA];
   float denv[S::MAXA * S::ENVA];
   float tp[LX_MAXNL][S::NP * S::U];          // tensor-product path weights [layer][path][u]
@@ -70,18 +76,20 @@ struct __attribute__((aligned(16))) LdsX {
   // Round 6: rows of the LAST layer that never travel to memory.  One workgroup per CU leaves ~58 KB of LDS unused: per wave NLROW register-image rows hold the last
   // layer's omega rows (l >= 1) and the first rows of its input tensor; its 8 latent-MLP rows go to the wave's own slots of stage[0], idle between that layer's
   // environment sum and its backward tensor product (as in k_fused: EpiSiluSaveDL / EpiSiluSaveZL).  22 of the 118 rows a wave-tile of the reference YAML's shape saves.
-  static constexpr int NLROW = 14;
+  // 8 waves (one workgroup per CU again, 128-slot stage, 8 centres): room for the last layer's 4 omega rows only -- its input tensor rows all go to the wave's scratch
+  // like a non-last layer's (NVL = 0 in the kernel).  stage 74 KB + env / denv 36.5 KB + tp 5.6 KB + rowsl 32 KB + tables = 153 392 B
+  static constexpr int NLROW = NW == 4 ? 14 : 4;
   float rowsl[NW][NLROW * ROW];
 };
-static_assert(sizeof(LdsX) <= 160 * 1024, "LDS budget of one CU");
+static_assert(sizeof(LdsX<4>) <= 160 * 1024 && sizeof(LdsX<8>) <= 160 * 1024, "LDS budget of one CU");
 
 
 // Per-centre sum of one staged K-tile: env[a][lm][16 t + f] = scale * sum_{slots of a} stage[slot][lm][f].
 // Work item = (centre, 4-feature column); its LPI adjacent lanes take every LPI-th slot with 16-byte LDS reads (all of a lane's reads
 // are in flight together) and combine with log2(LPI) cross-lane adds -- a fixed order, so the sums are reproducible.
+template <int NW>
 __device__ __forceinline__ void reduce_stage_x(const float *stg, const int *aoff, float *dst, int na, float scale, int t, int uwave) {
-  using S = ShapeX;
-  constexpr int NW = S::NW;
+  using S = ShapeX<NW>;
   constexpr int LPI = 4;                    // lanes per work item: 36 columns x 4 lanes = one round for a tile that holds one centre
   constexpr int NC = S::D * 4, PER_ROUND = NW * 64 / LPI, NRD = S::SLOTS / LPI;
   // lane -> (item, part): part = lane / 16, item = 16 * wave + lane % 16.  The 16 lanes of one 16-byte LDS read phase then hold 16
@@ -96,16 +104,33 @@ __device__ __forceinline__ void reduce_stage_x(const float *stg, const int *aoff
     const int s0 = aoff[a] + p, s1 = live ? aoff[a + 1] : 0;
     // all reads are issued before the first is used: addresses past the centre's last slot are clamped to slot 0 of the stage
     // (always mapped) and their values discarded -- a conditional read per slot costs one LDS round trip each
-    f32x4 v[NRD];
-#pragma unroll
-    for (int k = 0; k < NRD; ++k) {
-      const int sl = s0 + LPI * k;
-      v[k] = *(const f32x4 *)(stg + (sl < s1 ? sl : 0) * S::STG_LD + 4 * c);
-    }
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (NW == 4) {
+      f32x4 v[NRD];
 #pragma unroll
-    for (int k = 0; k < NRD; ++k)
-      if ((s0 + LPI * k) < s1) acc += v[k];
+      for (int k = 0; k < NRD; ++k) {
+        const int sl = s0 + LPI * k;
+        v[k] = *(const f32x4 *)(stg + (sl < s1 ? sl : 0) * S::STG_LD + 4 * c);
+      }
+#pragma unroll
+      for (int k = 0; k < NRD; ++k)
+        if ((s0 + LPI * k) < s1) acc += v[k];
+    } else {
+      // 8 waves: 32 reads per lane, in batches of 8 -- the edge tensor sits in ordinary registers there and 128 more would all be spilled
+      constexpr int NB = 8;
+#pragma unroll
+      for (int k0 = 0; k0 < NRD; k0 += NB) {
+        f32x4 v[NB];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+          const int sl = s0 + LPI * (k0 + k);
+          v[k] = *(const f32x4 *)(stg + (sl < s1 ? sl : 0) * S::STG_LD + 4 * c);
+        }
+#pragma unroll
+        for (int k = 0; k < NB; ++k)
+          if ((s0 + LPI * (k0 + k)) < s1) acc += v[k];
+      }
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float v1 = acc[r];
@@ -153,10 +178,14 @@ enum { PX_GEOM = 0, PX_EMB, PX_ENV, PX_TP, PX_LAT, PX_MIX, PX_OUT, PX_BLAT, PX_B
 // VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
 // MD: hidden layers of the latent MLP (allegro_mlp_hidden_layers_depth; 2 in the reference test YAML).  1 and 3 exist on the f16x2 arithmetic only, as in k_fused;
 // every MD-dependent piece below is `if constexpr`, and the MD = 2 instances are what they were before the parameter existed.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 only, built in fused_lx_r.o).
-template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1>
-__global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) {
-  constexpr int L = ShapeX::L, UT = ShapeX::UT, NW = ShapeX::NW;
-  using S = ShapeX;
+// NW: waves per workgroup = 16-slot groups of a tile.  4: one wave per SIMD, the edge tensor parked in AGPRs.  8: two waves per SIMD, 256 registers each, no park
+// (compiled with AHIP_NO_ACC_PARK in an object of its own: fused_lx_w.o), one staging buffer; (MD, RD) = (2, 1), not profiled.
+template <int NW, int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1>
+__global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
+  using S = ShapeX<NW>;
+  using LdsT = LdsX<NW>;
+  constexpr int L = S::L, UT = S::UT;
+  static_assert(NW == 4 || (MD == 2 && RD == 1 && !PROF), "8-wave tiles: MLP depth 2, read-out depth 1, not profiled");
   constexpr int NTHREADS = NW * 64, D = S::D, U = S::U, EW = S::EW, MAXA = S::MAXA, STG_LD = S::STG_LD, ENVA = S::ENVA, NP = S::NP;
   constexpr bool SAVEZ = AR == 3;          // f16x2: raw pre-activation rows of the last hidden layer instead of silu' rows, no u rows (see fused.hip)
   static_assert(MD >= 1 && MD <= 3 && (MD == 2 || AR == 3), "latent MLP depth 1 / 3: f16x2 instances only");
@@ -166,9 +195,9 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
   // A wave's slots hold 9 images; depth 3 would need 12, so the silu' rows of its hidden layer 1 go to the per-wave scratch like a non-last layer's.
   constexpr int ZIMG = MD == 1 ? 0 : 4;
   // last-layer rows in LDS (LdsX::rowsl, stage[0] images): LDS rows [0, NOML) = omega l >= 1, [NOML, NLROW) = the first NVL rows of the input tensor
-  constexpr int NLROW = LdsX::NLROW, NOML = L * UT, NVL = (NLROW - NOML) < D * UT ? (NLROW - NOML) : D * UT;
+  constexpr int NLROW = LdsT::NLROW, NSTG = LdsT::NSTG, NOML = L * UT, NVL = (NLROW - NOML) < D * UT ? (NLROW - NOML) : D * UT;
   static_assert(NOML <= NLROW, "omega rows of the last layer fit the LDS rows");
-  __shared__ LdsX lds;
+  __shared__ LdsT lds;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
   const int v16 = lane * 16;
@@ -259,7 +288,7 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
     const int envoff = aloc * ENVA + 4 * g;      // + kk * MAXA*ENVA (layer) + lm * U + 16 t
     // this lane's staging row in buffer b, formed where it is used from the hardware lane counter (round 6): as a value computed at the top of the tile it
     // lived in scratch once the last layer's rows moved into the stage, and its reload in front of every staging write drained the in-order load queue
-    auto STQ = [&](int b) { const int ln = fresh_lane(); return lds.stage[b] + (uwave * 16 + (ln & 15)) * STG_LD + 4 * (ln >> 4); };
+    auto STQ = [&](int b) { const int ln = fresh_lane(); return lds.stage[NSTG == 2 ? b : 0] + (uwave * 16 + (ln & 15)) * STG_LD + 4 * (ln >> 4); };
     PHASEX(PX_GEOM);
 
     // ---------------- two-body embedding x0(d; type pair) from the spline table ----------------
@@ -313,8 +342,9 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
 #pragma unroll
           for (int lm = 0; lm < D; ++lm) *(f32x4 *)(sp + lm * 16) = lm == 0 ? om[t] : om[l_of_lm(lm) * UT + t] * Y[lm];
           __syncthreads();
-          reduce_stage_x(lds.stage[t & 1], aoffp, envk, na, A.cenv, t, uwave);
+          reduce_stage_x<NW>(lds.stage[NSTG == 2 ? (t & 1) : 0], aoffp, envk, na, A.cenv, t, uwave);
           __builtin_amdgcn_sched_barrier(0);
+          if constexpr (NSTG == 1) { if (t + 1 < UT) __syncthreads(); }          // one staging buffer: every wave has read K-tile t before t + 1 is written
         }
 #endif
         __syncthreads();
@@ -627,8 +657,9 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
             } else load_rows<L * UT>(SB, RL + S::O_OM + UT, omall, v16);
           }
           __syncthreads();
-          reduce_stage_x(lds.stage[t & 1], aoffp, lds.denv, na, A.cenv, t, uwave);
+          reduce_stage_x<NW>(lds.stage[NSTG == 2 ? (t & 1) : 0], aoffp, lds.denv, na, A.cenv, t, uwave);
           __builtin_amdgcn_sched_barrier(0);
+          if constexpr (NSTG == 1) { if (t + 1 < UT) __syncthreads(); }
         }
         __syncthreads();
       PHASEX(PX_BTP);
@@ -783,16 +814,27 @@ __global__ void __launch_bounds__(ShapeX::NW * 64, 1) k_fused_lx(FusedLxArgs A) 
 }
 
 // ---------------------------------------------------------------------------- host side
-// This file is compiled twice (Makefile): AHIP_LX_PART 0 = the host side and the read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone (fused_lx_r.o)
+// This file is compiled three times (Makefile): AHIP_LX_PART 0 = the host side and the 4-wave read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone
+// (fused_lx_r.o), 2 = the 8-wave instances alone, with AHIP_NO_ACC_PARK (fused_lx_w.o)
 #ifndef AHIP_LX_PART
 #define AHIP_LX_PART 0
 #endif
 void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
+void fusedlx_launch_w8(int nl, int ar, int var, int grid, hipStream_t s, const FusedLxArgs &A);
 #if AHIP_LX_PART == 1
 void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // f16x2 only, plain and per-atom virial, not profiled
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
-    hipLaunchKernelGGL((k_fused_lx<nl, false, 3, v == VAR_VA, md, 2>), dim3(grid), dim3(ShapeX::NW * 64), 0, s, A);
+    hipLaunchKernelGGL((k_fused_lx<4, nl, false, 3, v == VAR_VA, md, 2>), dim3(grid), dim3(4 * 64), 0, s, A);
   }, nl, var, md);
+}
+#elif AHIP_LX_PART == 2
+#ifndef AHIP_NO_ACC_PARK
+#error "the 8-wave instances have 256 registers per wave: no AGPR park (build fused_lx_w.o with -DAHIP_NO_ACC_PARK)"
+#endif
+void fusedlx_launch_w8(int nl, int ar, int var, int grid, hipStream_t s, const FusedLxArgs &A) {      // f32 and f16x2, plain and per-atom virial, (MD, RD) = (2, 1), not profiled
+  dispatch<Choices<1, 2, 3>, Choices<3, 0>, Choices<VAR_VA, VAR_PLAIN>>([&](auto nl, auto ar, auto v) {
+    hipLaunchKernelGGL((k_fused_lx<8, nl, false, ar, v == VAR_VA>), dim3(grid), dim3(8 * 64), 0, s, A);
+  }, nl, ar, var);
 }
 #else
 
@@ -802,7 +844,7 @@ static_assert(LX_MAXNL == 3, "fused_shapes.h: 1..3 layers");
 
 // k_fused_lx's weight stream, in the order one tile consumes it: whole-matrix fragments (see k_fused_lx)
 static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, Arith arith) {
-  using S = ShapeX;
+  using S = ShapeX<4>;          // (the stream does not depend on the tile shape)
   constexpr int L = S::L, U = S::U, D = S::D;
   const int NL = h.num_layers, MD = h.mlp_depth;      // latent MLP: lat.w0 ([x, scalars] -> 64), lat.w1 .. lat.w{MD-1} (64 -> 64), output linear lat.w{MD}
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
@@ -861,17 +903,27 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
 }
 
 bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
-  if (!lx_list_fits(m, why)) return false;
-  FusedLxState &st = lx_prepare<ShapeX>(m, m.fusedlx_state, nullptr, false, lx_stream);
+  const int max_slots = lx_max_tile_slots(m, FusedFamily::lx32);
+  if (!lx_list_fits(m, why, max_slots)) return false;
+  FusedLxState &st = lx_prepare<ShapeX<4>>(m, m.fusedlx_state, nullptr, false, lx_stream, max_slots > LX_TILE_SLOTS ? 8 : 4);
   static_assert(PX_N == LX_NPHASE, "profile phases");
   if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
-  lx_run<ShapeX>(m, a, st, "fused_lx", [&](const FusedLxArgs &A, int grid, int var) {
+  // Tile shape (4 waves / 64 slots or 8 waves / 128 slots, option wide_tile=auto) from the largest degree of THIS list, as k_fused does (fused.hip: fused_run): on the
+  // host where it is known or bounded by the list's rows, else both shapes are launched and the device word decides (nw = 0)
+  int nw = 4;
+  if (max_slots > LX_TILE_SLOTS) {
+    if (!fused_has_wide_tile(FusedFamily::lx32, st.arith, st.md, st.rd)) throw StateError("wide_tile: the prepared instance has no 8-wave shape");      // (lx_max_tile_slots asked the same rule)
+    if (!m.counts_pending) nw = m.last_max_deg <= LX_TILE_SLOTS ? 4 : 8;
+    else nw = (m.max_list_row >= 0 && m.max_list_row <= LX_TILE_SLOTS) ? 4 : 0;
+  }
+  lx_run<ShapeX<4>, ShapeX<8>>(m, a, st, "fused_lx", [&](const FusedLxArgs &A, int grid, int var, int shape) {
+    if (shape == 8) { fusedlx_launch_w8(A.NL, st.arith, var, grid, a.stream, A); return; }      // fused_lx_w.o
     if (st.rd == 2) { fusedlx_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_r.o
     dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
       if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)
-        hipLaunchKernelGGL((k_fused_lx<nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(ShapeX::NW * 64), 0, a.stream, A);
+        hipLaunchKernelGGL((k_fused_lx<4, nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(4 * 64), 0, a.stream, A);
     }, A.NL, st.arith, var, st.md);
-  });
+  }, nw);
   return true;
 }
 

@@ -951,7 +951,7 @@ bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
   FusedLxState &st = lx_prepare<ShapeP>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream);     // path weights x the path's base |c| (tp_g)
   static_assert(PP_N == LX_NPHASE, "profile phases");
   if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
-  lx_run<ShapeP>(m, a, st, "fused_lx2", [&](const FusedLxArgs &A, int grid, int var) {
+  lx_run<ShapeP>(m, a, st, "fused_lx2", [&](const FusedLxArgs &A, int grid, int var, int) {
     if (st.rd == 2) { fusedlx2_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_r.o
     dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
       if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)

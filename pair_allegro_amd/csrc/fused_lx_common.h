@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace ahip {
@@ -84,15 +85,17 @@ struct FusedLxState {
   FusedLxArgs args;
   bool ready = false, prof_on = false;
   int ncu = 256;
+  int scratch_waves = 0;       // waves per workgroup the per-wave scratch holds
   int md = 2, rd = 1;          // hidden layers of the latent MLP and of the read-out MLP (template parameters MD, RD of the kernels)
   Arith arith = AR_F32;        // AR_F32 or AR_F16X2 (arith_policy.h: resolve_arith, wide)
 };
 
 // Prepares a wide kernel's state once (shape S).  `stream(w, A, h, arith)` appends the kernel's own weight-stream layout, sets A.o_stream (and
 // o_stream_hi) and returns its float16 range findings (engine.h: H_RANGE_*).  The rest is common (fused_common.h: fused_prepare_tail; cbase: the grouped
-// tensor product of fused_lx2.hip; tiny: the range verdict takes the model-wide tiny-linear finding too, fused_lx2.hip), then the per-wave scratch.
+// tensor product of fused_lx2.hip; tiny: the range verdict takes the model-wide tiny-linear finding too, fused_lx2.hip), then the per-wave scratch
+// (scratch_waves: waves per workgroup it is reserved for -- S::NW, or 8 where k_fused_lx may run its 8-wave shape; ahip_set_option drops the state when wide_tile changes).
 template <class S, class Stream>
-static FusedLxState &lx_prepare(Model &m, FusedLxState *&slot, const double *cbase, bool tiny, Stream stream) {
+static FusedLxState &lx_prepare(Model &m, FusedLxState *&slot, const double *cbase, bool tiny, Stream stream, int scratch_waves = S::NW) {
   if (!slot) slot = new FusedLxState();
   FusedLxState &st = *slot;
   if (st.ready) return st;
@@ -107,9 +110,10 @@ static FusedLxState &lx_prepare(Model &m, FusedLxState *&slot, const double *cba
   st.ncu = fused_prepare_tail(m, h, w, A, st.wbuf, true, S::NP, S::U, cbase, st.arith, h_flags);
   st.md = h.mlp_depth; st.rd = h.readout_depth;
   A.wave_scratch = (long long)S::R_TOTAL(NL, st.md) * ROW;
-  st.scratch.reserve((size_t)st.ncu * S::NW * A.wave_scratch * sizeof(float));
+  st.scratch.reserve((size_t)st.ncu * scratch_waves * A.wave_scratch * sizeof(float));
+  st.scratch_waves = scratch_waves;
   A.scratch = st.scratch.as<float>();
-  st.tiles.partial.reserve((size_t)st.ncu * 7 * sizeof(double));
+  st.tiles.partial.reserve((size_t)st.ncu * 2 * 7 * sizeof(double));      // (two shapes launched side by side: a block of rows each, lx_run)
   st.tiles.ntiles.reserve(64);
   st.prof.reserve(64 * sizeof(long long));
   const char *pe = std::getenv("AHIP_FUSED_PROF");
@@ -118,47 +122,75 @@ static FusedLxState &lx_prepare(Model &m, FusedLxState *&slot, const double *cba
   return st;
 }
 
-// What both wide kernels require of the edge list before anything is enqueued.  (Counts still in flight = single-pass edge build with
-// heavy_thresh = LX_TILE_SLOTS: every centre with more edges is listed, gets a tile of its own that the kernel skips, and is evaluated by
-// heavy_generic after the kernel has been enqueued -- the host reads the counts only then, VERDICT r03 #2.)
-static bool lx_list_fits(const Model &m, std::string *why) {
-  if (!m.counts_pending && m.last_max_deg > LX_TILE_SLOTS && (m.heavy_thresh != LX_TILE_SLOTS || (long long)m.nheavy * 8 > m.inum)) {
-    // centres with more than 64 edges are listed by the edge build and evaluated by the layer-at-a-time kernels; when the edge
+// What both wide kernels require of the edge list before anything is enqueued; max_slots: edge slots of the largest tile shape the kernel has for this model
+// (engine.h: lx_max_tile_slots; 64, or 128 for k_fused_lx under wide_tile=auto).  (Counts still in flight = single-pass edge build with heavy_thresh = max_slots:
+// every centre with more edges is listed, gets a tile of its own that the kernel skips, and is evaluated by heavy_generic after the kernel has been enqueued --
+// the host reads the counts only then, VERDICT r03 #2.)
+static bool lx_list_fits(const Model &m, std::string *why, int max_slots = LX_TILE_SLOTS) {
+  if (!m.counts_pending && m.last_max_deg > max_slots && (m.heavy_thresh != max_slots || (long long)m.nheavy * 8 > m.inum)) {
+    // centres with more edges than the largest tile are listed by the edge build and evaluated by the layer-at-a-time kernels; when the edge
     // build did not list them (two-pass fallback) or they are not a small minority, the whole system goes that way
-    if (why) *why = "an atom has " + std::to_string(m.last_max_deg) + " edges (> " + std::to_string(LX_TILE_SLOTS) + " per tile of the wide fused kernel)";
+    if (why) *why = "an atom has " + std::to_string(m.last_max_deg) + " edges (> " + std::to_string(max_slots) + " per tile of the wide fused kernel" +
+                    (max_slots == LX_TILE_SLOTS ? "" : " at its 8-wave shape") + ")";
     return false;
   }
   if (m.edges_T_size != 4) { if (why) *why = "edge vectors are not float32"; return false; }
   return true;
 }
 
+// Both shapes of k_fused_lx launched for one list (lx_run, nw == 0): the tile count goes to the shape the packing kernels chose from the largest degree, the other sees
+// none; both tile counters start at zero.  ntl: the packing's {tiles, counter} words followed by the two per-shape pairs (TileBufs::ntiles holds 16 words).
+static __global__ void k_lx_shape_select(int *ntl, const int *maxdeg) {
+  const int n = ntl[0];
+  const bool wide = *maxdeg > 64;
+  ntl[2] = wide ? 0 : n; ntl[3] = 0;
+  ntl[4] = wide ? n : 0; ntl[5] = 0;
+}
+
 // phases of the profiled instances (AHIP_FUSED_PROF=1, 3 layers, MLP depth 2, read-out depth 1): the kernels' PX_* / PP_* enums
 static constexpr int LX_NPHASE = 13;
-// One evaluation on a prepared wide kernel (shape S): tile packing, arguments, `launch(A, grid, variant)` (the file's instance dispatch; variant:
-// fused_common.h, VAR_*), the energy / virial sums, and the per-phase profile printed as "[ahip <name> prof]" (tools/abprof.sh reads it)
-template <class S, class Launch>
-static void lx_run(Model &m, const ComputeArgs &a, FusedLxState &st, const char *name, Launch launch) {
+// One evaluation on a prepared wide kernel (shape S): tile packing, arguments, `launch(A, grid, variant, waves)` (the file's instance dispatch; variant:
+// fused_common.h, VAR_*), the energy / virial sums, and the per-phase profile printed as "[ahip <name> prof]" (tools/abprof.sh reads it).
+// S8 / nw (k_fused_lx only): the kernel's second, 8-wave shape and which one runs -- 4: S, 8: S8, 0: both are launched, the stand-alone packing kernels widen the
+// tiles from the device word of the list's largest degree and k_lx_shape_select hands the tile count to the shape they were packed for and 0 to the other, which
+// returns at once.  Each shape has its own tile counter and its own rows of `partial`, so the kernels' device code knows nothing of the choice.
+template <class S, class S8 = S, class Launch>
+static void lx_run(Model &m, const ComputeArgs &a, FusedLxState &st, const char *name, Launch launch, int nw = 4) {
   static_assert(S::SLOTS == LX_TILE_SLOTS && S::MAXA == LX_TILE_MAXA, "allegro_hip.hip requests this tile shape from the edge build");
+  static_assert(std::is_same<S, S8>::value || (S8::SLOTS == lx_tile_slots(true) && S8::MAXA == lx_tile_maxa(true)), "fused_shapes.h: the 8-wave tile shape");
   m.arith.last = st.arith;
   hipStream_t s = a.stream;
-  const int grid = std::max(1, st.ncu - (m.reserve_wgs + 1) / 2);      // see fused.hip: slots left free for the exchange kernels
+  const int grid = std::max(1, st.ncu - (m.reserve_wgs + 1) / 2);      // see fused.hip: slots left free for the exchange kernels (one workgroup per CU at either shape)
   FusedLxArgs A = st.args;
-  A.wg_scratch = S::NW * A.wave_scratch;
-  fused_tile_args(m, st.tiles, a, A, S::SLOTS, S::MAXA);
-  // claims of TCHUNK tiles amortise the counter's round trip; with few tiles per workgroup the last claim decides the makespan
-  // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
-  A.tchunk = (fused_nedges_estimate(m) / S::SLOTS > (long long)grid * 256) ? TCHUNK : 1;
-  const bool prof = st.prof_on && A.NL == 3 && st.md == 2 && st.rd == 1;
+  if (st.scratch_waves < (nw == 4 ? S::NW : S8::NW)) throw StateError("wide fused kernel: the per-wave scratch was not prepared for this tile shape");      // (lx_prepare sizes it)
+  const int *maxdeg_sel = nw == 0 ? m.d_maxdeg : nullptr;
+  const int slots = nw == 8 ? S8::SLOTS : S::SLOTS, maxa = nw == 8 ? S8::MAXA : S::MAXA;      // nw == 0: the packing kernels widen them themselves
+  fused_tile_args(m, st.tiles, a, A, slots, maxa, maxdeg_sel, nw == 4, S8::MAXA);      // (the edge build packs 4-wave tiles only)
+  int *const ntl = const_cast<int *>(A.ntiles);      // [0] tiles, [1] counter (fused_tile_args); nw == 0: [2], [3] the same for the 4-wave shape, [4], [5] for the 8-wave shape
+  if (nw == 0) hipLaunchKernelGGL(k_lx_shape_select, dim3(1), dim3(1), 0, s, ntl, maxdeg_sel);
+  const bool prof = st.prof_on && A.NL == 3 && st.md == 2 && st.rd == 1 && nw == 4;
   {
     StageTimer tm(m, "model_fused", s);
     if (prof && !A.vatom) {
       AHIP_CHECK(hipMemsetAsync(st.prof.p, 0, 64 * sizeof(long long), s));
       A.prof = st.prof.as<long long>();
     }
-    launch(A, grid, fused_variant(A.vatom, prof));
+    for (int shape = 4; shape <= 8; shape += 4) {
+      if (nw != 0 && nw != shape) continue;
+      if (nw == 0) {
+        const int k = shape == 8 ? 1 : 0;
+        A.ntiles = ntl + 2 + 2 * k; A.tile_counter = (unsigned int *)(ntl + 3 + 2 * k);
+        A.partial = st.tiles.partial.as<double>() + (size_t)k * 7 * grid;
+      }
+      A.wg_scratch = (shape == 8 ? S8::NW : S::NW) * A.wave_scratch;      // (S::NW: k_fused_lx2's 64-slot tile is 8 waves, 4 pairs)
+      // claims of TCHUNK tiles amortise the counter's round trip; with few tiles per workgroup the last claim decides the makespan
+      // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
+      A.tchunk = (fused_nedges_estimate(m) / (shape == 8 ? S8::SLOTS : S::SLOTS) > (long long)grid * 256) ? TCHUNK : 1;
+      launch(A, grid, fused_variant(A.vatom, prof), shape);
+    }
   }
   AHIP_CHECK(hipGetLastError());
-  AHIP_CHECK(prim_sum_columns_f64(m.prim, st.tiles.partial.as<double>(), grid, 7, a.engvir, s));
+  AHIP_CHECK(prim_sum_columns_f64(m.prim, st.tiles.partial.as<double>(), nw == 0 ? 2 * grid : grid, 7, a.engvir, s));
   if (prof) {
     std::vector<long long> hp(LX_NPHASE);
     AHIP_CHECK(hipMemcpyAsync(hp.data(), st.prof.p, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, s));

@@ -12,6 +12,10 @@
 // Instances by (MD, RD) = (latent MLP depth, read-out depth): (2, 1) on every arithmetic the family has; every other pair of MD in 1..3, RD in 1..2 on the
 // f16x2 arithmetic only (k_fused: with the tabulated two-body embedding).  Read-out depth 0 (a linear read-out) would need a different fold of the last
 // layer's output linear into the read-out and has no instance.
+//
+// Tile shapes of the wide kernels (edge slots, centres per tile); a centre with more edges than the model's largest shape holds is "heavy":
+//   lx32, lx64   4 waves (lx64: 4 wave pairs)   64 slots, 4 centres    every instance
+//   lx32         8 waves                       128 slots, 8 centres    (MD, RD) = (2, 1) on f32 and f16x2, behind option wide_tile=auto (fused_has_wide_tile)
 #pragma once
 #include <string>
 
@@ -59,6 +63,16 @@ inline bool fused_instance_exists(FusedFamily f, Arith ar, bool tb_table, int MD
   if (MD == 2 && RD == 1) return fused_is_wide(f) ? (ar == AR_F32 || ar == AR_F16X2) : (ar != AR_F16X2 || tb_table);
   return ar == AR_F16X2 && (fused_is_wide(f) || tb_table);
 }
+
+// The second tile shape of k_fused_lx (8 waves, 128 edge slots: a centre with 65..128 edges stays on the fused kernel) exists for this family, arithmetic and
+// these depths.  Option wide_tile=auto uses it where this says yes and is the 64-slot shape everywhere else.
+inline bool fused_has_wide_tile(FusedFamily f, Arith ar, int MD, int RD) {
+  return f == FusedFamily::lx32 && (ar == AR_F32 || ar == AR_F16X2) && MD == 2 && RD == 1;
+}
+// edge slots and centres of a wide kernel's tile: the 4-wave shape of every instance, or the 8-wave shape of k_fused_lx (8 centres: 16 slots per centre as in the
+// 4-wave shape -- lists that need it are dense, two 54-edge centres or one of 78 fill a tile -- and the environment rows of 8 centres leave its LDS at 153 392 B of 160 KB)
+inline constexpr int lx_tile_slots(bool wide128) { return wide128 ? 128 : 64; }
+inline constexpr int lx_tile_maxa(bool wide128) { return wide128 ? 8 : 4; }
 
 inline constexpr const char *FUSED_WHY_DEPTHS =
     "fused kernels need MLP depth 1..3 and read-out depth 1..2 (a linear read-out, depth 0, needs a different fold of the last layer and has no instance)";
