@@ -140,6 +140,29 @@ int ahip_neigh_update_dev_table(ahip_model *m, int inum, int nall, const int *il
 int ahip_map_types_dev(ahip_model *m, int n, const int *type_dev, int ntypes, const int *type_mapper, int *mtype_dev,
                        void *stream);
 
+/* Active types: the model types a simulation can produce.  The reference maps every LAMMPS type to one model type by name
+ * (pair_nequip_allegro.cpp:274-294) and evaluates a model of tens of types like any other, however few of them `pair_coeff * * file A B C`
+ * names.  Here the fused kernels hold at most 16 types (4-bit packed edge types), but a type enters them only as a row of the first two-body
+ * linear, as scale / shift and as a row and column of the cutoff matrix: a fused evaluation therefore runs on the model restricted to its
+ * active types (compact slots in ascending model-type order), and a model qualifies when at most 16 of its types are ACTIVE, whatever their
+ * total (up to 255; beyond that, as with more than 16 active types, the layer-at-a-time kernels run and option path=fused says why).
+ * The layer-at-a-time kernels, ahip_model_meta and the registered outputs always see the model as loaded.
+ *   Automatic rule (no model that the fused kernels already served changes its behaviour): a model of MORE than 16 types takes the set from the
+ *   type mapping -- ahip_compute from its type_mapper argument (entries >= 0), device-resident callers from the mapper last given to
+ *   ahip_map_types_dev.  A model of at most 16 types runs whole.
+ *   ahip_set_active_types names the set explicitly for any model (n entries, duplicates allowed, any order; a value outside the model's types
+ *   is AHIP_ERR_ARG); n = 0 returns to the automatic rule.  It takes effect at the next evaluation; a change of the set rebuilds the prepared
+ *   weight streams and two-body tables there (once).  For a model of at most 16 types a subset shrinks the two-body table (0.5 MB per type
+ *   pair), which may well help a 10-type model that runs on two types; nobody has measured it, so it is not the default.
+ *   An atom whose type is not in the set makes that evaluation's forces invalid; every index stays in range.  It is reported as AHIP_ERR_ARG
+ *   naming the model type: by ahip_compute in the same call, before f is touched; to a device-resident caller by its next evaluation or
+ *   accessor (ahip_get_active_types, ahip_get_edges, ahip_get_timings), once the device has got that far.  Under the automatic rule it cannot
+ *   happen through ahip_compute / ahip_map_types_dev, which refuse unmapped types themselves.
+ *   ahip_get_active_types: the set the last evaluation ran with, ascending (model_types: room for num_types entries, or NULL for the count
+ *   alone); *n = 0: no subset. */
+int ahip_set_active_types(ahip_model *m, int n, const int *model_types);
+int ahip_get_active_types(ahip_model *m, int *n, int *model_types);
+
 /* One force evaluation = PairNequIPAllegro<false>::compute (pair_nequip_allegro.cpp:333-407).
  *   x            [nall][3] f64 positions, locals first then ghosts (atom->x)
  *   type         [nall] LAMMPS types, 1-based (atom->type)
@@ -290,7 +313,9 @@ int ahip_borders_local_dev(ahip_model *m, int nlocal, const double *x_dev, const
 
 /* v += dtf*f/m ; x += dt*v  style velocity-Verlet half steps on device arrays (NVE).
  *   mode 0: v += 0.5*dt*f*ftm2v/mass[type]; x += dt*v      (initial_integrate)
- *   mode 1: v += 0.5*dt*f*ftm2v/mass[type]                  (final_integrate)  */
+ *   mode 1: v += 0.5*dt*f*ftm2v/mass[type]                  (final_integrate)
+ * mass_by_mtype: HOST [num_types], indexed by (full) model type; any number of types (up to 16 travel in the kernel arguments, more in a small device
+ * table that is uploaded when its content changes, which synchronises `stream` once). */
 int ahip_nve_dev(ahip_model *m, int mode, int n, double *x_dev, double *v_dev, const double *f_dev,
                  const int *mtype_dev, const double *mass_by_mtype, double dt, double ftm2v, void *stream);
 /* mode 0 for the nlocal owned atoms AND f[0 .. nall) = 0 behind it (the array the next force evaluation accumulates into, pair_nequip_allegro.cpp:370-377

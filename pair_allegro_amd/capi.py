@@ -37,6 +37,7 @@ SYMBOLS = [
     "ahip_model_allow_tf32", "ahip_comm_unique_id", "ahip_comm_create_rccl", "ahip_comm_create_hosted", "ahip_comm_rccl_version", "ahip_comm_free", "ahip_comm_set_plan", "ahip_comm_set_plan_local",
     "ahip_comm_forward", "ahip_comm_reverse", "ahip_comm_allreduce", "ahip_comm_selftest", "ahip_fill_zero_dev", "ahip_borders_local_dev", "ahip_arith_note", "ahip_comm_borders", "ahip_comm_migrate",
     "ahip_debug_scan_i32", "ahip_debug_sum_columns_f64", "ahip_debug_max_i32", "ahip_debug_gemm_f32",
+    "ahip_set_active_types", "ahip_get_active_types",
 ]
 
 
@@ -104,6 +105,8 @@ class Library:
         L.ahip_reneighbor_flag_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         L.ahip_map_types_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
         L.ahip_last_list_size.restype = C.c_longlong
+        L.ahip_set_active_types.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.ahip_get_active_types.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.ahip_get_edges.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]
         L.ahip_debug_dump_edges.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.ahip_get_timings.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int)]
@@ -232,6 +235,19 @@ class Model:
 
     def set_option(self, key: str, value) -> None:
         self.L.check(self.L.lib.ahip_set_option(self.h, key.encode(), str(value).encode()))
+
+    # ---- active types (include/allegro_hip.h: ahip_set_active_types) -------------------------------
+    def set_active_types(self, model_types) -> None:
+        """Name the model types in use explicitly (any order, repeats allowed); an empty list returns to the automatic rule."""
+        t = np.ascontiguousarray(model_types, dtype=np.int32).reshape(-1)
+        self.L.check(self.L.lib.ahip_set_active_types(self.h, len(t), _p(t, C.c_int) if len(t) else None))
+
+    def get_active_types(self) -> list:
+        """The model types the last evaluation's fused side was restricted to, ascending; [] = no subset."""
+        n = C.c_int(0)
+        out = np.zeros(max(self.num_types, 1), dtype=np.int32)
+        self.L.check(self.L.lib.ahip_get_active_types(self.h, C.byref(n), _p(out, C.c_int)))
+        return [int(v) for v in out[:n.value]]
 
     # ---- neighbor lists ----------------------------------------------------------------------
     def neigh_update_csr(self, nall: int, ilist: np.ndarray, offsets: np.ndarray, neigh: np.ndarray,

@@ -145,7 +145,7 @@ namespace ahip {
 int *alarm_word(Model &m) {
   if (!m.h_alarm) {
     AHIP_CHECK(hipHostMalloc((void **)&m.h_alarm, 64, hipHostMallocMapped));
-    *m.h_alarm = 0;
+    m.h_alarm[0] = 0; m.h_alarm[1] = 0;          // [0] the f16x2 alarm, [1] the inactive-type word (engine.h: inactive_word)
   }
   int *d = nullptr;
   AHIP_CHECK(hipHostGetDevicePointer((void **)&d, m.h_alarm, 0));
@@ -155,8 +155,58 @@ bool alarm_take(Model &m) {
   if (m.h_alarm && *(volatile int *)m.h_alarm != 0) { *m.h_alarm = 0; return true; }
   return false;
 }
+int inactive_take(Model &m) {
+  if (!m.h_alarm) return 0;
+  const int v = ((volatile int *)m.h_alarm)[1];
+  if (v != 0) m.h_alarm[1] = 0;
+  return v;
+}
 // every fused kernel state of the model (weight streams are rebuilt on the next compute)
 static void free_fused_states(Model &m) { fused_free(m); fusedlx_free(m); }
+// the report of the inactive-type word (raised = 1 + model type): `when` says which evaluation
+static std::string inactive_message(const Model &m, int raised, const char *when) {
+  const int mt = raised - 1;
+  const std::string name = mt >= 0 && mt < (int)m.hm.type_names.size() ? " (" + m.hm.type_names[(size_t)mt] + ")" : "";
+  return std::string("an atom of model type ") + std::to_string(mt) + name + " is not among the active types of " + when +
+         " (ahip_set_active_types, or the type mapping the set was taken from): its forces are invalid; name every model type in use, or return to the automatic set (n = 0)";
+}
+// Installs `want` (strictly ascending model types; empty: no subset) as the active set: the fused side's model, its prepared weight streams, two-body and LDS tables
+// of all three families go (the next evaluation prepares them again for the new set), the byte table full -> compact type and the cutoffs at active x active are uploaded.
+static void apply_active(Model &m, const std::vector<int> &want) {
+  if (want == m.active) return;
+  AHIP_CHECK(hipDeviceSynchronize());        // kernels of an earlier device-resident evaluation may still read the table and the prepared state
+  m.active = want;
+  m.hm_fused_ready = false;
+  m.hm_fused = HostModel();
+  free_fused_states(m);
+  m.slot_cur = nullptr;
+  const int T = m.hm.num_types, A = (int)want.size();
+  if (A == 0 || T > FUSED_MAX_TYPES) return;  // (more than 255 types: the shape rule keeps such a model off the fused kernels, nothing reads a table)
+  std::vector<unsigned char> tab((size_t)T, (unsigned char)0xFF);
+  for (int k = 0; k < A; ++k) tab[(size_t)want[k]] = (unsigned char)k;
+  if (!m.slot_dev) AHIP_CHECK(hipMalloc((void **)&m.slot_dev, (size_t)T));
+  copy_h2d(m.slot_dev, tab.data(), (size_t)T);
+  m.rcut_fused_host.assign((size_t)A * A, 0.0);
+  for (int a = 0; a < A; ++a)
+    for (int b = 0; b < A; ++b) m.rcut_fused_host[(size_t)a * A + b] = m.rcut_model_host[(size_t)want[a] * T + want[b]];
+  if (m.rcut_fused_dev) { AHIP_CHECK(hipFree(m.rcut_fused_dev)); m.rcut_fused_dev = nullptr; }
+  AHIP_CHECK(hipMalloc((void **)&m.rcut_fused_dev, (size_t)A * A * sizeof(double)));
+  copy_h2d(m.rcut_fused_dev, m.rcut_fused_host.data(), (size_t)A * A * sizeof(double));
+}
+// The set an evaluation runs with: the explicit one, else -- for a model of more than 16 types only, so that no model the fused kernels already serve changes
+// its behaviour -- the types the last type mapping named, else none.
+static void resolve_active(Model &m) {
+  static const std::vector<int> none;
+  apply_active(m, !m.active_set.empty() ? m.active_set : (m.hm.num_types > FUSED_MAX_ACTIVE ? m.active_mapped : none));
+}
+// the model types a LAMMPS type mapper names (entries outside [0, T) are unmapped LAMMPS types), ascending
+static std::vector<int> mapped_types(const Model &m, int ntypes, const int *type_mapper) {
+  std::vector<int> v;
+  for (int k = 0; k < ntypes; ++k) if (type_mapper[k] >= 0 && type_mapper[k] < m.hm.num_types) v.push_back(type_mapper[k]);
+  std::sort(v.begin(), v.end());
+  v.erase(std::unique(v.begin(), v.end()), v.end());
+  return v;
+}
 // fused_arith=auto falls back to the f32-input MFMA instances for the rest of this model's life (engine.h): the prepared f16x2 weight streams go, the next
 // dispatch prepares the f32 ones; said once on stderr and kept for ahip_arith_note
 static void arith_degrade(Model &m, const std::string &why) {
@@ -168,6 +218,7 @@ static void arith_degrade(Model &m, const std::string &why) {
 // An alarm found at the START of an evaluation, or by an accessor, was raised by an EARLIER device-resident evaluation that nobody waited for: its forces were
 // not finite and have been handed out.  That is reported either way; under auto the model also switches to the f32 instance, so the error is reported once.
 void fused_poll_alarm(Model &m) {
+  if (const int bad = inactive_take(m)) throw ArgError(inactive_message(m, bad, "an EARLIER evaluation"));
   if (!alarm_take(m)) return;
   if (arith_may_degrade(m)) {
     arith_degrade(m, "an earlier evaluation produced a non-finite edge gradient on the f16x2 arithmetic (an activation left float16's range)");
@@ -197,6 +248,8 @@ void ahip_model_free(ahip_model *m) {
   free_weights(m->wd);
   if (m->cg_dev) (void)hipFree(m->cg_dev);
   if (m->rcut_model_dev) (void)hipFree(m->rcut_model_dev);
+  if (m->rcut_fused_dev) (void)hipFree(m->rcut_fused_dev);
+  if (m->slot_dev) (void)hipFree(m->slot_dev);
   for (DevBuf *b : {&m->b_flagwork, &m->b_ilist, &m->b_nloff, &m->b_nlj, &m->b_x, &m->b_ftype, &m->b_mtype, &m->b_f, &m->b_eatom,
                     &m->b_engvir, &m->b_cutsq, &m->b_cnt, &m->b_eoff, &m->b_eii, &m->b_ej, &m->b_rvec, &m->b_ett, &m->b_partial,
                     &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom,
@@ -714,6 +767,7 @@ static void run_model_selfcheck(ahip_model *m, const ComputeArgs &a) {
 }
 static void run_model(ahip_model *m, const ComputeArgs &a) {
   fused_poll_alarm(*m);                      // raised by an EARLIER device-resident evaluation (nobody waits for those kernels)
+  resolve_active(*m);                        // the active types of this evaluation (a change drops the prepared fused state)
   const bool wants_check = !m->arith.checked && arith_may_degrade(*m) && m->inum > 0 && !model_runs_f64(*m) && m->opt_path != Model::Path::Generic &&
                            !m->hm.allow_tf32 && fused_family(*m, nullptr) != FusedFamily::none &&
                            std::getenv("AHIP_NO_ARITH_SELFCHECK") == nullptr;
@@ -724,6 +778,7 @@ static void run_model(ahip_model *m, const ComputeArgs &a) {
 }
 static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   m->nedges = 0;
+  m->slot_cur = nullptr;
   m->last_heavy_centres = 0; m->last_heavy_edges = 0; m->last_tile_edges = -1;
   // W restarts with every dispatch: it always belongs to the evaluation whose forces reach f (self-check passes, ArithDegraded re-dispatch, float32 fallback)
   if (a.vatom) AHIP_CHECK(hipMemsetAsync(a.vatom, 0, (size_t)(a.nlocal + a.nghost) * 9 * sizeof(double), a.stream));
@@ -741,6 +796,9 @@ static void run_model_once(ahip_model *m, const ComputeArgs &a) {
   std::string why;
   const FusedFamily fam = m->opt_path == Model::Path::Generic ? FusedFamily::none : fused_family(*m, &why);
   const bool wide = fam == FusedFamily::lx32 || fam == FusedFamily::lx64;
+  // a fused kernel will run on the model restricted to its active types: the writers of fused-side types translate through the byte table (everything else, the
+  // heavy centres of the layer-at-a-time kernels included, keeps full model types)
+  if (fam != FusedFamily::none && !m->active.empty()) m->slot_cur = m->slot_dev;
   m->have_ett = false;
   m->nheavy = 0;
   // the largest tile of the wide kernel that will run: 64 slots, or 128 under wide_tile=auto where k_fused_lx has its 8-wave shape for this model
@@ -902,6 +960,7 @@ int ahip_compute(ahip_model *m, int nlocal, int nghost, const double *x, const i
       if (bad_range.load()) throw ArgError("ahip_compute: atom type out of range");
       if (bad_map.load()) throw ArgError("ahip_compute: LAMMPS type " + std::to_string(bad_map.load()) + " is not mapped to a model type (all pair coeffs are not set)");
     }
+    m->active_mapped = mapped_types(*m, ntypes, type_mapper);
     std::vector<double> cutsq((size_t)ntypes * ntypes);
     for (size_t k = 0; k < cutsq.size(); ++k) cutsq[k] = cutsq_bound(m, cutoff_matrix[k]);
     m->b_x.reserve((size_t)nall * 3 * sizeof(double));
@@ -962,6 +1021,10 @@ int ahip_compute(ahip_model *m, int nlocal, int nghost, const double *x, const i
       AHIP_CHECK(hipMemcpyAsync(m->h_eatom.data(), m->b_eatom.p, (size_t)nall * sizeof(double), hipMemcpyDeviceToHost, s));
     }
     AHIP_CHECK(hipEventSynchronize(m->f_events[nfch]));
+    if (const int bad = inactive_take(*m)) {   // an explicit active set that leaves out a type in use: reported by this call, before f is touched
+      (void)hipStreamSynchronize(s);
+      throw ArgError("ahip_compute: " + inactive_message(*m, bad, "this evaluation") + " (nothing was added to f)");
+    }
     if (alarm_take(*m)) {                    // raised by THIS evaluation: nothing of it has touched the caller's arrays yet
       (void)hipStreamSynchronize(s);         // (the copies into the page-locked vectors finish before anybody may free or refill them)
       if (arith_may_degrade(*m) && attempt == 0) {
@@ -1241,7 +1304,31 @@ int ahip_map_types_dev(ahip_model *m, int n, const int *type_dev, int ntypes, co
     require_model(m);
     if (n < 0 || ntypes < 1 || !type_mapper || (n > 0 && (!type_dev || !mtype_dev))) throw ArgError("ahip_map_types_dev: bad argument");
     AHIP_CHECK(hipSetDevice(m->device));
+    m->active_mapped = mapped_types(*m, ntypes, type_mapper);
     map_types(*m, n, type_dev, ntypes, type_mapper, mtype_dev, (hipStream_t)stream);
+  });
+}
+
+int ahip_set_active_types(ahip_model *m, int n, const int *model_types) {
+  return guarded([&] {
+    require_model(m);
+    if (n < 0 || (n > 0 && !model_types)) throw ArgError("ahip_set_active_types: bad argument");
+    std::vector<int> v(model_types, model_types + n);
+    for (int t : v)
+      if (t < 0 || t >= m->hm.num_types) throw ArgError("ahip_set_active_types: model type " + std::to_string(t) + " is outside the model's " + std::to_string(m->hm.num_types) + " types");
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    m->active_set = v;                       // installed by the next evaluation (run_model: resolve_active)
+  });
+}
+
+int ahip_get_active_types(ahip_model *m, int *n, int *model_types) {
+  return guarded([&] {
+    require_model(m);
+    if (!n) throw ArgError("ahip_get_active_types: n is NULL");
+    fused_poll_alarm(*m);                    // (an inactive type met by the last device-resident evaluation is reported here at the latest)
+    *n = (int)m->active.size();
+    if (model_types) std::copy(m->active.begin(), m->active.end(), model_types);
   });
 }
 
@@ -1275,7 +1362,7 @@ int ahip_nve_first_dev(ahip_model *m, int nlocal, int nall, double *x_dev, doubl
     if (nlocal < 0 || nall < nlocal || (nall > 0 && !f_dev) || (nlocal > 0 && (!x_dev || !v_dev || !mtype_dev || !mass_by_mtype)))
       throw ArgError("ahip_nve_first_dev: bad argument");
     AHIP_CHECK(hipSetDevice(m->device));
-    nve_first_step(nlocal, nall, x_dev, v_dev, f_dev, mtype_dev, mass_by_mtype, m->hm.num_types, dt, ftm2v, (hipStream_t)stream);
+    nve_first_step(*m, nlocal, nall, x_dev, v_dev, f_dev, mtype_dev, mass_by_mtype, m->hm.num_types, dt, ftm2v, (hipStream_t)stream);
   });
 }
 
@@ -1286,7 +1373,7 @@ int ahip_nve_dev(ahip_model *m, int mode, int n, double *x_dev, double *v_dev, c
     if (n < 0 || (n > 0 && (!x_dev || !v_dev || !f_dev || !mtype_dev || !mass_by_mtype))) throw ArgError("ahip_nve_dev: bad argument");
     if (mode != 0 && mode != 1) throw ArgError("ahip_nve_dev: mode must be 0 or 1");
     AHIP_CHECK(hipSetDevice(m->device));
-    nve_step(mode, n, x_dev, v_dev, f_dev, mtype_dev, mass_by_mtype, m->hm.num_types, dt, ftm2v, (hipStream_t)stream);
+    nve_step(*m, mode, n, x_dev, v_dev, f_dev, mtype_dev, mass_by_mtype, m->hm.num_types, dt, ftm2v, (hipStream_t)stream);
   });
 }
 

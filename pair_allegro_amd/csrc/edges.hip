@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "engine.h"
+#include "fused_type_slot.h"
 
 namespace ahip {
 
@@ -37,17 +38,18 @@ static constexpr int EB_PER_WAVE = 8;    // centres per wave
 struct __attribute__((aligned(32))) AtomXT { double x, y, z; int ft, mt; };
 
 // It also clears the edge build's header + look-back status words and the caller's 7 energy / virial sums (two memset launches less per call:
-// a small system's step is a chain of short launches).
+// a small system's step is a chain of short launches).  `mt` is the type the fused kernels see (e_tt, the centre records): the model type, or its compact slot under a
+// subset of active types (slot / bad: fused_type_slot.h; null without a subset -- one uniform branch, no load).  Nothing else reads AtomXT.mt.
 __global__ void __launch_bounds__(256) k_pack_xt(int nall, const double *__restrict__ x, const int *__restrict__ ftype,
                                                   const int *__restrict__ mtype, AtomXT *__restrict__ xt, unsigned long long *clear, int nclear,
-                                                  double *zero7) {
+                                                  double *zero7, const unsigned char *__restrict__ slot, int *bad) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < nclear) clear[i] = 0ull;
   if (i < 7) zero7[i] = 0.0;
   if (i >= nall) return;
   AtomXT a;
   a.x = x[3 * (size_t)i]; a.y = x[3 * (size_t)i + 1]; a.z = x[3 * (size_t)i + 2];
-  a.ft = ftype[i]; a.mt = mtype[i];
+  a.ft = ftype[i]; a.mt = fused_type_slot(slot, mtype[i], bad);
   xt[i] = a;
 }
 
@@ -572,7 +574,7 @@ bool edges_build_f32(Model &m, const ComputeArgs &a) {
   st.xt.reserve((size_t)nall * sizeof(AtomXT));
   const int nclear = (int)(bytes / 8);
   hipLaunchKernelGGL(k_pack_xt, dim3((std::max(nall, nclear) + 255) / 256), dim3(256), 0, a.stream, m.nall, a.x, a.ftype, a.mtype, (AtomXT *)st.xt.p,
-                     (unsigned long long *)st.flags.p, nclear, a.engvir);
+                     (unsigned long long *)st.flags.p, nclear, a.engvir, m.slot_cur, m.slot_cur ? inactive_word(m) : nullptr);
 #define EB_LAUNCH(CH, DY) hipLaunchKernelGGL((k_build_edges<CH, DY>), dim3(nblocks), dim3(EB_THREADS), 0, a.stream, inum, m.d_ilist, m.d_nloff, m.d_nlj,       \
                      (const AtomXT *)st.xt.p, a.cutsq, a.nft, nunits, (unsigned int *)hdr, (unsigned long long *)((char *)st.flags.p + 64),   \
                      m.b_eoff.as<int>(), m.b_eii.as<int>(), m.b_ej.as<int>(), m.b_rvec.as<float>(), hdr + 1, hdr + 2,                \

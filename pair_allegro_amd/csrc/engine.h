@@ -127,6 +127,17 @@ struct Model {
   // fused_shapes.h).  hm stays the model as loaded (layer-at-a-time kernels, metadata).
   HostModel hm_fused;
   bool hm_fused_ready = false;
+  // Active types (fused_shapes.h): the model types the caller's type mapping can produce.  While `active` is non-empty the fused side runs on the model restricted to
+  // it (fused_host_model: subset_host_model, then padded / lifted) with compact type slots 0 .. A - 1 in ascending model-type order; the three writers of fused-side
+  // types (edges.hip: k_pack_xt; fused_common.h: k_centre_info / k_pack_small, k_edge_types) translate through the byte table slot_dev.  Everything else -- hm, the
+  // layer-at-a-time kernels, heavy centres, ghost rows of atomic_energy, ahip_model_meta -- keeps full model types and full tables.
+  std::vector<int> active;                   // the subset in force (strictly ascending); empty: none, the fused side sees every type of the model
+  std::vector<int> active_set;               // set by ahip_set_active_types (sorted, unique); empty: automatic
+  std::vector<int> active_mapped;            // the model types named by the last type mapping (ahip_compute, ahip_map_types_dev); used when the model has more than 16 types and nothing was set
+  unsigned char *slot_dev = nullptr;         // [T] model type -> compact slot, 0xFF = inactive (valid while `active` is non-empty)
+  const unsigned char *slot_cur = nullptr;   // slot_dev while a fused kernel is about to run on the subset, else null: what the three writers are handed (run_model_once)
+  std::vector<double> rcut_fused_host;       // [A*A] slice of rcut_model_host at active x active
+  double *rcut_fused_dev = nullptr;
   long long chunk_edges = 2000000;
   int reserve_wgs = 0;                      // workgroup slots the persistent fused kernels leave free (for kernels of other streams)
   bool timing = false;
@@ -276,13 +287,25 @@ bool alarm_take(Model &m);                  // true (and cleared) when a kernel 
 void fused_poll_alarm(Model &m);            // alarm_take + the policy: auto -> degrade to f32 and report once; explicit f16x2 -> StateError
 // the model at the fixed shape of the fused kernel family its l_max and tensor features belong to (fused_shapes.h: the model itself when it is exactly that shape,
 // else zero-padded, and an l_max = 1 model with more than 32 tensor features lifted to l_max = 2)
+// ... of the model restricted to its active types when a subset is in force (Model::active)
 inline const HostModel &fused_host_model(Model &m) {
   const HostModel &h = m.hm;
   const FusedFamily cls = fused_shape_class(h);
-  if (fused_shape_exact(h, cls)) return h;
-  if (!m.hm_fused_ready) { m.hm_fused = fused_shaped_model(h, cls); m.hm_fused_ready = true; }
+  if (m.active.empty() && fused_shape_exact(h, cls)) return h;
+  if (!m.hm_fused_ready) {
+    m.hm_fused = m.active.empty() ? fused_shaped_model(h, cls) : fused_shaped_model(subset_host_model(h, m.active), cls);
+    m.hm_fused_ready = true;
+  }
   return m.hm_fused;
 }
+// what the fused side reads in place of num_types / rcut_model_*: the active count for the gates (-1: every type), the cutoffs at active x active
+inline int fused_n_active(const Model &m) { return m.active.empty() ? -1 : (int)m.active.size(); }
+inline const std::vector<double> &fused_rcut_host(const Model &m) { return m.active.empty() ? m.rcut_model_host : m.rcut_fused_host; }
+inline const double *fused_rcut_dev(const Model &m) { return m.active.empty() ? m.rcut_model_dev : m.rcut_fused_dev; }
+// host-mapped word next to the f16x2 alarm word (alarm_word(m) + 1): 1 + the model type of an atom whose type is not in the active set, raised by the writers
+// of fused-side types (such an atom takes slot 0, so every index stays in range); inactive_take reads and clears it, fused_poll_alarm reports it as ArgError
+inline int *inactive_word(Model &m) { return alarm_word(m) + 1; }
+int inactive_take(Model &m);
 // the arithmetic policy (arith_policy.h) applied to a model: k_fused (wide = false) or the wide kernels
 inline bool arith_may_degrade(const Model &m) { return arith_may_degrade(m.arith); }
 inline bool fused_tb_is_table(const Model &m) { return fused_tb_is_table(m.opt_fused_tb); }
@@ -390,9 +413,9 @@ void neigh_free(Model &m);
 // periodic images of a single rank's own atoms inside the halo (neigh.hip); returns their number (may exceed `capacity`: then the arrays hold the first `capacity`)
 int borders_local(Model &m, int nlocal, const double *x, const int *mtype, const double *lo, const double *hi, const double *box, double rc, int capacity,
                   double *xg, int *mtg, long long *src, double *shift, hipStream_t s);
-void nve_first_step(int n, int nall, double *x, double *v, double *f, const int *mtype, const double *mass_host, int ntypes, double dt, double ftm2v,
+void nve_first_step(Model &m, int n, int nall, double *x, double *v, double *f, const int *mtype, const double *mass_host, int ntypes, double dt, double ftm2v,
                     hipStream_t s);
-void nve_step(int mode, int n, double *x, double *v, const double *f, const int *mtype, const double *mass_dev_or_host,
+void nve_step(Model &m, int mode, int n, double *x, double *v, const double *f, const int *mtype, const double *mass_dev_or_host,
               int ntypes, double dt, double ftm2v, hipStream_t s);
 
 }  // namespace ahip

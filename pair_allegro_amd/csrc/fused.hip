@@ -1177,7 +1177,7 @@ static int append_frag_b(std::vector<float> &out, const double *W, int K, int N,
   return 2 * nterm * KS * (NT / 2);
 }
 // the gate itself: fused_shapes.h
-bool fused_model_supported(const Model &m, std::string *why) { return fused_narrow_supported(m.hm, resolve_arith(m, false), fused_tb_is_table(m), why); }
+bool fused_model_supported(const Model &m, std::string *why) { return fused_narrow_supported(m.hm, resolve_arith(m, false), fused_tb_is_table(m), why, fused_n_active(m)); }
 static_assert(MAXNL == 3, "fused_shapes.h: 1..3 layers");
 
 static void fused_prepare(Model &m) {

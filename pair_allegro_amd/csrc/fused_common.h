@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "fused_type_slot.h"
 #include "prims.h"
 
 namespace ahip {
@@ -381,9 +382,10 @@ static __global__ void k_pack_finish(int inum, int nseg, const int *seg_base, in
     ntiles[1] = 0;          // the fused kernel's tile counter
   }
 }
-static __global__ void k_centre_info(int inum, const int *ilist, const int *mtype, int2 *centre) {
+// (slot, bad: fused_type_slot.h -- the byte table of a subset of active types, null without one)
+static __global__ void k_centre_info(int inum, const int *ilist, const int *mtype, int2 *centre, const unsigned char *slot, int *bad) {
   int ii = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ii < inum) { const int i = ilist[ii]; centre[ii] = make_int2(i, mtype[i]); }
+  if (ii < inum) { const int i = ilist[ii]; centre[ii] = make_int2(i, fused_type_slot(slot, mtype[i], bad)); }
 }
 // Small systems (<= PACK_SMALL_ATOMS centres, below): the whole tile packing -- segment counts, their scan, the fill, the tile bounds
 // and the per-centre {atom, type} records -- in ONE single-workgroup launch instead of six (a 10 648-atom step is launch-bound: 0.056 -> 0.03 ms).
@@ -398,7 +400,7 @@ static constexpr int PACK_CH = 32768;          // atoms per LDS chunk of k_pack_
 // walkers of a chunk then hit different banks), the walks, the tiles' first edges and the tile bounds come from there.
 __device__ __forceinline__ int pack_lds_pos(int k) { return k + (k >> 7); }
 static __global__ void __launch_bounds__(PACK_SMALL_SEGS) k_pack_small(int inum, const int *eoff, int nseg, int *tile_a0, int *tile_e0, int *ntiles, int tile_slots, int maxa,
-                                                                       const int *ilist, const int *mtype, int2 *centre, const int *maxdeg = nullptr, int maxa_wide = 12) {
+                                                                       const int *ilist, const int *mtype, int2 *centre, const unsigned char *slot, int *bad, const int *maxdeg = nullptr, int maxa_wide = 12) {
   __shared__ int cnt[PACK_SMALL_SEGS];
   __shared__ int se[PACK_CH + PACK_CH / SEG + 2];
   __shared__ int total;
@@ -412,6 +414,10 @@ static __global__ void __launch_bounds__(PACK_SMALL_SEGS) k_pack_small(int inum,
     for (int q = 0; q < 8; ++q) { const int ii = i0 + q * PACK_SMALL_SEGS; iv[q] = ii < inum ? ilist[ii] : 0; }
 #pragma unroll
     for (int q = 0; q < 8; ++q) tv[q] = mtype[iv[q]];
+    if (slot) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) tv[q] = fused_type_slot(slot, tv[q], bad);
+    }
 #pragma unroll
     for (int q = 0; q < 8; ++q) { const int ii = i0 + q * PACK_SMALL_SEGS; if (ii < inum) centre[ii] = make_int2(iv[q], tv[q]); }
   }
@@ -474,9 +480,9 @@ static __global__ void __launch_bounds__(PACK_SMALL_SEGS) k_pack_small(int inum,
   if (sg == 0) { const int n = total; tile_a0[n] = inum; tile_e0[n] = eoff[inum]; ntiles[0] = n; ntiles[1] = 0; }
 }
 // packed per-edge types when the edge list did not come from the single-pass build (edges.hip writes them itself)
-static __global__ void k_edge_types(long long E, const int *e_ii, const int *e_j, const int *ilist, const int *mtype, unsigned char *e_tt) {
+static __global__ void k_edge_types(long long E, const int *e_ii, const int *e_j, const int *ilist, const int *mtype, unsigned char *e_tt, const unsigned char *slot, int *bad) {
   long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < E) e_tt[e] = (unsigned char)((mtype[ilist[e_ii[e]]] << 4) | mtype[e_j[e]]);
+  if (e < E) e_tt[e] = (unsigned char)((fused_type_slot(slot, mtype[ilist[e_ii[e]]], bad) << 4) | fused_type_slot(slot, mtype[e_j[e]], bad));
 }
 static __global__ void k_tile_e0(const int *ntiles, const int *tile_a0, const int *eoff, int *tile_e0) {
   int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -504,6 +510,8 @@ static void fused_tile_args(Model &m, TileBufs &tb, const ComputeArgs &a, Args &
   hipStream_t s = a.stream;
   const int inum = m.inum;
   if (!pre) {
+    const unsigned char *const slot = m.slot_cur;                 // subset of active types in force: the byte table and the word an inactive type raises
+    int *const bad = slot ? inactive_word(m) : nullptr;
     const int nseg = (inum + SEG - 1) / SEG;
     tb.seg_count.reserve((size_t)(nseg + 1) * sizeof(int));
     tb.seg_base.reserve((size_t)(nseg + 2) * sizeof(int));
@@ -515,17 +523,17 @@ static void fused_tile_args(Model &m, TileBufs &tb, const ComputeArgs &a, Args &
     const bool small = inum <= PACK_SMALL_ATOMS;
     if (small)
       hipLaunchKernelGGL(k_pack_small, dim3(1), dim3(PACK_SMALL_SEGS), 0, s, inum, m.b_eoff.as<int>(), nseg, tb.tile_a0.as<int>(), tb.tile_e0.as<int>(), tb.ntiles.as<int>(), slots, maxa,
-                         m.d_ilist, a.mtype, tb.centre.as<int2>(), maxdeg_sel, maxa_wide);
+                         m.d_ilist, a.mtype, tb.centre.as<int2>(), slot, bad, maxdeg_sel, maxa_wide);
     else {
       hipLaunchKernelGGL(k_pack_tiles<false>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, tb.seg_count.as<int>(), (const int *)nullptr, (int *)nullptr, slots, maxa, maxdeg_sel, maxa_wide);
       AHIP_CHECK(prim_exclusive_scan_i32(m.prim, tb.seg_count.as<int>(), tb.seg_base.as<int>(), nseg, s));
       hipLaunchKernelGGL(k_pack_tiles<true>, dim3((nseg + B - 1) / B), dim3(B), 0, s, inum, m.b_eoff.as<int>(), nseg, (int *)nullptr, tb.seg_base.as<int>(), tb.tile_a0.as<int>(), slots, maxa, maxdeg_sel, maxa_wide);
       hipLaunchKernelGGL(k_pack_finish, dim3(1), dim3(1), 0, s, inum, nseg, tb.seg_base.as<int>(), tb.tile_a0.as<int>(), tb.ntiles.as<int>());
-      hipLaunchKernelGGL(k_centre_info, dim3((inum + 255) / 256), dim3(256), 0, s, inum, m.d_ilist, a.mtype, tb.centre.as<int2>());
+      hipLaunchKernelGGL(k_centre_info, dim3((inum + 255) / 256), dim3(256), 0, s, inum, m.d_ilist, a.mtype, tb.centre.as<int2>(), slot, bad);
     }
     if (!m.have_ett) {            // two-pass edge build: its counts are on the host
       m.b_ett.reserve((size_t)std::max<long long>(m.nedges, 1));
-      hipLaunchKernelGGL(k_edge_types, dim3((unsigned)((m.nedges + 255) / 256)), dim3(256), 0, s, m.nedges, m.b_eii.as<int>(), m.b_ej.as<int>(), m.d_ilist, a.mtype, m.b_ett.as<unsigned char>());
+      hipLaunchKernelGGL(k_edge_types, dim3((unsigned)((m.nedges + 255) / 256)), dim3(256), 0, s, m.nedges, m.b_eii.as<int>(), m.b_ej.as<int>(), m.d_ilist, a.mtype, m.b_ett.as<unsigned char>(), slot, bad);
       m.have_ett = true;
     }
     if (!small) {
@@ -534,7 +542,7 @@ static void fused_tile_args(Model &m, TileBufs &tb, const ComputeArgs &a, Args &
     }
   }
   A.eoff = m.b_eoff.as<int>(); A.e_ii = m.b_eii.as<int>(); A.e_j = m.b_ej.as<int>();
-  A.e_tt = m.b_ett.as<unsigned char>(); A.rvec = m.b_rvec.as<float>(); A.rcut = m.rcut_model_dev;
+  A.e_tt = m.b_ett.as<unsigned char>(); A.rvec = m.b_rvec.as<float>(); A.rcut = fused_rcut_dev(m);
   int *const ntl = pre ? m.b_ntiles.as<int>() : tb.ntiles.as<int>();
   A.centre = pre ? m.b_centre.as<int2>() : tb.centre.as<int2>();
   A.tile_a0 = pre ? m.b_tile_a0.as<int>() : tb.tile_a0.as<int>(); A.tile_e0 = pre ? m.b_tile_e0.as<int>() : tb.tile_e0.as<int>(); A.ntiles = ntl;
@@ -681,7 +689,7 @@ static int fused_prepare_tail(Model &m, const HostModel &h, std::vector<float> &
   // two-body embedding table: per type pair, cubic Hermite in d on [0, r_c(pair)] from the float64 MLP
   A.tb_nk = 512;
   A.o_tbtab = w_mark(w);
-  if (tbt) append_two_body_table(w, h, m.rcut_model_host, A.tb_nk);
+  if (tbt) append_two_body_table(w, h, fused_rcut_host(m), A.tb_nk);
   // small tables: path weights (last layer: only the scalar paths, the rest zero)
   A.o_tpl = w_mark(w);
   for (int k = 0; k < NL; ++k) {

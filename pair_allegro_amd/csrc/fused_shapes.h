@@ -7,7 +7,12 @@
 //   k_fused   k_fused       l_max 1, 32 features      l_max = 1, U <= 32
 //   lx32      k_fused_lx    l_max 2, 32 features      l_max = 2, U <= 32
 //   lx64      k_fused_lx2   l_max 2, 64 features      l_max = 2, 33 <= U <= 64;  l_max = 1, 33 <= U <= 64 (lifted: model_io.h, lift_host_model)
-// all with S <= 64 scalars, MLP width <= 64, read-out width <= 32 (narrower models run zero-padded: pad_host_model), 1..3 layers, <= 16 types.
+// all with S <= 64 scalars, MLP width <= 64, read-out width <= 32 (narrower models run zero-padded: pad_host_model), 1..3 layers, <= 16 ACTIVE types.
+//
+// Active types: the model types the caller's type mapping can produce (engine.h: Model::active).  A fused evaluation runs on the model restricted to them
+// (model_io.h: subset_host_model; compact slots 0 .. A - 1 in ascending model-type order, 4 bits each in the packed edge types), so the gates count A, not the
+// model's T: a 20-type model mapped to three elements qualifies.  T <= 255 because the full -> compact table on the device holds bytes (0xFF = inactive).  The gates take
+// A as a trailing argument; a caller that leaves it out gets A = T.
 //
 // Instances by (MD, RD) = (latent MLP depth, read-out depth): (2, 1) on every arithmetic the family has; every other pair of MD in 1..3, RD in 1..2 on the
 // f16x2 arithmetic only (k_fused: with the tabulated two-body embedding).  Read-out depth 0 (a linear read-out) would need a different fold of the last
@@ -77,8 +82,24 @@ inline constexpr int lx_tile_maxa(bool wide128) { return wide128 ? 8 : 4; }
 inline constexpr const char *FUSED_WHY_DEPTHS =
     "fused kernels need MLP depth 1..3 and read-out depth 1..2 (a linear read-out, depth 0, needs a different fold of the last layer and has no instance)";
 
+// The type gate of every family.  n_active: the number of active types (see the head of this file), -1 = all of the model's.  The packed edge types hold two
+// 4-bit slots, the full -> compact table on the device one byte per model type.
+inline constexpr int FUSED_MAX_ACTIVE = 16, FUSED_MAX_TYPES = 255;
+inline bool fused_types_fit(const HostModel &h, int n_active, std::string *why) {
+  const int T = h.num_types, A = n_active < 0 ? T : n_active;
+  if (A != T && T > FUSED_MAX_TYPES) {
+    if (why) *why = "fused kernels on a subset of the types need a model of at most 255 types (byte table full -> compact type; this model has " + std::to_string(T) + ")";
+    return false;
+  }
+  if (A > FUSED_MAX_ACTIVE) {
+    if (why) *why = "fused kernels support at most 16 active model types (" + std::to_string(A) + " of the model's " + std::to_string(T) + " are mapped)";
+    return false;
+  }
+  return true;
+}
+
 // k_fused's gate: `arith` is the arithmetic the model's options resolve to on k_fused (resolve_arith, wide = false)
-inline bool fused_narrow_supported(const HostModel &h, Arith arith, bool tb_table, std::string *why) {
+inline bool fused_narrow_supported(const HostModel &h, Arith arith, bool tb_table, std::string *why, int n_active = -1) {
   auto no = [&](const char *msg) { if (why) *why = msg; return false; };
   if (h.l_max != 1) return no("fused kernels need l_max = 1");
   if (!fused_widths_fit(h, false)) return no("fused kernels hold at most U=32, S=64, MLP width 64, read-out width 32 (narrower models run zero-padded)");
@@ -93,12 +114,12 @@ inline bool fused_narrow_supported(const HostModel &h, Arith arith, bool tb_tabl
   // (fused_tb=mlp) its first linear is laid out for 8
   if (h.num_bessels < 1 || (!tb_table && h.num_bessels != 8)) return no("fused_tb=mlp needs 8 Bessel functions (the tabulated two-body embedding takes any number)");
   if (h.num_layers < 1 || h.num_layers > 3) return no("fused kernels need 1..3 layers");
-  if (h.num_types > 16) return no("fused kernels support at most 16 model types (4-bit packed edge types)");
+  if (!fused_types_fit(h, n_active, why)) return false;
   return true;
 }
 
 // the wide kernels' gate: `arith` is what the options resolve to on them (resolve_arith, wide = true)
-inline bool fused_wide_supported(const HostModel &h, Arith arith, std::string *why) {
+inline bool fused_wide_supported(const HostModel &h, Arith arith, std::string *why, int n_active = -1) {
   auto no = [&](const char *msg) { if (why) *why = msg; return false; };
   if (h.l_max != 2 && !(h.l_max == 1 && h.U > 32)) return no("wide fused kernels are built for l_max = 2 (an l_max = 1 model runs on them lifted when it has 33..64 tensor features)");
   if (!fused_widths_fit(h, true)) return no("wide fused kernels hold at most 64 tensor features, S=64, MLP width 64, read-out width 32 (narrower models run zero-padded)");
@@ -111,7 +132,7 @@ inline bool fused_wide_supported(const HostModel &h, Arith arith, std::string *w
   }
   if (h.num_bessels < 1) return no("no radial basis");      // any number of Bessel functions: the two-body embedding is always tabulated here
   if (h.num_layers < 1 || h.num_layers > 3) return no("fused kernels need 1..3 layers");
-  if (h.num_types > 16) return no("fused kernels support at most 16 model types (4-bit packed edge types)");
+  if (!fused_types_fit(h, n_active, why)) return false;
   return true;
 }
 
@@ -122,18 +143,18 @@ struct FusedDecision {
   Arith arith = AR_F32;
   std::string why;
 };
-inline FusedDecision fused_decide(const HostModel &h, Arith arith_narrow, Arith arith_wide, bool tb_table) {
+inline FusedDecision fused_decide(const HostModel &h, Arith arith_narrow, Arith arith_wide, bool tb_table, int n_active = -1) {
   FusedDecision d;
   std::string why1, why2;
-  if (fused_narrow_supported(h, arith_narrow, tb_table, &why1)) { d.family = FusedFamily::k_fused; d.arith = arith_narrow; }
-  else if (fused_wide_supported(h, arith_wide, &why2)) { d.family = fused_shape_class(h); d.arith = arith_wide; }
+  if (fused_narrow_supported(h, arith_narrow, tb_table, &why1, n_active)) { d.family = FusedFamily::k_fused; d.arith = arith_narrow; }
+  else if (fused_wide_supported(h, arith_wide, &why2, n_active)) { d.family = fused_shape_class(h); d.arith = arith_wide; }
   else { d.why = why1 + "; " + why2; return d; }
   d.l_run = fused_l_run(d.family); d.UF = fused_UF(d.family);
   return d;
 }
 // the same from an effective option (arith_effective) and the state of fused_arith=auto
-inline FusedDecision fused_decide(const HostModel &h, ArithOpt opt, bool degraded, bool force_f32, bool tb_table) {
-  return fused_decide(h, resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, false), resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, true), tb_table);
+inline FusedDecision fused_decide(const HostModel &h, ArithOpt opt, bool degraded, bool force_f32, bool tb_table, int n_active = -1) {
+  return fused_decide(h, resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, false), resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, true), tb_table, n_active);
 }
 
 }  // namespace ahip

@@ -131,6 +131,50 @@ HostModel lift_host_model(const HostModel &h, int LF) {
   return p;
 }
 
+HostModel subset_host_model(const HostModel &h, const std::vector<int> &active) {
+  const int T = h.num_types, A = (int)active.size();
+  if (A < 1) throw std::runtime_error("subset_host_model: no active type");
+  for (int k = 0; k < A; ++k) {
+    if (active[k] < 0 || active[k] >= T) throw std::runtime_error("subset_host_model: type " + std::to_string(active[k]) + " is outside the model's " + std::to_string(T) + " types");
+    if (k > 0 && active[k] <= active[k - 1]) throw std::runtime_error("subset_host_model: the active types must be strictly ascending");
+  }
+  HostModel p = h;
+  p.num_types = A;
+  p.type_names.clear();
+  p.type_names_joined.clear();
+  for (int k = 0; k < A; ++k) {
+    p.type_names.push_back(h.type_names.at((size_t)active[k]));
+    if (k) p.type_names_joined += " ";
+    p.type_names_joined += p.type_names.back();
+  }
+  if (!h.per_edge_type_cutoff.empty()) {
+    p.per_edge_type_cutoff.assign((size_t)A * A, 0.0);
+    for (int a = 0; a < A; ++a)
+      for (int b = 0; b < A; ++b) p.per_edge_type_cutoff[(size_t)a * A + b] = h.per_edge_type_cutoff[(size_t)active[a] * T + active[b]];
+  }
+  {   // first two-body linear [2 T + B][width]: centre one-hot rows, neighbour one-hot rows, Bessel rows
+    const HostTensor &t = h.get("tb.w0");
+    if (t.shape.size() != 2 || t.shape[0] < 2 * T) throw std::runtime_error("subset_host_model: unexpected shape of 'tb.w0'");
+    const int C = t.shape[1], B = t.shape[0] - 2 * T;
+    HostTensor o;
+    o.shape = {2 * A + B, C};
+    o.data.resize((size_t)(2 * A + B) * C);
+    auto row = [&](int dst, int src) { std::copy(t.data.begin() + (size_t)src * C, t.data.begin() + (size_t)(src + 1) * C, o.data.begin() + (size_t)dst * C); };
+    for (int k = 0; k < A; ++k) { row(k, active[k]); row(A + k, T + active[k]); }
+    for (int b = 0; b < B; ++b) row(2 * A + b, 2 * T + b);
+    p.tensors["tb.w0"] = o;
+  }
+  for (const char *name : {"scale", "shift"}) {
+    const HostTensor &t = h.get(name);
+    if (t.numel() != T) throw std::runtime_error(std::string("subset_host_model: unexpected shape of '") + name + "'");
+    HostTensor o;
+    o.shape = {A};
+    for (int k = 0; k < A; ++k) o.data.push_back(t.data[(size_t)active[k]]);
+    p.tensors[name] = o;
+  }
+  return p;
+}
+
 static std::vector<unsigned char> read_all(const std::string &path) {
   std::ifstream f(path, std::ios::binary);
   if (!f) throw std::runtime_error("cannot open model file " + path);

@@ -44,6 +44,12 @@ HostModel pad_host_model(const HostModel &h, int SF, int UF, int WF, int RF);
 // float64; it is what lets an l_max = 1 model with more than 32 tensor features run on the 64-feature l_max = 2 kernel (fused_shapes.h).
 HostModel lift_host_model(const HostModel &h, int LF);
 
+// The same model restricted to the model types `active` (strictly ascending, each in [0, T)), which take the compact slots 0 .. A - 1: rows active[k] and
+// T + active[k] of `tb.w0` (the centre and neighbour one-hot rows) followed by its Bessel rows, `scale`, `shift` and the type names at `active`, the per-pair cutoffs
+// at active x active (an empty matrix stays empty), num_types = A; every other tensor untouched.  A type enters the model nowhere else, so the atoms of a system
+// that uses only these types see exactly this model (float64: bit for bit).  Throws std::runtime_error when `active` is not strictly ascending or out of range.
+HostModel subset_host_model(const HostModel &h, const std::vector<int> &active);
+
 // Parses an in-memory blob.
 HostModel parse_blob(const unsigned char *p, size_t n, const std::string &origin);
 

@@ -13,6 +13,8 @@ namespace ahip {
 struct NbState {
   DevBuf bin_of, bin_cnt, bin_start, bin_fill, sorted, cnt, off, nlj, ilist, box, mapper;
   long long cap_j = 0;
+  DevBuf inv_mass;                         // nve helpers, more than 16 model types: 1 / mass by model type on the device ...
+  std::vector<double> inv_mass_host;       // ... and what it holds (uploaded when it changes)
 };
 
 struct BinGrid {
@@ -324,19 +326,30 @@ int borders_local(Model &m, int nlocal, const double *x, const int *mtype, const
 void neigh_free(Model &m) {
   if (!m.nb_state) return;
   NbState *st = (NbState *)m.nb_state;
-  for (DevBuf *b : {&st->bin_of, &st->bin_cnt, &st->bin_start, &st->bin_fill, &st->sorted, &st->cnt, &st->off, &st->nlj, &st->ilist, &st->box, &st->mapper})
+  for (DevBuf *b : {&st->bin_of, &st->bin_cnt, &st->bin_start, &st->bin_fill, &st->sorted, &st->cnt, &st->off, &st->nlj, &st->ilist, &st->box, &st->mapper, &st->inv_mass})
     b->release();
   delete st;
   m.nb_state = nullptr;
 }
 
+// Inverse masses by model type: up to 16 types travel by value in the kernel arguments (no upload, no table to keep), more in a small device table that is
+// uploaded when its content changes (the masses of a run do not).
 struct MassTab { double inv_mass[16]; };
+struct MassByValue {
+  MassTab t;
+  __device__ __forceinline__ double operator()(int mt) const { return t.inv_mass[mt]; }
+};
+struct MassByTable {
+  const double *inv_mass;
+  __device__ __forceinline__ double operator()(int mt) const { return inv_mass[mt]; }
+};
 
-__global__ void k_nve(int mode, int n, double *x, double *v, const double *f, const int *mtype, MassTab mt, double dt, double dtf) {
+template <class Mass>
+__global__ void k_nve(int mode, int n, double *x, double *v, const double *f, const int *mtype, Mass mass, double dt, double dtf) {
   long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3LL * n) return;
   long long i = t / 3;
-  double dtfm = dtf * mt.inv_mass[mtype[i]];
+  double dtfm = dtf * mass(mtype[i]);
   double vv = v[t] + dtfm * f[t];
   v[t] = vv;
   if (mode == 0) x[t] += dt * vv;
@@ -344,36 +357,64 @@ __global__ void k_nve(int mode, int n, double *x, double *v, const double *f, co
 
 // first half step + the zero-fill of the force array the coming evaluation accumulates into (rows [0, nall): locals after their force has been
 // used, ghosts outright): one launch instead of two in every step of the stand-alone driver
-__global__ void k_nve_first(int n, int nall, double *x, double *v, double *f, const int *mtype, MassTab mt, double dt, double dtf) {
+template <class Mass>
+__global__ void k_nve_first(int n, int nall, double *x, double *v, double *f, const int *mtype, Mass mass, double dt, double dtf) {
   long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 3LL * nall) return;
   if (t < 3LL * n) {
-    double dtfm = dtf * mt.inv_mass[mtype[t / 3]];
+    double dtfm = dtf * mass(mtype[t / 3]);
     double vv = v[t] + dtfm * f[t];
     v[t] = vv;
     x[t] += dt * vv;
   }
   f[t] = 0.0;
 }
-void nve_first_step(int n, int nall, double *x, double *v, double *f, const int *mtype, const double *mass_host, int ntypes, double dt, double ftm2v,
+static MassByValue mass_by_value(const double *mass_host, int ntypes) {
+  MassByValue mv;
+  for (int k = 0; k < 16; ++k) mv.t.inv_mass[k] = k < ntypes ? 1.0 / mass_host[k] : 0.0;
+  return mv;
+}
+// the device table of a model with more than 16 types, current for mass_host (a change waits for the kernels of `s` that still read the old content)
+static MassByTable mass_by_table(Model &m, const double *mass_host, int ntypes, hipStream_t s) {
+  if (!m.nb_state) m.nb_state = new NbState();
+  NbState &st = *(NbState *)m.nb_state;
+  std::vector<double> inv((size_t)ntypes);
+  for (int k = 0; k < ntypes; ++k) inv[(size_t)k] = 1.0 / mass_host[k];
+  if (inv != st.inv_mass_host) {
+    AHIP_CHECK(hipStreamSynchronize(s));
+    st.inv_mass.reserve(inv.size() * sizeof(double));
+    copy_h2d(st.inv_mass.p, inv.data(), inv.size() * sizeof(double));
+    st.inv_mass_host = inv;
+  }
+  return MassByTable{st.inv_mass.as<double>()};
+}
+void nve_first_step(Model &m, int n, int nall, double *x, double *v, double *f, const int *mtype, const double *mass_host, int ntypes, double dt, double ftm2v,
                     hipStream_t s) {
-  if (ntypes > 16) throw UnsupportedError("nve: more than 16 model types");
-  MassTab mt;
-  for (int k = 0; k < 16; ++k) mt.inv_mass[k] = k < ntypes ? 1.0 / mass_host[k] : 0.0;
   if (nall <= 0) return;
   const unsigned B = 256;
-  hipLaunchKernelGGL(k_nve_first, dim3((unsigned)((3LL * nall + B - 1) / B)), dim3(B), 0, s, n, nall, x, v, f, mtype, mt, dt, 0.5 * dt * ftm2v);
+  const dim3 G((unsigned)((3LL * nall + B - 1) / B));
+  if (ntypes <= 16) {
+    const MassByValue mv = mass_by_value(mass_host, ntypes);
+    hipLaunchKernelGGL(k_nve_first<MassByValue>, G, dim3(B), 0, s, n, nall, x, v, f, mtype, mv, dt, 0.5 * dt * ftm2v);
+  } else {
+    const MassByTable mt = mass_by_table(m, mass_host, ntypes, s);
+    hipLaunchKernelGGL(k_nve_first<MassByTable>, G, dim3(B), 0, s, n, nall, x, v, f, mtype, mt, dt, 0.5 * dt * ftm2v);
+  }
   AHIP_CHECK(hipGetLastError());
 }
 
-void nve_step(int mode, int n, double *x, double *v, const double *f, const int *mtype, const double *mass_host,
+void nve_step(Model &m, int mode, int n, double *x, double *v, const double *f, const int *mtype, const double *mass_host,
               int ntypes, double dt, double ftm2v, hipStream_t s) {
-  if (ntypes > 16) throw UnsupportedError("nve: more than 16 model types");
-  MassTab mt;
-  for (int k = 0; k < 16; ++k) mt.inv_mass[k] = k < ntypes ? 1.0 / mass_host[k] : 0.0;
   if (n <= 0) return;
   const unsigned B = 256;
-  hipLaunchKernelGGL(k_nve, dim3((unsigned)((3LL * n + B - 1) / B)), dim3(B), 0, s, mode, n, x, v, f, mtype, mt, dt, 0.5 * dt * ftm2v);
+  const dim3 G((unsigned)((3LL * n + B - 1) / B));
+  if (ntypes <= 16) {
+    const MassByValue mv = mass_by_value(mass_host, ntypes);
+    hipLaunchKernelGGL(k_nve<MassByValue>, G, dim3(B), 0, s, mode, n, x, v, f, mtype, mv, dt, 0.5 * dt * ftm2v);
+  } else {
+    const MassByTable mt = mass_by_table(m, mass_host, ntypes, s);
+    hipLaunchKernelGGL(k_nve<MassByTable>, G, dim3(B), 0, s, mode, n, x, v, f, mtype, mt, dt, 0.5 * dt * ftm2v);
+  }
   AHIP_CHECK(hipGetLastError());
 }
 

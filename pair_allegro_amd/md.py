@@ -171,7 +171,12 @@ class Simulation:
         self.x = torch.tensor(xg[idx], dtype=torch.float64, device=device)
         self.tag = torch.tensor(idx, dtype=torch.int64, device=device)
         self.mtype = torch.tensor(np.asarray(mtype_global)[idx], dtype=torch.int32, device=device)
-        v0 = np.zeros((self.nlocal, 3)) if v_global is None else np.asarray(v_global, dtype=np.float64)[idx]
+        # This driver holds model types from the start: no pair_coeff mapping ever reaches the library, so a model of more than 16 types is told here
+        # which of them the system uses (include/allegro_hip.h: ahip_set_active_types; atoms migrate between ranks, hence the global set)
+        mdl = getattr(backend, "model", None)
+        if mdl is not None and getattr(mdl, "num_types", 0) > 16 and hasattr(mdl, "set_active_types"):
+            mdl.set_active_types(np.unique(np.asarray(mtype_global)))
+        v0 =np.zeros((self.nlocal, 3)) if v_global is None else np.asarray(v_global, dtype=np.float64)[idx]
         self.v = torch.tensor(v0, dtype=torch.float64, device=device)
         self.f = torch.zeros((self.nlocal, 3), dtype=torch.float64, device=device)
         self.engvir = torch.zeros(7, dtype=torch.float64, device=device)

@@ -129,6 +129,37 @@ def init_weights(cfg: dict) -> Dict[str, np.ndarray]:
     return w
 
 
+def subset_types(cfg: dict, weights: Dict[str, np.ndarray], names) -> Tuple[dict, Dict[str, np.ndarray]]:
+    """The model restricted to the types ``names`` (any order, repeats allowed; kept in model order).
+
+    A type enters the model only as a one-hot row of the first two-body linear ``tb.w0`` (rows ``t`` for the centre,
+    ``T + t`` for the neighbour, then the Bessel rows), as ``scale`` / ``shift`` and as a row and column of
+    ``per_edge_type_cutoff``; slicing those gives a model that computes, for a system using only these types, exactly what
+    the full model computes (float64: bit for bit).  Use it to write a reduced model file
+    (``save_ahip(path, *subset_types(cfg, w, ["Ag", "Cu", "O"]))``); it is also the numpy statement of what the library
+    does on the fly for a model of more than 16 types (csrc/model_io.cpp: subset_host_model).
+    """
+    tn = list(cfg["type_names"])
+    T = len(tn)
+    missing = [n for n in names if n not in tn]
+    if missing:
+        raise ValueError(f"subset_types: {missing} not among the model's type names")
+    act = sorted({tn.index(n) for n in names})
+    if not act:
+        raise ValueError("subset_types: no type named")
+    c = dict(cfg)
+    c["type_names"] = [tn[t] for t in act]
+    pc = cfg.get("per_edge_type_cutoff")
+    if pc is not None:
+        c["per_edge_type_cutoff"] = np.asarray(pc, dtype=np.float64).reshape(T, T)[np.ix_(act, act)].tolist()
+    w = dict(weights)
+    w0 = np.asarray(weights["tb.w0"])
+    w["tb.w0"] = np.concatenate([w0[act], w0[[T + t for t in act]], w0[2 * T:]], axis=0)
+    w["scale"] = np.asarray(weights["scale"])[act].copy()
+    w["shift"] = np.asarray(weights["shift"])[act].copy()
+    return c, w
+
+
 # ----------------------------------------------------------------------------- blob I/O
 
 def _fmt(v) -> str:
