@@ -116,6 +116,7 @@ template <int NW, int NL = MAXNL> struct __attribute__((aligned(16))) Lds {
   float scale[16], shift[16];             // per-type energy scale / shift
   float res[NL][2];                       // residual update coefficients per layer
   int chunk[2];                           // first tile of the current / next claimed chunk
+  float wo1[32];                          // the read-out's final 32 -> 1 vector: read in every tile (a global load there drained the vector-memory queue behind `za`)
 };
 
 // ---------------------------------------------------------------------------- device helpers
@@ -291,9 +292,10 @@ template <int AR> struct RingT {
   f32x4 f[AR != 0 ? 1 : RING];
   u32x4 b[AR == 0 ? 1 : (AR == 1 ? RINGB : AR == 2 ? RINGB2 : RINGH)];
 };
-template <int AR, int KT, int NT, bool ACC, int RPI, class Epi>
+// BR = false: the caller has tested ring.act itself, around a PAIR of one-step linears (see lin_mix).
+template <int AR, int KT, int NT, bool ACC, int RPI, bool BR = true, class Epi>
 __device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in)[KT], f32x4 (&out)[NT], int v16, RingT<AR> &ring, Epi epi) {
-  if (!ring.act) {             // (uniform) a wave without edges in this tile: no fragments, no MFMAs, no epilogue; finite outputs for the arithmetic around the linears
+  if (BR && !ring.act) {             // (uniform) a wave without edges in this tile: no fragments, no MFMAs, no epilogue; finite outputs for the arithmetic around the linears
     if constexpr (!ACC) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) out[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -306,7 +308,7 @@ __device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32
 #pragma unroll
     for (int ks = 0; ks < KT / 2; ++ks) b[0][ks] = split_pair_h(in[2 * ks], in[2 * ks + 1]);
     Epi ep[1] = {epi};
-    linear_h<1, KT / 2, NT, ACC, false, (4 * RPI) % RINGH, Epi>(W, wp, b, reinterpret_cast<f32x4 (&)[1][NT]>(out), unused, v16, ring.b, ep);
+    linear_h<1, KT / 2, NT, ACC, false, (4 * RPI) % RINGH, Epi, true>(W, wp, b, reinterpret_cast<f32x4 (&)[1][NT]>(out), unused, v16, ring.b, ep);
   } else if constexpr (AR != 0) {
     static_assert(KT % 2 == 0, "K-steps are pairs of 16-feature tiles");
     constexpr int NTERM = AR == 1 ? 3 : 2;
@@ -323,17 +325,33 @@ __device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32
 // The three m components of an l = 1 row share ONE channel-mixing matrix: on the f16x2 arithmetic they go through the linear as three GROUPS that share every weight
 // fragment (linear_h<3, ...>: one fragment load, three B operands, three accumulator sets) instead of three passes over three copies of the matrix in the stream:
 // 8 KiB of fragments fewer per mixing block and direction and wave-tile.
-template <int RPI, class Epi>
+template <int RPI, bool BR = true, class Epi>
 __device__ __forceinline__ void lin_m3(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in0)[2], const f32x4 (&in1)[2], const f32x4 (&in2)[2], f32x4 (&out)[3][2], int v16,
                                        RingT<3> &ring, Epi (&epi)[3]) {
-  if (!ring.act) {
+  if (BR && !ring.act) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) { out[q][0] = f32x4{0.f, 0.f, 0.f, 0.f}; out[q][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     return;
   }
   Hop b[3][1], unused[3][1];
   b[0][0] = split_pair_h(in0[0], in0[1]); b[1][0] = split_pair_h(in1[0], in1[1]); b[2][0] = split_pair_h(in2[0], in2[1]);
-  linear_h<3, 1, 2, false, false, (4 * RPI) % RINGH, Epi>(W, wp, b, out, unused, v16, ring.b, epi);
+  linear_h<3, 1, 2, false, false, (4 * RPI) % RINGH, Epi, true>(W, wp, b, out, unused, v16, ring.b, epi);
+}
+// A channel mixing on the f16x2 arithmetic is two ONE-step linears (the l = 0 block, then lin_m3).  They share one `ring.act` branch: a region that consumes a whole
+// ring (two steps) leaves every slot at the age it had on entry, whichever way the branch went.  With a branch each, the path "first skipped, second taken" -- which
+// never runs, a wave is idle for a whole tile, but which the wait-count insertion has to merge -- presents the second linear's fragments as the youngest loads of the
+// queue, and its first products wait behind s_waitcnt vmcnt(3..2) for everything older.
+template <class Epi0, class Epi3>
+__device__ __forceinline__ void lin_mix(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in0)[2], const f32x4 (&in1)[2], const f32x4 (&in2)[2], const f32x4 (&in3)[2], f32x4 (&out0)[2],
+                                        f32x4 (&out)[3][2], int v16, RingT<3> &ring, Epi0 epi0, Epi3 (&epi)[3]) {
+  if (!ring.act) {
+    out0[0] = f32x4{0.f, 0.f, 0.f, 0.f}; out0[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { out[q][0] = f32x4{0.f, 0.f, 0.f, 0.f}; out[q][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    return;
+  }
+  lin<3, 2, 2, false, 0, false>(W, wp, in0, out0, v16, ring, epi0);
+  lin_m3<1, false>(W, wp, in1, in2, in3, out, v16, ring, epi);
 }
 
 // MD: hidden layers of the latent MLP (allegro_mlp_hidden_layers_depth of /root/reference/tests/test_data/test_repro_allegro.yaml:94; 2 there).  1 and 3 exist for the
@@ -345,20 +363,37 @@ struct TileIn {
   int eii, jat, tt;
   int eoff;
 };
-__device__ __forceinline__ void tile_fetch(const FusedArgs &A, int tile, int ntiles, int s, int tid, TileIn &n) {
-  n.a0 = n.a1 = n.e0 = n.e1 = 0;
-  n.rx = 1.f; n.ry = 0.f; n.rz = 0.f;
-  n.eii = 0; n.jat = 0; n.tt = 0; n.eoff = 0;
-  if (tile >= ntiles) return;                      // (uniform)
-  n.a0 = A.tile_a0[tile]; n.a1 = A.tile_a0[tile + 1]; n.e0 = A.tile_e0[tile]; n.e1 = A.tile_e0[tile + 1];
-  const int e = n.e0 + s, na = n.a1 - n.a0;
-  if (e < n.e1) {
-    n.rx = A.rvec[3 * (size_t)e]; n.ry = A.rvec[3 * (size_t)e + 1]; n.rz = A.rvec[3 * (size_t)e + 2];
-    n.eii = A.e_ii[e];
-    n.jat = A.e_j[e];
-    n.tt = A.e_tt[e];
-  }
-  if (tid <= na) n.eoff = A.eoff[n.a0 + tid];
+// The fetch is a REQUEST: nothing in it waits on the vector-memory queue, which holds the weight ring and the saved rows of the linear it runs under.
+//  - tile_bounds: the four bounds through SCALAR loads (the addresses are wave-uniform and the packing kernels wrote the arrays before this launch: the constant
+//    address space is what lets the compiler pick s_load_dword in a kernel that also stores).  Called a tile's length ahead of tile_fetch, their wait is lgkmcnt.
+//  - tile_fetch: per-edge and per-centre entries through range-checked buffer loads whose descriptors start at the tile's first edge / centre and end at its last:
+//    no branch (the join of an exec-masked branch gets s_waitcnt vmcnt(0)), a lane beyond the tile -- or any lane of a tile >= ntiles, whose bounds are 0 -- reads
+//    nothing and receives 0.  The one default that is not 0 (rx = 1: a finite unit vector for idle slots) is applied where the values are consumed.
+struct TileBounds { int a0, a1, e0, e1; };
+typedef const __attribute__((address_space(4))) int *cint_p;
+__device__ __forceinline__ TileBounds tile_bounds(const FusedArgs &A, int tile, int ntiles) {
+  const int tc = max(min(tile, ntiles - 1), 0);       // (uniform) a readable entry for every tile; both arrays hold at least two words
+  const cint_p ta = (cint_p)(unsigned long long)A.tile_a0, te = (cint_p)(unsigned long long)A.tile_e0;
+  TileBounds b = {ta[tc], ta[tc + 1], te[tc], te[tc + 1]};
+  if (tile >= ntiles) b = TileBounds{0, 0, 0, 0};
+  return b;
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t list_rsrc(const void *base, long long first_byte, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)((unsigned long long)base + (unsigned long long)first_byte), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ void tile_fetch(const FusedArgs &A, const TileBounds &b, int s, int tid, TileIn &n) {
+  n.a0 = b.a0; n.a1 = b.a1; n.e0 = b.e0; n.e1 = b.e1;
+  const int ne = b.e1 - b.e0, na = b.a1 - b.a0;       // (uniform) <= tile slots, <= MAXA
+  const int eb = b.e0 & 3;                            // the byte list's descriptor starts on a dword
+  const __amdgpu_buffer_rsrc_t RV = list_rsrc(A.rvec, 12ll * b.e0, 12 * ne), EI = list_rsrc(A.e_ii, 4ll * b.e0, 4 * ne), EJ = list_rsrc(A.e_j, 4ll * b.e0, 4 * ne),
+                               ET = list_rsrc(A.e_tt, b.e0 - eb, ne + eb), EO = list_rsrc(A.eoff, 4ll * b.a0, na > 0 ? 4 * (na + 1) : 0);
+  n.rx = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(RV, 12 * s, 0, 0));           // (three dwords: the 96-bit form of the builtin compiles to ONE dword here)
+  n.ry = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(RV, 12 * s + 4, 0, 0));
+  n.rz = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(RV, 12 * s + 8, 0, 0));
+  n.eii = (int)__builtin_amdgcn_raw_buffer_load_b32(EI, 4 * s, 0, 0);
+  n.jat = (int)__builtin_amdgcn_raw_buffer_load_b32(EJ, 4 * s, 0, 0);
+  n.tt = (int)__builtin_amdgcn_raw_buffer_load_b8(ET, s + eb, 0, 0);
+  n.eoff = (int)__builtin_amdgcn_raw_buffer_load_b32(EO, 4 * tid, 0, 0);
 }
 
 // VA: also the per-atom virial (output "atomic_virial"); instances launched only while that output is registered, so the default ones keep their code.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 + table only, built in fused_hr.o)
@@ -417,6 +452,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   if (A.T <= 4 && tid < A.T * A.T) lds.rc[tid] = (float)A.rcut[tid];
   if (tid < A.T) { lds.scale[tid] = Wb[A.o_scale + tid]; lds.shift[tid] = Wb[A.o_shift + tid]; }
   if (tid < 2 * A.NL) lds.res[tid >> 1][tid & 1] = Wb[A.o_res[tid >> 1] + (tid & 1)];
+  if (tid >= 64 && tid < 96) lds.wo1[tid - 64] = Wb[A.o_out1 + tid - 64];
 
   const int s = wave * 16 + j;                 // this lane's edge slot
   float *const st = lds.stage + s * STG_LD;
@@ -429,13 +465,22 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   int cbase = __builtin_amdgcn_readfirstlane(lds.chunk[0]);
 
   TileIn nx_;
-  tile_fetch(A, cbase, ntiles, s, tid, nx_);
+  tile_fetch(A, tile_bounds(A, cbase, ntiles), s, tid, nx_);
+  asm volatile("" : "+v"(nx_.rx), "+v"(nx_.ry), "+v"(nx_.rz), "+v"(nx_.eii), "+v"(nx_.jat), "+v"(nx_.tt), "+v"(nx_.eoff));       // landed before the loop is entered, as on its back edge (the finish waits for them in front of the force atomics): one queue state at the tile top
 
   for (;;) {
     const int tile = cbase + ck;
     if (tile >= ntiles) break;
     int claimed = 0;
-    if (ck == 0 && tid == 0) claimed = (int)atomicAdd(A.tile_counter, (unsigned)A.tchunk);
+    if (ck == 0 && tid == 0) {
+      // The counter's address goes through a vector register the optimiser cannot see through: with a provably uniform address the atomic is rewritten into a
+      // wave-wide reduction whose result is broadcast by v_readfirstlane right behind it, i.e. behind s_waitcnt vmcnt(0).  One lane runs this; the returned value is
+      // first touched at the `lds.chunk` write below, a whole phase later.
+      // (A GLOBAL atomic: a flat one makes every later wait a vmcnt(0).)
+      unsigned long long tcnt = (unsigned long long)A.tile_counter;
+      asm volatile("" : "+v"(tcnt));
+      claimed = (int)__hip_atomic_fetch_add((__attribute__((address_space(1))) unsigned int *)tcnt, (unsigned)A.tchunk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     // Everything a tile reads from the lists is ONE level of loads behind the (scalar) tile bounds: the edge
     // build packs the type pair per edge and k_tile_info the centre index/type, so no dependent chain
     // (edge -> centre -> type) is exposed here.  The whole set was requested a phase before the previous tile ended (tile_fetch below).
@@ -456,7 +501,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     int *const aoffp = lds.aoff[par];
     const int e = e0 + s;
     const bool valid = e < e1;
-    const float rx = nx_.rx, ry = nx_.ry, rz = nx_.rz;
+    const float rx = valid ? nx_.rx : 1.f, ry = nx_.ry, rz = nx_.rz;      // (a slot beyond the tile's edges fetched zeros: tile_fetch)
     const int aloc = valid ? nx_.eii - a0 : 0, jat = nx_.jat, ti = nx_.tt >> 4, tj = nx_.tt & 15;
     if (tid <= na) aoffp[tid] = nx_.eoff - e0;
     // ---------------- geometry ----------------
@@ -531,6 +576,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     }
     if (ck == 0 && tid == 0) lds.chunk[cpar ^ 1] = claimed;
     __syncthreads();          // aoff visible; previous tile's LDS users done
+    // the NEXT tile's bounds, requested a whole tile before tile_fetch builds its descriptors from them (the next chunk's first tile has just been published)
+    const TileBounds nb_ = tile_bounds(A, (ck + 1 == A.tchunk) ? __builtin_amdgcn_readfirstlane(lds.chunk[cpar ^ 1]) : tile + 1, ntiles);
     PHASE(PH_EMB);
 
     // ---------------- layers, forward ----------------
@@ -603,14 +650,12 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
           // f16x2: the l = 0 block, then the l = 1 block once for its three components (lin_m3)
           f32x4 o3[3][2];
           if (PARKV && kk + 1 == NL - 1) {                 // (the LAST layer's input tensor is not saved: see below)
-            lin<AR, 2, 2, false, 0>(WB, wp, Vp[0], o2, v16t, ring, EpiPark{pk, 0, lane});
             EpiPark ep[3] = {EpiPark{pk, 2, lane}, EpiPark{pk, 4, lane}, EpiPark{pk, 6, lane}};
-            lin_m3<1>(WB, wp, Vp[1], Vp[2], Vp[3], o3, v16t, ring, ep);
+            lin_mix(WB, wp, Vp[0], Vp[1], Vp[2], Vp[3], o2, o3, v16t, ring, EpiPark{pk, 0, lane}, ep);
           } else {
-            lin<AR, 2, 2, false, 0>(WB, wp, Vp[0], o2, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 0, v16t}, pk, 0, lane});
             EpiSavePark ep[3] = {EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 2, v16t}, pk, 2, lane}, EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 4, v16t}, pk, 4, lane},
                                  EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 6, v16t}, pk, 6, lane}};
-            lin_m3<1>(WB, wp, Vp[1], Vp[2], Vp[3], o3, v16t, ring, ep);
+            lin_mix(WB, wp, Vp[0], Vp[1], Vp[2], Vp[3], o2, o3, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 0, v16t}, pk, 0, lane}, ep);
           }
         } else if (PARKV && kk + 1 == NL - 1) {
           // the LAST layer's input tensor is not saved: nothing writes the park between its forward tensor product and its backward one (the last layer has
@@ -687,7 +732,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     f32x4 (&zo)[2] = RD == 2 ? zr2 : zr;        // pre-activations of the last hidden layer
     f32x4 wo1[2];              // the read-out's final 32 -> 1 vector (out.w1, or out.w2 of a depth-2 read-out)
 #pragma unroll
-    for (int t = 0; t < 2; ++t) wo1[t] = *(const f32x4 *)(Wb + A.o_out1 + 16 * t + 4 * g);
+    for (int t = 0; t < 2; ++t) wo1[t] = *(const f32x4 *)(lds.wo1 + 16 * t + 4 * g);
     float eps = 0.f;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -838,17 +883,18 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
       if (!last) {
         f32x4 in2[2], o2[2];
         in2[0] = park_load(pk, 0, lane); in2[1] = park_load(pk, 1, lane);
-        lin<AR, 2, 2, false, 0>(WB, wp, in2, o2, v16t, ring, EpiNone{});
-        dVp[0][0] += o2[0]; dVp[0][1] += o2[1];
         if constexpr (AR == 3) {
           f32x4 i1[2] = {park_load(pk, 2, lane), park_load(pk, 3, lane)}, i2[2] = {park_load(pk, 4, lane), park_load(pk, 5, lane)},
                 i3[2] = {park_load(pk, 6, lane), park_load(pk, 7, lane)};
           f32x4 o3[3][2];
           EpiNone ep[3];
-          lin_m3<1>(WB, wp, i1, i2, i3, o3, v16t, ring, ep);
+          lin_mix(WB, wp, in2, i1, i2, i3, o2, o3, v16t, ring, EpiNone{}, ep);
+          dVp[0][0] += o2[0]; dVp[0][1] += o2[1];
 #pragma unroll
           for (int q = 0; q < 3; ++q) { dVp[1 + q][0] = o3[q][0]; dVp[1 + q][1] = o3[q][1]; }
         } else {
+          lin<AR, 2, 2, false, 0>(WB, wp, in2, o2, v16t, ring, EpiNone{});
+          dVp[0][0] += o2[0]; dVp[0][1] += o2[1];
           in2[0] = park_load(pk, 2, lane); in2[1] = park_load(pk, 3, lane);
           lin<AR, 2, 2, false, 1>(WB, wp, in2, dVp[1], v16t, ring, EpiNone{});
           in2[0] = park_load(pk, 4, lane); in2[1] = park_load(pk, 5, lane);
@@ -932,11 +978,13 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     // ---------------- embedding backward ----------------
     // The NEXT tile's list entries are requested here, two phases before they are used: at the top of a tile they were two dependent
     // round trips (bounds, then entries) behind the wrap-around weight fragments in the in-order return queue -- 8 % of the wave-cycles.
-    // (The next chunk's first tile was published in lds.chunk by thread 0 during the chunk's first tile, several barriers ago.)
-    {
-      const int ntile = (ck + 1 == A.tchunk) ? __builtin_amdgcn_readfirstlane(lds.chunk[cpar ^ 1]) : tile + 1;
-      tile_fetch(A, ntile, ntiles, s, tid, nx_);
-    }
+    // Since 4.2c the fetch waits for nothing: its bounds (nb_) were read through the scalar unit at the tile's first barrier.
+    tile_fetch(A, nb_, s, tid, nx_);
+    // this thread's centre {atom, type}: requested with the next tile's entries, consumed behind the finish barrier.  A range-checked load, not a branch: a branch's join waited for vmcnt(0),
+    // i.e. for the acknowledgements of the force atomics below, with the whole workgroup at the barrier behind it.  (Its thread index: an opaque copy, see the finish.)
+    int tidc = tid;
+    asm volatile("" : "+v"(tidc));
+    auto cil_ = __builtin_amdgcn_raw_buffer_load_b64(list_rsrc(A.centre, 8ll * a0, 8 * na), (tidc >> 4) * 8, 0, 0);
     f32x4 zt1b[4];
     if constexpr (!TBT) load_rows<4>(SB, R_Z1TB(), zt1b, v16t);
     __builtin_amdgcn_sched_barrier(0);
@@ -1013,6 +1061,9 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
 #if !defined(ABL_NOW) && !defined(ABL_NOROWS) && !defined(ABL_NOROWLD) && !defined(ABL_NOROWST)
       if (AR == 3 && valid && !(fabsf(gx) + fabsf(gy) + fabsf(gz) + fabsf(eps) < 3.0e38f)) *A.err = 1;      // inf / NaN: an operand left float16's range
 #endif
+      // The next tile's entries and this thread's centre record are waited for HERE, in front of the force atomics (they were requested a linear ago, nothing younger
+      // is in flight): behind the atomics, the first wait for any of them would also wait for the atomics' acknowledgements -- at the top of the next tile.
+      asm volatile("" : "+v"(nx_.rx), "+v"(nx_.ry), "+v"(nx_.rz), "+v"(nx_.eii), "+v"(nx_.jat), "+v"(nx_.tt), "+v"(nx_.eoff), "+v"(cil_));
       if (g == 0) {
         st[0] = valid ? gx : 0.f; st[1] = valid ? gy : 0.f; st[2] = valid ? gz : 0.f; st[3] = valid ? eps : 0.f;      // selects, not products: a skipped wave's values are arbitrary
         if (valid) {
@@ -1043,9 +1094,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     int tidf = tid;
     asm volatile("" : "+v"(tidf));
     const int caf = tidf >> 4;
-    int2 cil = make_int2(0, 0);
-    if (caf < na) cil = A.centre[a0 + caf];          // this thread's centre {atom, type}: fetched here, under the barrier, instead of held since the tile's top
     __syncthreads();
+    const int2 cil = make_int2((int)cil_[0], (int)cil_[1]);
     {
       // per-centre sums of (g, eps): 16 lanes per atom = 4 columns x 4 row-parts; the atom index, scale and
       // shift of this thread's centre were prefetched with the tile.  No trailing barrier: the next tile's first
@@ -1069,10 +1119,12 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     if (++ck == A.tchunk) { ck = 0; cpar ^= 1; cbase = __builtin_amdgcn_readfirstlane(lds.chunk[cpar]); }
   }
   __syncthreads();
-  if (tid == 0) {
+  int tide = tid;                  // (an opaque copy, as in the finish: what the epilogue derives from the thread index is not kept -- in scratch -- across the tile loop)
+  asm volatile("" : "+v"(tide));
+  if (tide == 0) {
     for (int a = 0; a < MAXA; ++a) acc_part += lds.eacc[a];
-  } else if (tid >= 64 && tid < 70) {
-    for (int w = 0; w < NW; ++w) acc_part += lds.virw[w][tid - 64];
+  } else if (tide >= 64 && tide < 70) {
+    for (int w = 0; w < NW; ++w) acc_part += lds.virw[w][tide - 64];
   }
   if (PROF && lane == 0) {
 #pragma unroll
@@ -1086,8 +1138,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     o[2] = wall_clock64();
     o[3] = ((long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32) | (unsigned)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
   }
-  if (tid == 0) A.partial[7 * (size_t)blockIdx.x] = acc_part;
-  if (tid >= 64 && tid < 70) A.partial[7 * (size_t)blockIdx.x + 1 + (tid - 64)] = acc_part;
+  if (tide == 0) A.partial[7 * (size_t)blockIdx.x] = acc_part;
+  if (tide >= 64 && tide < 70) A.partial[7 * (size_t)blockIdx.x + 1 + (tide - 64)] = acc_part;
 }
 
 

@@ -69,12 +69,21 @@ template <class E> __device__ __forceinline__ f32x2 epi_apply2(E &e, int ot, int
 // Streamed linear, f16x2.  in[g][ks]: KS K-steps (pairs of 16-feature tiles, split) per group; out[g][t]: NT f32 tiles through the epilogue functors of
 // fused_common.h (one functor per group); SPLIT additionally emits the outputs as the next linear's B operands.  Fragments per (tile pair p, K-step):
 // hi0 hi1 lo0 lo1, 1 KiB each, in consumption order, RINGH of them in flight.  The 8 G epilogue elements of pair p-1 are spread over the MFMAs of pair p.
-template <int G, int KS, int NT, bool ACC, bool SPLIT, int RP, class Epi>
+template <int G, int KS, int NT, bool ACC, bool SPLIT, int RP, class Epi, bool LATE_OK = false>
 __device__ __forceinline__ void linear_h(__amdgpu_buffer_rsrc_t W, int &wp, const Hop (&in)[G][KS], f32x4 (&out)[G][NT], Hop (&outb)[G][NT / 2],
                                          int v16, u32x4 (&ring)[RINGH], Epi (&epi)[G]) {
   static_assert(NT % 2 == 0, "output tiles are processed in pairs");
   constexpr int RB = RINGH, NF = 4, NP = NT / 2, NSTEP = NP * KS, NS = NF * NSTEP;
   constexpr int MF = 6 * G;                        // MFMAs per step
+  // A step reads ring slot k and requests it again.  Requested BEFORE the step's products, the new fragment cannot land in the registers the products still read, so
+  // the ring's registers rotate; a linear of three or more steps rotates them back before it ends, a shorter one cannot, and at the join of lin()'s per-linear branch
+  // the compiler then copies the in-flight destinations into the ring's canonical registers behind s_waitcnt vmcnt(3..0): a drain of the whole in-order queue, eight
+  // times per wave-tile.  Short linears therefore request each slot right AFTER the last product that reads it (lo after m = 0, hi after m = 2).
+  // LATE_OK: k_fused only (the wide kernels order their linears by hand and have no per-linear branch).
+#ifndef AHIP_LATE_STEPS
+#define AHIP_LATE_STEPS 2                          // experiments: 0 = the round-6 form everywhere
+#endif
+  constexpr bool LATE = LATE_OK && NSTEP <= AHIP_LATE_STEPS;
   f32x4 ah[G][2], ac[G][2], prev[G][2];
   int wo = (wp + RB * 256) * 4;                    // byte offset of the next fragments to request: one running scalar (see linear_s)
   pin_s(wo);
@@ -92,12 +101,19 @@ __device__ __forceinline__ void linear_h(__amdgpu_buffer_rsrc_t W, int &wp, cons
     }
     u32x4 a[NF];
 #pragma unroll
-    for (int i = 0; i < NF; ++i) {
-      a[i] = ring[(RP + NF * s + i) % RB];
-      ring[(RP + NF * s + i) % RB] = __builtin_bit_cast(u32x4, bload_w(W, v16 + i * 1024, wo));      // + i KiB: the instruction's immediate offset
+    for (int i = 0; i < NF; ++i) a[i] = ring[(RP + NF * s + i) % RB];
+    if (!LATE) {
+      // (LATE_OK: lo before hi, the order of consumption and of the late form: a slot's age in the in-order queue is then the same after every linear)
+#pragma unroll
+      for (int q = 0; q < NF; ++q) {
+        const int i = LATE_OK ? (q + 2) % NF : q;
+        ring[(RP + NF * s + i) % RB] = __builtin_bit_cast(u32x4, bload_w(W, v16 + i * 1024, wo));      // + i KiB: the instruction's immediate offset
+      }
     }
-    wo += NF * 1024;
-    pin_s(wo);
+    if (!LATE) {
+      wo += NF * 1024;
+      pin_s(wo);
+    }
     // products: (w_lo', x_hi) -> ac, (w_hi, x_lo') -> ac, (w_hi, x_hi) -> ah; the accumulators of the two tiles and of the groups alternate
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
@@ -108,6 +124,11 @@ __device__ __forceinline__ void linear_h(__amdgpu_buffer_rsrc_t W, int &wp, cons
           if (m == 0) ac[g][hh] = mfma_h(a[2 + hh], in[g][ks].hi, ac[g][hh]);
           else if (m == 1) ac[g][hh] = mfma_h(a[hh], in[g][ks].lo, ac[g][hh]);
           else ah[g][hh] = mfma_h(a[hh], in[g][ks].hi, ah[g][hh]);
+          if (LATE && g == G - 1 && m != 1) {
+            // the last product that reads this fragment has been issued: its slot is requested again now, into the slot's own registers
+            const int i = m == 0 ? 2 + hh : hh;
+            ring[(RP + NF * s + i) % RB] = __builtin_bit_cast(u32x4, bload_w(W, v16 + i * 1024, wo));
+          }
           if (p > 0) {
             // the 4 G register pairs of the previous tile pair, spread over this pair's MFMAs
             const int idx = ks * MF + (m * 2 + hh) * G + g, tot = KS * MF, NE = 4 * G;
@@ -127,6 +148,10 @@ __device__ __forceinline__ void linear_h(__amdgpu_buffer_rsrc_t W, int &wp, cons
           __builtin_amdgcn_sched_barrier(0);
         }
       }
+    }
+    if (LATE) {
+      wo += NF * 1024;
+      pin_s(wo);
     }
     if (ks == KS - 1) {
 #pragma unroll
