@@ -25,7 +25,7 @@
 //            only for model files that set allow_tf32).
 //
 // Supported model shape (fused_shapes.h decides; others run the wide kernels or the generic path): l_max = 1, up to 32 tensor features (33..64: k_fused_lx2 on the lifted
-// model), up to 64 scalars, MLP width up to 64, read-out width up to 32 (narrower than the kernel's fixed 32 / 64 / 64 / 32: zero-padded by the host, model_io.cpp: pad_host_model),
+// model), up to 64 scalars, MLP width up to 64 (65..128: the WT = 8 instances, zero-padded to 128), read-out width up to 32 (narrower than the kernel's fixed 32 / 64 / 64 or 128 / 32: zero-padded by the host, model_io.cpp: pad_host_model),
 // MLPs of 2 hidden layers x 64 (1 or 3 hidden layers on the f16x2 instances with the tabulated two-body embedding: template parameter MD, round 5),
 // read-out 1 x 32 (2 x 32 on the same f16x2 instances: template parameter RD), <= 3 layers, <= 16 types; any number of Bessel functions and any cutoff-polynomial order (the radial basis only
 // enters through the tabulated two-body embedding; fused_tb=mlp needs 8).  Reference graph:
@@ -46,10 +46,11 @@
 #define AHIP_RING 4
 #include "fused_common.h"
 #include "fused_h.h"
+#include "fused_rows.h"
 #include "prims.h"
 
-// This file is compiled in four parts (Makefile; same options, divides the build time): AHIP_FUSED_PART 0 = the host side + the f32-input MFMA
-// instances of k_fused, AHIP_FUSED_PART 1 = the bf16-split instances, 2 = the f16x2 instances, 3 = their read-out-depth-2 twins.  (Rounds 2-3 gave part 1 other compiler options because it computed wrong
+// This file is compiled in five parts (Makefile; same options, divides the build time): AHIP_FUSED_PART 0 = the host side + the f32-input MFMA
+// instances of k_fused, AHIP_FUSED_PART 1 = the bf16-split instances, 2 = the f16x2 instances, 3 = their read-out-depth-2 twins, 4 = their MLP-width-128 twins.  (Rounds 2-3 gave part 1 other compiler options because it computed wrong
 // forces with part 0's: that was the store-data hazard described at fused_common.h: bstore, not the options.)
 #ifndef AHIP_FUSED_PART
 #define AHIP_FUSED_PART 0
@@ -121,15 +122,8 @@ template <int NW, int NL = MAXNL> struct __attribute__((aligned(16))) Lds {
 
 // ---------------------------------------------------------------------------- device helpers
 
-// scratch row map (per wave, rows of 1 KiB)
-__device__ __host__ constexpr int R_Z1TB() { return 0; }
-__device__ __host__ constexpr int R_Z2TB() { return 4; }
-__device__ __host__ constexpr int R_U0() { return 8; }
-__device__ __host__ constexpr int R_W0() { return 12; }
-// per layer: omega 4 | silu' of the MD hidden layers of the latent MLP, 4 each | u 4 | V_in 8   (MD = latent MLP depth, 1..3; 2 = the reference YAML's, 24 rows)
-__device__ __host__ constexpr int R_LSZ(int MD) { return 16 + 4 * MD; }
-__device__ __host__ constexpr int R_LAYER(int kk, int MD = 2) { return 16 + R_LSZ(MD) * kk; }
-__device__ __host__ constexpr int R_TOTAL(int NL, int MD = 2) { return 16 + R_LSZ(MD) * NL; }
+// scratch row map (per wave, rows of 1 KiB): fused_rows.h
+// per layer: omega 4 | silu' of the MD hidden layers of the latent MLP, WT each | u 4 | V_in 8   (MD = latent MLP depth, 1..3; WT = 16-feature tiles of a hidden layer, 4 or 8; MD = 2, WT = 4: the reference YAML's, 24 rows)
 
 static constexpr float C_S3 = 1.7320508075688772f;
 static constexpr float C_P1 = 0.5773502691896258f;     // (1,1,0): sqrt(1) * w3j = 1/sqrt(3)
@@ -397,7 +391,9 @@ __device__ __forceinline__ void tile_fetch(const FusedArgs &A, const TileBounds 
 }
 
 // VA: also the per-atom virial (output "atomic_virial"); instances launched only while that output is registered, so the default ones keep their code.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 + table only, built in fused_hr.o)
-template <int NW, bool PROF, int AR, bool TBT, int NLT, int MD = 2, bool VA = false, int RD = 1>
+// WT: 16-feature tiles of one hidden layer of the latent MLP: 4 (MLP width <= 64), or 8 (65..128, zero-padded to 128: f16x2 + table, read-out depth 1, not profiled; built in fused_hm.o).
+// Only the hidden vectors z, z2 / dh, du and their saved rows grow: no LDS array, table, latent x or environment row depends on it, so the LDS (two workgroups per CU at NW = 4) is the same.
+template <int NW, bool PROF, int AR, bool TBT, int NLT, int MD = 2, bool VA = false, int RD = 1, int WT = 4>
 __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   constexpr int NTHREADS = NW * 64, MAXA = Lds<NW>::MAXA;
   // f16x2 instances (round 5): the last hidden layer of the latent MLP saves its RAW pre-activation rows and the layer's output rows u are not saved at all: the backward
@@ -408,7 +404,16 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   // The LAST layer's activation rows (silu' / pre-activations of its last two hidden layers) live in the wave's own slots of the staging tile instead of scratch rows:
   // the tile is idle from that layer's environment sum to its backward tensor product (EpiSiluSaveDL / EpiSiluSaveZL): 8 row stores and 8 row loads fewer per wave-tile.
   constexpr bool STGROWS = true;           // (36.0 -> 34.3 ms)
-  constexpr int OZL = 4 + 4 * (MD - 1), OU = 4 + 4 * MD, OVIN = 8 + 4 * MD;      // row offsets inside a layer: silu' of the LAST hidden layer, u, V_in (MD = 2: 8, 12, 16)
+  // WT = 8: a slot's staging row (128 floats = 8 images) holds ONE 128-wide hidden layer, so only the last hidden layer is parked there (images 0..7); the one below it
+  // goes to the wave's scratch rows like a non-last layer's
+  constexpr bool STG2 = WT == 4;           // the hidden layer below the last is parked as well (images 0..3; the last one then sits in images ZQ = 4..7)
+  constexpr int ZQ = WT == 4 ? 4 : 0;
+  constexpr int OZL = R_OZ(MD, WT), OU = R_OU(MD, WT), OVIN = R_OVIN(MD, WT);      // row offsets inside a layer: silu' of the LAST hidden layer, u, V_in (MD = 2, WT = 4: 8, 12, 16)
+  static_assert(WT == 4 || (WT == 8 && AR == 3 && TBT && !PROF && RD == 1), "MLP width 128: f16x2 instances with the two-body table only, read-out depth 1, not profiled");
+  // every linear whose shape depends on WT consumes whole rings of the weight stream, so the ring phases (RPI) of everything behind it are those of WT = 4
+  static_assert(lin_frags_h(6, WT) % RINGH == 0 && lin_frags_h(WT, WT) % RINGH == 0 && lin_frags_h(WT, 4) % RINGH == 0 && lin_frags_h(4, WT) % RINGH == 0 && lin_frags_h(WT, 6) % RINGH == 0 &&
+                    lin_frags_h(WT, 2) % RINGH == 0 && lin_frags_h(2, WT) % RINGH == 0,
+                "the weight ring stays in phase");
   static_assert(MD >= 1 && MD <= 3 && (MD == 2 || (AR == 3 && TBT)), "latent MLP depth 1 / 3: f16x2 instances with the two-body table only");
   static_assert(RD == 1 || (RD == 2 && AR == 3 && TBT && !PROF), "read-out depth 2: f16x2 instances with the two-body table only, not profiled");
   __shared__ Lds<NW, NLT> lds;
@@ -585,7 +590,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
 #pragma unroll
     for (int kk = 0; kk < NL; ++kk) {
       const bool last = (kk == NL - 1);
-      const int RL = R_LAYER(kk, MD);
+      const int RL = R_LAYER(kk, MD, WT);
       float *const envk = lds.env[0] + kk * (MAXA * ENV_LD);
       f32x4 V[4][2];
       {
@@ -653,9 +658,9 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
             EpiPark ep[3] = {EpiPark{pk, 2, lane}, EpiPark{pk, 4, lane}, EpiPark{pk, 6, lane}};
             lin_mix(WB, wp, Vp[0], Vp[1], Vp[2], Vp[3], o2, o3, v16t, ring, EpiPark{pk, 0, lane}, ep);
           } else {
-            EpiSavePark ep[3] = {EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 2, v16t}, pk, 2, lane}, EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 4, v16t}, pk, 4, lane},
-                                 EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 6, v16t}, pk, 6, lane}};
-            lin_mix(WB, wp, Vp[0], Vp[1], Vp[2], Vp[3], o2, o3, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 0, v16t}, pk, 0, lane}, ep);
+            EpiSavePark ep[3] = {EpiSavePark{{SB, R_LAYER(kk + 1, MD, WT) + OVIN + 2, v16t}, pk, 2, lane}, EpiSavePark{{SB, R_LAYER(kk + 1, MD, WT) + OVIN + 4, v16t}, pk, 4, lane},
+                                 EpiSavePark{{SB, R_LAYER(kk + 1, MD, WT) + OVIN + 6, v16t}, pk, 6, lane}};
+            lin_mix(WB, wp, Vp[0], Vp[1], Vp[2], Vp[3], o2, o3, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD, WT) + OVIN + 0, v16t}, pk, 0, lane}, ep);
           }
         } else if (PARKV && kk + 1 == NL - 1) {
           // the LAST layer's input tensor is not saved: nothing writes the park between its forward tensor product and its backward one (the last layer has
@@ -665,37 +670,37 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
           lin<AR, 2, 2, false, 2>(WB, wp, Vp[2], o2, v16t, ring, EpiPark{pk, 4, lane});
           lin<AR, 2, 2, false, 3>(WB, wp, Vp[3], o2, v16t, ring, EpiPark{pk, 6, lane});
         } else {
-          lin<AR, 2, 2, false, 0>(WB, wp, Vp[0], o2, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 0, v16t}, pk, 0, lane});
-          lin<AR, 2, 2, false, 1>(WB, wp, Vp[1], o2, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 2, v16t}, pk, 2, lane});
-          lin<AR, 2, 2, false, 2>(WB, wp, Vp[2], o2, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 4, v16t}, pk, 4, lane});
-          lin<AR, 2, 2, false, 3>(WB, wp, Vp[3], o2, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD) + OVIN + 6, v16t}, pk, 6, lane});
+          lin<AR, 2, 2, false, 0>(WB, wp, Vp[0], o2, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD, WT) + OVIN + 0, v16t}, pk, 0, lane});
+          lin<AR, 2, 2, false, 1>(WB, wp, Vp[1], o2, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD, WT) + OVIN + 2, v16t}, pk, 2, lane});
+          lin<AR, 2, 2, false, 2>(WB, wp, Vp[2], o2, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD, WT) + OVIN + 4, v16t}, pk, 4, lane});
+          lin<AR, 2, 2, false, 3>(WB, wp, Vp[3], o2, v16t, ring, EpiSavePark{{SB, R_LAYER(kk + 1, MD, WT) + OVIN + 6, v16t}, pk, 6, lane});
         }
       }
       PHASE(PH_MIX);
       // latent MLP
       {
-        f32x4 cat[6], z[4], z2[4];
+        f32x4 cat[6], z[WT], z2[WT];
         cat[0] = x[0]; cat[1] = x[1]; cat[2] = x[2]; cat[3] = x[3]; cat[4] = Vp[0][0]; cat[5] = Vp[0][1];
         // hidden layer h (1..MD) saves silu'(z), the last one its raw z on the f16x2 instances (SAVEZ); in the last layer of the model the rows of hidden layers
-        // MD - 1 and MD go to the staging tile (images 0..3 and 4..7) instead of scratch
+        // MD - 1 and MD go to the staging tile (images 0..3 and 4..7) instead of scratch (WT = 8: those of hidden layer MD alone, images 0..7: STG2, ZQ)
         const bool stg = STGROWS && last;
         float *const sq = st + 4 * g;
 #define AHIP_HIDDEN(KT, IN, OUT, H) do { \
-          if (stg && (H) >= MD - 1) { \
-            if (SAVEZ && (H) == MD) lin<AR, KT, 4, false, 0>(WB, wp, IN, OUT, v16t, ring, EpiSiluSaveZL{sq, 4}); \
-            else lin<AR, KT, 4, false, 0>(WB, wp, IN, OUT, v16t, ring, EpiSiluSaveDL{sq, (H) == MD ? 4 : 0}); \
-          } else if (SAVEZ && (H) == MD) lin<AR, KT, 4, false, 0>(WB, wp, IN, OUT, v16t, ring, EpiSiluSaveZ{SB, RL + 4 * (H), v16t}); \
-          else lin<AR, KT, 4, false, 0>(WB, wp, IN, OUT, v16t, ring, EpiSiluSaveD{SB, RL + 4 * (H), v16t}); } while (0)
+          if (stg && (H) >= (STG2 ? MD - 1 : MD)) { \
+            if (SAVEZ && (H) == MD) lin<AR, KT, WT, false, 0>(WB, wp, IN, OUT, v16t, ring, EpiSiluSaveZL{sq, ZQ}); \
+            else lin<AR, KT, WT, false, 0>(WB, wp, IN, OUT, v16t, ring, EpiSiluSaveDL{sq, (H) == MD ? ZQ : 0}); \
+          } else if (SAVEZ && (H) == MD) lin<AR, KT, WT, false, 0>(WB, wp, IN, OUT, v16t, ring, EpiSiluSaveZ{SB, RL + R_OZ(H, WT), v16t}); \
+          else lin<AR, KT, WT, false, 0>(WB, wp, IN, OUT, v16t, ring, EpiSiluSaveD{SB, RL + R_OZ(H, WT), v16t}); } while (0)
         AHIP_HIDDEN(6, cat, z, 1);
-        if constexpr (MD >= 2) AHIP_HIDDEN(4, z, z2, 2);
-        if constexpr (MD >= 3) AHIP_HIDDEN(4, z2, z, 3);
+        if constexpr (MD >= 2) AHIP_HIDDEN(WT, z, z2, 2);
+        if constexpr (MD >= 3) AHIP_HIDDEN(WT, z2, z, 3);
 #undef AHIP_HIDDEN
-        f32x4 (&zl)[4] = MD == 2 ? z2 : z;              // output of the last hidden layer
+        f32x4 (&zl)[WT] = MD == 2 ? z2 : z;             // output of the last hidden layer
         const float ra = lds.res[kk][0], rbf = lds.res[kk][1] * fc;
         if (!last) {
           f32x4 xn[4];
-          if constexpr (SAVEZ) lin<AR, 4, 4, false, 0>(WB, wp, zl, xn, v16t, ring, EpiResidualNS<4>{x, ra, rbf});
-          else lin<AR, 4, 4, false, 0>(WB, wp, zl, xn, v16t, ring, EpiResidual<4>{{SB, RL + OU, v16t}, x, ra, rbf});
+          if constexpr (SAVEZ) lin<AR, WT, 4, false, 0>(WB, wp, zl, xn, v16t, ring, EpiResidualNS<4>{x, ra, rbf});
+          else lin<AR, WT, 4, false, 0>(WB, wp, zl, xn, v16t, ring, EpiResidual<4>{{SB, RL + OU, v16t}, x, ra, rbf});
           x[0] = xn[0]; x[1] = xn[1]; x[2] = xn[2]; x[3] = xn[3];
         } else {
           // Last layer: its new latent x' = ra x + rb fc (z2 W3) feeds nothing but the read-out's first linear, and no non-linearity
@@ -703,8 +708,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
           // 64 -> 32 linears instead of a 64 -> 64 and a 64 -> 32 one, here and (transposed) in the backward pass: 64 of the tile's
           // 1472 MFMAs per wave and two saved rows less.  z2 first: it dies there.
           f32x4 za[2], up[2];
-          if constexpr (SAVEZ) lin<AR, 4, 2, false, 0>(WB, wp, zl, up, v16t, ring, EpiNone{});
-          else lin<AR, 4, 2, false, 0>(WB, wp, zl, up, v16t, ring, EpiSave{SB, RL + OU, v16t});
+          if constexpr (SAVEZ) lin<AR, WT, 2, false, 0>(WB, wp, zl, up, v16t, ring, EpiNone{});
+          else lin<AR, WT, 2, false, 0>(WB, wp, zl, up, v16t, ring, EpiSave{SB, RL + OU, v16t});
           lin<AR, 4, 2, false, 0>(WB, wp, x, za, v16t, ring, EpiNone{});
           zr[0] = ra * za[0] + rbf * up[0]; zr[1] = ra * za[1] + rbf * up[1];
         }
@@ -715,10 +720,10 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     // ---------------- read-out ----------------
     // saved rows are requested one linear ahead of their first use all through the backward pass (their
     // round trip is an L2 miss: ~2 us): u and z2 of the last layer now, under the read-out MFMAs
-    f32x4 upre[4], zt[4], w0h[2];
+    f32x4 upre[4], zt[WT], w0h[2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) if (!SAVEZ) upre[t] = bload(SB, v16t, (R_LAYER(NL - 1, MD) + OU + t) * ROW * 4);       // the last layer saved two rows: z2 (W3 Wr)
-    if (!STGROWS) load_rows<4>(SB, R_LAYER(NL - 1, MD) + OZL, zt, v16t);
+    for (int t = 0; t < 2; ++t) if (!SAVEZ) upre[t] = bload(SB, v16t, (R_LAYER(NL - 1, MD, WT) + OU + t) * ROW * 4);       // the last layer saved two rows: z2 (W3 Wr)
+    if (!STGROWS) load_rows<WT>(SB, R_LAYER(NL - 1, MD, WT) + OZL, zt, v16t);
     __builtin_amdgcn_sched_barrier(0);
     f32x4 zr2[2];              // RD = 2: pre-activations of the read-out's second hidden layer
     if constexpr (RD == 2) {
@@ -773,7 +778,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     lin<AR, 2, 4, false, 0>(WB, wp, dzr, dx, v16t, ring, EpiNone{});               // dzr Wr^T = the gradient w.r.t. x' of the last layer
     if (STGROWS) {                                                                 // the last layer's rows of its last hidden layer, from the staging tile
 #pragma unroll
-      for (int t = 0; t < 4; ++t) zt[t] = stg_load(st + 4 * g, 4 + t);
+      for (int t = 0; t < WT; ++t) zt[t] = stg_load(st + 4 * g, ZQ + t);
     }
     float dfc_part = 0.f, dY1 = 0.f, dY2 = 0.f, dY3 = 0.f;
     PHASE(PH_OUT);
@@ -781,31 +786,32 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
 #pragma unroll
     for (int kk = NL - 1; kk >= 0; --kk) {
       const bool last = (kk == NL - 1);
-      const int RL = R_LAYER(kk, MD);
+      const int RL = R_LAYER(kk, MD, WT);
       f32x4 dVp[4][2], Vk[4][2], W0b[4];
       {
-        f32x4 du[4], dh[4];
-        f32x4 zt1[4];
+        f32x4 du[WT], dh[WT];
+        f32x4 zt1[WT];
         if (!last && SAVEZ) {
           // the u rows are not saved: <u, g> = <silu(z), g W^T> comes out of the first backward linear's epilogue (EpiMulSiluZ), whose input is the unscaled gradient
           const float ra = lds.res[kk][0], rb = lds.res[kk][1];
-          if constexpr (MD >= 2) load_rows<4>(SB, RL + OZL - 4, zt1, v16t);
+          if constexpr (MD >= 2) load_rows<WT>(SB, RL + OZL - WT, zt1, v16t);
           __builtin_amdgcn_sched_barrier(0);
           float ug = 0.f;
-          lin<AR, 4, 4, false, 0>(WB, wp, dx, dh, v16t, ring, EpiMulSiluZ<4>{zt, rb * fc, ug});
+          lin<AR, 4, WT, false, 0>(WB, wp, dx, dh, v16t, ring, EpiMulSiluZ<WT>{zt, rb * fc, ug});
           dfc_part += rb * ug;
 #pragma unroll
           for (int t = 0; t < 4; ++t) dx[t] = ra * dx[t];
         } else if (last && SAVEZ) {
           const float ra = lds.res[kk][0], rb = lds.res[kk][1];
-          if constexpr (MD >= 2) { if (!STGROWS) load_rows<4>(SB, RL + OZL - 4, zt1, v16t); }
+          if constexpr (MD >= 2) { if (!(STGROWS && STG2)) load_rows<WT>(SB, RL + OZL - WT, zt1, v16t); }      // (WT = 8: the staging row holds the last hidden layer alone)
           __builtin_amdgcn_sched_barrier(0);
           float ug = 0.f;
-          lin<AR, 2, 4, false, 0>(WB, wp, dzr, dh, v16t, ring, EpiMulSiluZ<4>{zt, rb * fc, ug});
+          lin<AR, 2, WT, false, 0>(WB, wp, dzr, dh, v16t, ring, EpiMulSiluZ<WT>{zt, rb * fc, ug});
           dfc_part += rb * ug;
 #pragma unroll
           for (int t = 0; t < 4; ++t) dx[t] = ra * dx[t];
         } else if (!last) {
+          if constexpr (!SAVEZ) {             // (the instances that save u rows: WT = 4)
           const float ra = lds.res[kk][0], rb = lds.res[kk][1];
           f32x4 accv = upre[0] * dx[0];
 #pragma unroll
@@ -817,7 +823,9 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
           if constexpr (MD >= 2) load_rows<4>(SB, RL + OZL - 4, zt1, v16t);                  // silu' of the hidden layer below the last: first used 96 MFMAs from here
           __builtin_amdgcn_sched_barrier(0);
           lin<AR, 4, 4, false, 0>(WB, wp, du, dh, v16t, ring, EpiMulRows<4>{zt});
+          }
         } else {
+          if constexpr (!SAVEZ) {
           // last layer (read-out folded in, see the forward pass): upre = the two rows z2 (W3 Wr); the z2 gradient comes straight
           // from dzr through (W3 Wr)^T
           const float ra = lds.res[kk][0], rb = lds.res[kk][1];
@@ -832,9 +840,10 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
           if constexpr (MD >= 2) { if (!STGROWS) load_rows<4>(SB, RL + OZL - 4, zt1, v16t); }
           __builtin_amdgcn_sched_barrier(0);
           lin<AR, 2, 4, false, 0>(WB, wp, du2, dh, v16t, ring, EpiMulRows<4>{zt});
+          }
         }
         if constexpr (MD >= 2) {
-          if (STGROWS && last) {                                 // silu' of the hidden layer below the last, from the staging tile
+          if (STGROWS && STG2 && last) {                         // silu' of the hidden layer below the last, from the staging tile
 #pragma unroll
             for (int t = 0; t < 4; ++t) zt1[t] = stg_load(st + 4 * g, t);
           }
@@ -849,15 +858,15 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
         __builtin_amdgcn_sched_barrier(0);
         // down the hidden layers: g_{k-1} = (g_k W_k^T) * silu'(z_{k-1}), then dcat = g_0 W_0^T
         f32x4 dcat[6];
-        if constexpr (MD == 1) lin<AR, 4, 6, false, 0>(WB, wp, dh, dcat, v16t, ring, EpiNone{});
+        if constexpr (MD == 1) lin<AR, WT, 6, false, 0>(WB, wp, dh, dcat, v16t, ring, EpiNone{});
         else {
-          f32x4 zt0[4];
-          if constexpr (MD == 3) load_rows<4>(SB, RL + 4, zt0, v16t);
-          lin<AR, 4, 4, false, 0>(WB, wp, dh, du, v16t, ring, EpiMulRows<4>{zt1});
+          f32x4 zt0[WT];
+          if constexpr (MD == 3) load_rows<WT>(SB, RL + R_OZ(1, WT), zt0, v16t);
+          lin<AR, WT, WT, false, 0>(WB, wp, dh, du, v16t, ring, EpiMulRows<WT>{zt1});
           if constexpr (MD == 3) {
-            lin<AR, 4, 4, false, 0>(WB, wp, du, dh, v16t, ring, EpiMulRows<4>{zt0});
-            lin<AR, 4, 6, false, 0>(WB, wp, dh, dcat, v16t, ring, EpiNone{});
-          } else lin<AR, 4, 6, false, 0>(WB, wp, du, dcat, v16t, ring, EpiNone{});
+            lin<AR, WT, WT, false, 0>(WB, wp, du, dh, v16t, ring, EpiMulRows<WT>{zt0});
+            lin<AR, WT, 6, false, 0>(WB, wp, dh, dcat, v16t, ring, EpiNone{});
+          } else lin<AR, WT, 6, false, 0>(WB, wp, du, dcat, v16t, ring, EpiNone{});
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) dx[t] += dcat[t];
@@ -961,13 +970,17 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
         }
         asm volatile("" : "+v"(dY1), "+v"(dY2), "+v"(dY3));      // summed HERE: sunk to their use at the end of the tile, the sums keep a gradient row alive (in scratch) across the linear below
         if (kk > 0) {                                                      // next iteration's u and z2 rows
-          if (!SAVEZ) load_rows<4>(SB, R_LAYER(kk - 1, MD) + OU, upre, v16t);
-          load_rows<4>(SB, R_LAYER(kk - 1, MD) + OZL, zt, v16t);
+          if (!SAVEZ) load_rows<4>(SB, R_LAYER(kk - 1, MD, WT) + OU, upre, v16t);
+          load_rows<WT>(SB, R_LAYER(kk - 1, MD, WT) + OZL, zt, v16t);
         } else {                                                           // two-body u and z2 rows, l=1 embedding weights
           if constexpr (!TBT) {
             load_rows<4>(SB, R_U0(), upre, v16t);
             load_rows<4>(SB, R_Z2TB(), zt, v16t);
-          } else load_rows<4>(SB, R_Z1TB(), zt, v16t);                      // d x0 / dd rows of the two-body table
+          } else if constexpr (WT == 4) load_rows<4>(SB, R_Z1TB(), zt, v16t);      // d x0 / dd rows of the two-body table
+          else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) zt[t] = bload(SB, v16t, (R_Z1TB() + t) * ROW * 4);      // (four rows into the first half of the eight)
+          }
           load_rows<2>(SB, R_W0() + 2, w0h, v16t);
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1147,6 +1160,15 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
 void fused_launch_bf16(int nw, bool prof, int arith, bool tbt, int grid, hipStream_t s, const FusedArgs &A);
 void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const FusedArgs &A);
 void fused_launch_f16_rd2(int nw, int md, int grid, hipStream_t s, const FusedArgs &A);
+void fused_launch_f16_w128(int nw, int md, int grid, hipStream_t s, const FusedArgs &A);
+#if AHIP_FUSED_PART == 4
+// the MLP-width-128 f16x2 instances (fused_hm.o; template parameter WT = 8): two-body table only, latent MLP depth 1..3, read-out depth 1, plain and per-atom virial, not profiled
+void fused_launch_f16_w128(int nw, int md, int grid, hipStream_t s, const FusedArgs &A) {
+  dispatch<Choices<4, 8>, Choices<1, 2, 3>, Choices<1, 3, 2>, Choices<VAR_VA, VAR_PLAIN>>([&](auto nw, auto nl, auto md, auto var) {
+    hipLaunchKernelGGL((k_fused<nw, false, 3, true, nl, md, var == VAR_VA, 1, 8>), dim3(grid), dim3(nw * 64), 0, s, A);
+  }, nw, A.NL, md, fused_variant(A.vatom, false));
+}
+#endif
 #if AHIP_FUSED_PART == 3
 // the read-out-depth-2 f16x2 instances (fused_hr.o): two-body table only, latent MLP depth 1..3, plain and per-atom virial, not profiled
 void fused_launch_f16_rd2(int nw, int md, int grid, hipStream_t s, const FusedArgs &A) {
@@ -1188,6 +1210,7 @@ struct FusedState {
   bool tbt = true;             // two-body embedding from the spline table (default) or evaluated as an MLP (option fused_tb=mlp)
   int md = 2;                  // hidden layers of the latent MLP (template parameter MD of k_fused)
   int rd = 1;                  // hidden layers of the read-out MLP (template parameter RD)
+  int wt = 4;                  // 16-feature tiles of a hidden layer of the latent MLP (template parameter WT: 4 = MLP width 64, 8 = 128)
   Arith arith = AR_F32;        // arith_policy.h: resolve_arith (every arithmetic has its k_fused instances)
   DevBuf prof, dbg;
   int ncu = 256;
@@ -1242,11 +1265,13 @@ static void fused_prepare(Model &m) {
   FusedArgs &A = st.args;
   std::memset(&A, 0, sizeof(A));
   // two-body: pair table (type-type rows of the first layer)
-  const HostTensor &w0 = h.get("tb.w0");          // [2T+8][64]
+  const int W = h.mlp_width;                      // hidden width of the MLPs at the kernel's shape: 64 or 128 (fused_shapes.h: FUSED_WF, FUSED_WF2)
+  if (W != FUSED_WF && W != FUSED_WF2) throw UnsupportedError("fused kernels: MLP width " + std::to_string(W) + " is not a width of the kernel");      // (fused_host_model pads to one)
+  const HostTensor &w0 = h.get("tb.w0");          // [2T+8][W]
   A.o_pair = w_mark(w);
   for (int ti = 0; ti < T; ++ti)
     for (int tj = 0; tj < T; ++tj)
-      for (int n = 0; n < 64; ++n) w.push_back((float)(w0.data[(size_t)ti * 64 + n] + w0.data[(size_t)(T + tj) * 64 + n]));
+      for (int n = 0; n < 64; ++n) w.push_back((float)(w0.data[(size_t)ti * W + n] + w0.data[(size_t)(T + tj) * W + n]));      // (read by fused_tb=mlp only: W = 64)
   // ---- the weight stream, in the order one tile consumes it ----
   A.o_stream = w_mark(w);
   const size_t stream0 = w.size();
@@ -1254,6 +1279,7 @@ static void fused_prepare(Model &m) {
   st.arith = resolve_arith(m, false);
   st.md = h.mlp_depth;
   st.rd = h.readout_depth;
+  st.wt = W / 16;
   const int MD = st.md, RD = st.rd;
   const bool b3 = st.arith == AR_BF16X3 || st.arith == AR_TF32EQ, h2 = st.arith == AR_F16X2, tbt = st.tbt;
   const int nterm = st.arith == AR_BF16X3 ? 3 : 2;
@@ -1268,16 +1294,17 @@ static void fused_prepare(Model &m) {
     else if (b3) append_frag_b(w, t.data(), N, K, K, nterm); else append_frag(w, t.data(), N, K, K);
   };
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
-  const double *wc = w0.data.data() + (size_t)2 * T * 64;       // Bessel block [8][64]
-  std::vector<double> w3r((size_t)64 * 32, 0.0);                // W3 (last layer) @ Wr (read-out), float64
+  const double *wc = w0.data.data() + (size_t)2 * T * W;        // Bessel block [8][W]
+  std::vector<double> w3r((size_t)W * 32, 0.0);                 // W3 (last layer, [W][64]) @ Wr (read-out), float64
   {
     const double *W3 = T_("l" + std::to_string(NL) + ".lat.w" + std::to_string(MD)), *Wr = T_("out.w0");
-    for (int i = 0; i < 64; ++i)
+    for (int i = 0; i < W; ++i)
       for (int q = 0; q < 64; ++q)
         for (int n = 0; n < 32; ++n) w3r[(size_t)i * 32 + n] += W3[(size_t)i * 64 + q] * Wr[(size_t)q * 32 + n];
   }
   if (!tbt && MD != 2) throw UnsupportedError("fused_tb=mlp needs MLP depth 2");
   if (RD != 1 && !h2) throw UnsupportedError("fused kernels: read-out depth 2 has f16x2 instances only");      // (fused_model_supported keeps such a model away)
+  if (W != FUSED_WF && !(h2 && tbt && RD == 1)) throw UnsupportedError("fused kernels: MLP width 65..128 has f16x2 instances with the two-body table and read-out depth 1 only");      // (likewise)
   if (!tbt) {
     fwd(wc, 8, 64);
     fwd(T_("tb.w1"), 64, 64);
@@ -1292,11 +1319,11 @@ static void fused_prepare(Model &m) {
       fwd(mx, 32, 32);
       for (int c = 0; c < (h2 ? 1 : 3); ++c) fwd(mx + 1024, 32, 32);      // f16x2: once, shared by the three components (k_fused: lin_m3)
     }
-    fwd(T_(lk + ".lat.w0"), 96, 64);
-    for (int hl = 1; hl < MD; ++hl) fwd(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64);
-    if (k < NL - 1) fwd(T_(lk + ".lat.w" + std::to_string(MD)), 64, 64);
+    fwd(T_(lk + ".lat.w0"), 96, W);
+    for (int hl = 1; hl < MD; ++hl) fwd(T_(lk + ".lat.w" + std::to_string(hl)), W, W);
+    if (k < NL - 1) fwd(T_(lk + ".lat.w" + std::to_string(MD)), W, 64);
     else {            // last layer: the read-out's first linear applied, multiplied into W3, to z2 and then to x (k_fused, latent MLP)
-      fwd(w3r.data(), 64, 32);
+      fwd(w3r.data(), W, 32);
       fwd(T_("out.w0"), 64, 32);
     }
   }
@@ -1307,10 +1334,10 @@ static void fused_prepare(Model &m) {
   bwd(T_("out.w0"), 64, 32);
   for (int k = NL - 1; k >= 0; --k) {
     const std::string lk = "l" + std::to_string(k + 1);
-    if (k < NL - 1) bwd(T_(lk + ".lat.w" + std::to_string(MD)), 64, 64);
-    else bwd(w3r.data(), 64, 32);
-    for (int hl = MD - 1; hl >= 1; --hl) bwd(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64);
-    bwd(T_(lk + ".lat.w0"), 96, 64);
+    if (k < NL - 1) bwd(T_(lk + ".lat.w" + std::to_string(MD)), W, 64);
+    else bwd(w3r.data(), W, 32);
+    for (int hl = MD - 1; hl >= 1; --hl) bwd(T_(lk + ".lat.w" + std::to_string(hl)), W, W);
+    bwd(T_(lk + ".lat.w0"), 96, W);
     if (k < NL - 1) {
       const double *mx = T_(lk + ".mix");
       bwd(mx, 32, 32);
@@ -1331,7 +1358,7 @@ static void fused_prepare(Model &m) {
   // two-body table (see k_fused), small tables, upload, scalar arguments, float16 range verdict: fused_common.h
   st.ncu = fused_prepare_tail(m, h, w, A, st.wbuf, tbt, 5, 32, nullptr, st.arith, h_flags);
   // Persistent workgroups, 8 waves per CU either way (two per SIMD, 256 registers each).
-  A.wave_scratch = (long long)R_TOTAL(NL, MD) * ROW;
+  A.wave_scratch = (long long)R_TOTAL(NL, MD, st.wt) * ROW;
   st.scratch.reserve((size_t)st.ncu * 8 * A.wave_scratch * sizeof(float));
   A.scratch = st.scratch.as<float>();
   st.tiles.partial.reserve((size_t)st.ncu * 2 * 7 * sizeof(double));
@@ -1398,6 +1425,7 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
       // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
       A.tchunk = (nedges_est / (16 * shape) > (long long)g * 256) ? TCHUNK : 1;
       if (const char *tc = std::getenv("AHIP_TCHUNK")) A.tchunk = std::max(1, std::atoi(tc));       // experiments
+      if (st.arith == AR_F16X2 && st.wt == 8) { fused_launch_f16_w128(shape, st.md, g, s, A); continue; }                   // fused_hm.o (read-out depth 1: fused_prepare)
       if (st.arith == AR_F16X2 && st.rd == 2) { fused_launch_f16_rd2(shape, st.md, g, s, A); continue; }                     // fused_hr.o
       if (st.arith == AR_F16X2) { fused_launch_f16(shape, st.prof_on, st.md, g, s, A); continue; }                        // fused_h.o
       if (st.arith != AR_F32) { fused_launch_bf16(shape, st.prof_on, st.arith, st.tbt, g, s, A); continue; }     // fused_bf.o
@@ -1580,6 +1608,7 @@ extern "C" int ahip_debug_fused_linear(int K, int N, const double *W, const floa
 #define CASEB(ks, nt) do { if (h2) hipLaunchKernelGGL((k_selftest_linear_h<ks, nt>), dim3(1), dim3(128), 0, 0, dW, wbytes, din, K, dout, N); \
                            else if (nterm == 3) hipLaunchKernelGGL((k_selftest_linear_b<ks, nt, 3>), dim3(1), dim3(128), 0, 0, dW, wbytes, din, K, dout, N); \
                            else hipLaunchKernelGGL((k_selftest_linear_b<ks, nt, 2>), dim3(1), dim3(128), 0, 0, dW, wbytes, din, K, dout, N); } while (0)
+#define CASEH(ks, nt) hipLaunchKernelGGL((k_selftest_linear_h<ks, nt>), dim3(1), dim3(128), 0, 0, dW, wbytes, din, K, dout, N)
     if (b3) {
       if (KT == 1 && NT == 2) CASEB(1, 2);
       else if (KT == 1 && NT == 4) CASEB(1, 4);
@@ -1587,9 +1616,18 @@ extern "C" int ahip_debug_fused_linear(int K, int N, const double *W, const floa
       else if (KT == 2 && NT == 4) CASEB(2, 4);
       else if (KT == 3 && NT == 4) CASEB(3, 4);
       else if (KT == 2 && NT == 6) CASEB(2, 6);
+      // the f16x2 shapes of the MLP-width-128 instances (k_fused WT = 8, k_fused_lx HT = 8)
+      else if (h2 && KT == 3 && NT == 8) CASEH(3, 8);
+      else if (h2 && KT == 4 && NT == 8) CASEH(4, 8);
+      else if (h2 && KT == 4 && NT == 4) CASEH(4, 4);
+      else if (h2 && KT == 1 && NT == 8) CASEH(1, 8);
+      else if (h2 && KT == 4 && NT == 6) CASEH(4, 6);
+      else if (h2 && KT == 2 && NT == 8) CASEH(2, 8);
+      else if (h2 && KT == 4 && NT == 2) CASEH(4, 2);
       else ok = false;
     } else
 #undef CASEB_
+#undef CASEH
 #define CASE(kt, nt) hipLaunchKernelGGL((k_selftest_linear<kt, nt>), dim3(1), dim3(128), 0, 0, dW, wbytes, din, K, dout, N)
     if (KT == 2 && NT == 2) CASE(2, 2);
     else if (KT == 2 && NT == 4) CASE(2, 4);

@@ -611,13 +611,14 @@ static std::vector<double> transpose(const double *W, int K, int N) {
 // stored as cubic-Hermite coefficients [pair][NK intervals][tile 4][coef 4][16]; the kernels gather 16 x 16 B per lane.
 static void append_two_body_table(std::vector<float> &w, const HostModel &h, const std::vector<double> &rcut_model_host, int NKin) {
   const int T = h.num_types;
-  const HostTensor &w0 = h.get("tb.w0");          // [2T+B][64]
-  const double *wc = w0.data.data() + (size_t)2 * T * 64;       // Bessel block [B][64], B = num_bessels: any count (the kernels never see the basis, only the table)
+  const int WH = h.mlp_width;                     // hidden width of the two-body MLP (the model's mlp_width, padded: 64 or 128); its output is the 64 scalars
+  const HostTensor &w0 = h.get("tb.w0");          // [2T+B][WH]
+  const double *wc = w0.data.data() + (size_t)2 * T * WH;       // Bessel block [B][WH], B = num_bessels: any count (the kernels never see the basis, only the table)
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
   struct { const std::vector<double> &rcut_model_host; } m{rcut_model_host};
   const int NK = NKin;
   const double PI = 3.14159265358979323846;
-  // hidden layers beyond the first: tb.w1 .. tb.w{depth-1} (64 x 64), output layer tb.w{depth}; depth = the model's MLP depth (1..3 on the fused paths)
+  // hidden layers beyond the first: tb.w1 .. tb.w{depth-1} (WH x WH), output layer tb.w{depth} (WH x 64); depth = the model's MLP depth (1..3 on the fused paths)
   const int depth = h.mlp_depth;
   std::vector<const double *> Wh;
   for (int k = 1; k <= depth; ++k) Wh.push_back(T_("tb.w" + std::to_string(k)));
@@ -638,27 +639,27 @@ static void append_two_body_table(std::vector<float> &w, const HostModel &h, con
           fcv = 1.0 - ca * xp + cb * xp * xq - cc * xp * xq * xq;
           dfc = -ca * p * xp1 + cb * (p + 1) * xp - cc * (p + 2) * xp * xq;
         }
-        double z[64], dz[64], hh[64], dh[64];
-        for (int n = 0; n < 64; ++n) { z[n] = w0.data[(size_t)ti * 64 + n] + w0.data[(size_t)(T + tj) * 64 + n]; dz[n] = 0; }
+        std::vector<double> z(WH), dz(WH), hh(WH), dh(WH);
+        for (int n = 0; n < WH; ++n) { z[n] = w0.data[(size_t)ti * WH + n] + w0.data[(size_t)(T + tj) * WH + n]; dz[n] = 0; }
         for (int b = 1; b <= h.num_bessels; ++b) {
           const double a = b * PI / rc;
           double sv, ds;                                // s = sin(a d)/d and ds/dd, series near 0
           if (a * d < 1e-4) { sv = a * (1.0 - a * a * d * d / 6.0); ds = -a * a * a * d / 3.0; }
           else { sv = std::sin(a * d) / d; ds = (a * d * std::cos(a * d) - std::sin(a * d)) / (d * d); }
           const double bf = 2.0 / rc * sv * fcv, dbf = 2.0 / rc * (ds * fcv + sv * dfc / rc);
-          for (int n = 0; n < 64; ++n) { z[n] += wc[(size_t)(b - 1) * 64 + n] * bf; dz[n] += wc[(size_t)(b - 1) * 64 + n] * dbf; }
+          for (int n = 0; n < WH; ++n) { z[n] += wc[(size_t)(b - 1) * WH + n] * bf; dz[n] += wc[(size_t)(b - 1) * WH + n] * dbf; }
         }
-        for (int n = 0; n < 64; ++n) { hh[n] = silu(z[n]); dh[n] = dsilu(z[n]) * dz[n]; }
+        for (int n = 0; n < WH; ++n) { hh[n] = silu(z[n]); dh[n] = dsilu(z[n]) * dz[n]; }
         for (int l = 0; l + 1 < depth; ++l) {            // hidden layers 2 .. depth, value and d/dd (forward mode)
-          for (int n = 0; n < 64; ++n) { z[n] = 0; dz[n] = 0; }
-          for (int q = 0; q < 64; ++q)
-            for (int n = 0; n < 64; ++n) { z[n] += hh[q] * Wh[l][(size_t)q * 64 + n]; dz[n] += dh[q] * Wh[l][(size_t)q * 64 + n]; }
-          for (int n = 0; n < 64; ++n) { hh[n] = silu(z[n]); dh[n] = dsilu(z[n]) * dz[n]; }
+          for (int n = 0; n < WH; ++n) { z[n] = 0; dz[n] = 0; }
+          for (int q = 0; q < WH; ++q)
+            for (int n = 0; n < WH; ++n) { z[n] += hh[q] * Wh[l][(size_t)q * WH + n]; dz[n] += dh[q] * Wh[l][(size_t)q * WH + n]; }
+          for (int n = 0; n < WH; ++n) { hh[n] = silu(z[n]); dh[n] = dsilu(z[n]) * dz[n]; }
         }
         const double *Wo = Wh[depth - 1];
         for (int n = 0; n < 64; ++n) {
           double u = 0, du = 0;
-          for (int q = 0; q < 64; ++q) { u += hh[q] * Wo[(size_t)q * 64 + n]; du += dh[q] * Wo[(size_t)q * 64 + n]; }
+          for (int q = 0; q < WH; ++q) { u += hh[q] * Wo[(size_t)q * 64 + n]; du += dh[q] * Wo[(size_t)q * 64 + n]; }
           y[(size_t)k * 64 + n] = fcv * u;
           dy[(size_t)k * 64 + n] = dfc / rc * u + fcv * du;
         }

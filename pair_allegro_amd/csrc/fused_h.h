@@ -30,6 +30,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct Hop { u32x4 hi, lo; };                  // B operand of one K-step (two 16-feature tiles): 8 f16 per lane and term
 static constexpr float H_LO_SCALE = 2048.f, H_LO_INV = 1.f / 2048.f;
 static constexpr int RINGH = 8;                // fragments in flight: two steps of hi0 hi1 lo0 lo1
+// fragments of the weight stream one linear of KT input and NT output tiles consumes (linear_h: four per tile pair and K-step)
+constexpr int lin_frags_h(int KT, int NT) { return 4 * (NT / 2) * (KT / 2); }
 
 __device__ __forceinline__ f32x4 mfma_h(u32x4 a, u32x4 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);

@@ -33,9 +33,11 @@
 namespace ahip {
 
 // The shape of k_fused_lx: l_max = 2, 2 16-feature tiles (32 tensor features); NW = 4 waves (one per SIMD, 64 edge slots) or 8 (two per SIMD, 128 slots:
-// centres with 65..128 edges, option wide_tile=auto)
-template <int NW_> struct ShapeX {
+// centres with 65..128 edges, option wide_tile=auto); HT = 16-feature tiles of a hidden layer of the latent MLP: 4 (MLP width <= 64) or 8 (65..128, zero-padded to 128),
+// which only the saved-row map knows
+template <int NW_, int HT_ = 4> struct ShapeX {
   static_assert(NW_ == 4 || NW_ == 8, "4- or 8-wave tiles");
+  static_assert(HT_ == 4 || HT_ == 8, "hidden layers of 64 or 128 features");
   static constexpr int L = 2, UT = 2, NW = NW_;
   static constexpr int D = (L + 1) * (L + 1), NLP = L + 1, U = 16 * UT, EW = NLP * UT;   // EW: 16-feature tiles of an (l, u) weight vector
   static constexpr int SLOTS = 16 * NW;
@@ -44,9 +46,9 @@ template <int NW_> struct ShapeX {
   static constexpr int STG_LD = D * 16 + 4;             // one K-tile of a slot: [lm][16] + pad (16-byte rows, conflict-free b128 writes)
   static constexpr int ENVA = D * U + 4;                // environment row of one centre: [lm][u] + pad
   static constexpr int NP = CgX<L>::NP;
-  // scratch rows (per wave, 1 KiB each): d x0/dd 4 | w0 EW | per layer: omega EW, hidden layers 1..MD 4 each, u 4, V_in D*UT  (fused_lx_rows.h; MD = latent MLP depth)
-  using R = RowsX;
-  static_assert(R::EW == EW && R::NV == D * UT, "row map of this shape");
+  // scratch rows (per wave, 1 KiB each): d x0/dd 4 | w0 EW | per layer: omega EW, hidden layers 1..MD HT each, u 4, V_in D*UT  (fused_lx_rows.h; MD = latent MLP depth)
+  using R = std::conditional_t<HT_ == 4, RowsX, RowsXM>;
+  static_assert(R::EW == EW && R::NV == D * UT && R::HR == HT_ && R::UR == 4, "row map of this shape");
   static constexpr int R_DX0 = R::R_DX0, R_W0 = R::R_W0, O_OM = R::O_OM;
   __host__ __device__ static constexpr int O_Z(int h) { return R::O_Z(h); }
   __host__ __device__ static constexpr int O_U(int MD) { return R::O_U(MD); }
@@ -180,9 +182,11 @@ enum { PX_GEOM = 0, PX_EMB, PX_ENV, PX_TP, PX_LAT, PX_MIX, PX_OUT, PX_BLAT, PX_B
 // every MD-dependent piece below is `if constexpr`, and the MD = 2 instances are what they were before the parameter existed.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 only, built in fused_lx_r.o).
 // NW: waves per workgroup = 16-slot groups of a tile.  4: one wave per SIMD, the edge tensor parked in AGPRs.  8: two waves per SIMD, 256 registers each, no park
 // (compiled with AHIP_NO_ACC_PARK in an object of its own: fused_lx_w.o), one staging buffer; (MD, RD) = (2, 1), not profiled.
-template <int NW, int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1>
+// HT: 16-feature tiles of one hidden layer of the latent MLP: 4, or 8 for MLP width 65..128 zero-padded to 128 (f16x2, 4-wave tiles, read-out depth 1, not profiled; built in
+// fused_lx_m.o).  Only the hidden vectors and their saved rows grow (as in k_fused: template parameter WT); the LDS is that of HT = 4.
+template <int NW, int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1, int HT = 4>
 __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
-  using S = ShapeX<NW>;
+  using S = ShapeX<NW, HT>;
   using LdsT = LdsX<NW>;
   constexpr int L = S::L, UT = S::UT;
   static_assert(NW == 4 || (MD == 2 && RD == 1 && !PROF), "8-wave tiles: MLP depth 2, read-out depth 1, not profiled");
@@ -193,7 +197,13 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
   static_assert(RD == 1 || (RD == 2 && AR == 3 && !PROF), "read-out depth 2: f16x2 instances only, not profiled");
   // The last model layer keeps its latent-MLP rows in the staging tile: the last hidden layer in images ZIMG .. ZIMG + 3, the one below it (MD >= 2) in images 0..3.
   // A wave's slots hold 9 images; depth 3 would need 12, so the silu' rows of its hidden layer 1 go to the per-wave scratch like a non-last layer's.
-  constexpr int ZIMG = MD == 1 ? 0 : 4;
+  // HT = 8: the 8 images of the last hidden layer fill the slot (images 0..7 of 9); every hidden layer below it goes to the scratch rows, in the last model layer too.
+  constexpr int ZIMG = (MD == 1 || HT == 8) ? 0 : 4;
+  static_assert(HT == 4 || (HT == 8 && NW == 4 && AR == 3 && RD == 1 && !PROF), "MLP width 128: f16x2 instances on 4-wave tiles, read-out depth 1, not profiled");
+  static_assert(HT <= D, "the last hidden layer's images fit a staging slot");
+  // every linear whose shape depends on HT consumes whole rings of the weight stream: the ring phases of the mixing rows are those of HT = 4
+  static_assert(lin_frags_h(4 + UT, HT) % RINGH == 0 && lin_frags_h(HT, HT) % RINGH == 0 && lin_frags_h(HT, 4) % RINGH == 0 && lin_frags_h(4, HT) % RINGH == 0 &&
+                    lin_frags_h(HT, 4 + UT) % RINGH == 0, "the weight ring stays in phase");
   // last-layer rows in LDS (LdsX::rowsl, stage[0] images): LDS rows [0, NOML) = omega l >= 1, [NOML, NLROW) = the first NVL rows of the input tensor
   constexpr int NLROW = LdsT::NLROW, NSTG = LdsT::NSTG, NOML = L * UT, NVL = (NLROW - NOML) < D * UT ? (NLROW - NOML) : D * UT;
   static_assert(NOML <= NLROW, "omega rows of the last layer fit the LDS rows");
@@ -398,12 +408,26 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
       // latent MLP on [x, scalars]
 #ifndef ABL_NO_LAT
       {
-        f32x4 cat[4 + UT], z[4], z2[4];
+        f32x4 cat[4 + UT], z[HT], z2[HT];
 #pragma unroll
         for (int t = 0; t < 4; ++t) cat[t] = x[t];
 #pragma unroll
         for (int t = 0; t < UT; ++t) cat[4 + t] = sc[t];
-        if constexpr (MD == 2) {
+        if constexpr (HT == 8) {
+          // 128-wide hidden layers: 1 .. MD - 1 save silu' rows to scratch in every model layer; the last saves its raw z rows -- in the last model layer as images 0..7 of the
+          // wave's own slots of stage[0].  The chain ping-pongs z / z2 and ends in z2 for MD = 2, in z otherwise.
+          if constexpr (MD == 1) {
+            if (last) lx_lin<AR, 4 + UT, HT, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveZL{STQ(0), ZIMG});
+            else lx_lin<AR, 4 + UT, HT, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveZ{SB, RL + S::O_Z(1), v16});
+          } else {
+            lx_lin<AR, 4 + UT, HT, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveD{SB, RL + S::O_Z(1), v16});
+            if constexpr (MD == 3) lx_lin<AR, HT, HT, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveD{SB, RL + S::O_Z(2), v16});
+            f32x4 (&zi)[HT] = MD == 3 ? z2 : z;
+            f32x4 (&zo)[HT] = MD == 3 ? z : z2;
+            if (last) lx_lin<AR, HT, HT, false>(WB, wp, zi, zo, v16, ring, EpiSiluSaveZL{STQ(0), ZIMG});
+            else lx_lin<AR, HT, HT, false>(WB, wp, zi, zo, v16, ring, EpiSiluSaveZ{SB, RL + S::O_Z(MD), v16});
+          }
+        } else if constexpr (MD == 2) {
           if (last) {          // the last layer's rows: images 0..3 / 4..7 of the wave's own slots of stage[0] (idle until this layer's backward tensor product)
             lx_lin<AR, 4 + UT, 4, false>(WB, wp, cat, z, v16, ring, EpiSiluSaveDL{STQ(0), 0});
             if constexpr (SAVEZ) lx_lin<AR, 4, 4, false>(WB, wp, z, z2, v16, ring, EpiSiluSaveZL{STQ(0), 4});
@@ -429,11 +453,11 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
             lx_lin<AR, 4, 4, false>(WB, wp, z2, z, v16, ring, EpiSiluSaveZ{SB, RL + S::O_Z(3), v16});
           }
         }
-        f32x4 (&zl)[4] = MD == 2 ? z2 : z;              // output of the last hidden layer
+        f32x4 (&zl)[HT] = MD == 2 ? z2 : z;             // output of the last hidden layer
         const float ra = lds.res[kk][0], rbf = lds.res[kk][1] * fc;
         f32x4 xn[4];
-        if constexpr (SAVEZ) lx_lin<AR, 4, 4, false>(WB, wp, zl, xn, v16, ring, EpiResidualNS<4>{x, ra, rbf});
-        else lx_lin<AR, 4, 4, false>(WB, wp, zl, xn, v16, ring, EpiResidual<4>{{SB, RL + S::O_U(MD), v16}, x, ra, rbf});
+        if constexpr (SAVEZ) lx_lin<AR, HT, 4, false>(WB, wp, zl, xn, v16, ring, EpiResidualNS<4>{x, ra, rbf});
+        else lx_lin<AR, HT, 4, false>(WB, wp, zl, xn, v16, ring, EpiResidual<4>{{SB, RL + S::O_U(MD), v16}, x, ra, rbf});
 #pragma unroll
         for (int t = 0; t < 4; ++t) x[t] = xn[t];
       }
@@ -454,7 +478,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
     // ---------------- read-out ----------------
     // saved rows are requested well ahead of their first use all through the backward pass (their round trip is an L2 miss:
     // 1-2 us, and with one wave per SIMD nothing else covers it): u and silu'(z2) of the last layer under the read-out MFMAs
-    f32x4 upre[4], zt[4], w0pre[L * UT];
+    f32x4 upre[4], zt[HT], w0pre[L * UT];
     if constexpr (!SAVEZ) load_rows<4>(SB, S::R_LAYER(NL - 1, MD) + S::O_U(MD), upre, v16);
     __builtin_amdgcn_sched_barrier(0);
     f32x4 zr[2];
@@ -511,7 +535,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
       lx_lin<AR, 2, 4, false>(WB, wp, dzr, dx, v16, ring, EpiNone{});
     }
 #pragma unroll
-    for (int t = 0; t < 4; ++t) zt[t] = stg_load(STQ(0), ZIMG + t);         // the last layer's last hidden layer rows, from the staging tile
+    for (int t = 0; t < HT; ++t) zt[t] = stg_load(STQ(0), ZIMG + t);        // the last layer's last hidden layer rows, from the staging tile
     float dfc_part = 0.f;
     float dY[D];
 #pragma unroll
@@ -524,20 +548,20 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
       const int RL = S::R_LAYER(kk, MD);
       f32x4 ds[UT];
       {
-        f32x4 du[4], dh[4];
-        f32x4 rows1[4];          // silu' of the hidden layer below the last (MD >= 2): first used one linear from here
+        f32x4 du[HT], dh[HT];
+        f32x4 rows1[HT];         // silu' of the hidden layer below the last (MD >= 2): first used one linear from here
         if constexpr (MD >= 2) {
-          if (last) {
+          if (HT == 4 && last) {   // (HT = 8: in scratch in every model layer)
 #pragma unroll
             for (int t = 0; t < 4; ++t) rows1[t] = stg_load(STQ(0), t);
-          } else load_rows<4>(SB, RL + S::O_Z(MD - 1), rows1, v16);
+          } else load_rows<HT>(SB, RL + S::O_Z(MD - 1), rows1, v16);
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (SAVEZ) {
           // the u rows are not saved (fused.hip: SAVEZ): <u, g> falls out of the epilogue of the first backward linear, fed with the unscaled gradient
           const float ra = lds.res[kk][0], rb = lds.res[kk][1];
           float ug = 0.f;
-          lx_lin<AR, 4, 4, false>(WB, wp, dx, dh, v16, ring, EpiMulSiluZ<4>{zt, rb * fc, ug});
+          lx_lin<AR, 4, HT, false>(WB, wp, dx, dh, v16, ring, EpiMulSiluZ<HT>{zt, rb * fc, ug});
 #pragma unroll
           for (int t = 0; t < 4; ++t) dx[t] = ra * dx[t];
           dfc_part += rb * ug;
@@ -557,18 +581,18 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
         // down the hidden layers: g_{h-1} = (g_h W_h^T) * silu'(z_{h-1}), then dcat = g_1 W_0^T
         f32x4 dcat[4 + UT];
         if constexpr (MD == 2) {
-          lx_lin<AR, 4, 4, false>(WB, wp, dh, du, v16, ring, EpiMulRows<4>{rows1});
-          lx_lin<AR, 4, 4 + UT, false>(WB, wp, du, dcat, v16, ring, EpiNone{});
+          lx_lin<AR, HT, HT, false>(WB, wp, dh, du, v16, ring, EpiMulRows<HT>{rows1});
+          lx_lin<AR, HT, 4 + UT, false>(WB, wp, du, dcat, v16, ring, EpiNone{});
         } else if constexpr (MD == 1) {
-          lx_lin<AR, 4, 4 + UT, false>(WB, wp, dh, dcat, v16, ring, EpiNone{});
+          lx_lin<AR, HT, 4 + UT, false>(WB, wp, dh, dcat, v16, ring, EpiNone{});
         } else {
           // silu' of hidden layer 1 (scratch in every model layer): requested one linear ahead, after the stage reads of rows1 above
-          f32x4 rows0[4];
-          load_rows<4>(SB, RL + S::O_Z(1), rows0, v16);
+          f32x4 rows0[HT];
+          load_rows<HT>(SB, RL + S::O_Z(1), rows0, v16);
           __builtin_amdgcn_sched_barrier(0);
-          lx_lin<AR, 4, 4, false>(WB, wp, dh, du, v16, ring, EpiMulRows<4>{rows1});
-          lx_lin<AR, 4, 4, false>(WB, wp, du, dh, v16, ring, EpiMulRows<4>{rows0});
-          lx_lin<AR, 4, 4 + UT, false>(WB, wp, dh, dcat, v16, ring, EpiNone{});
+          lx_lin<AR, HT, HT, false>(WB, wp, dh, du, v16, ring, EpiMulRows<HT>{rows1});
+          lx_lin<AR, HT, HT, false>(WB, wp, du, dh, v16, ring, EpiMulRows<HT>{rows0});
+          lx_lin<AR, HT, 4 + UT, false>(WB, wp, dh, dcat, v16, ring, EpiNone{});
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) dx[t] += dcat[t];
@@ -690,7 +714,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
         // next iteration's u / silu'(z2) rows (or the l >= 1 embedding weights for the last step) under this linear
         if (kk > 0) {
           if constexpr (!SAVEZ) load_rows<4>(SB, S::R_LAYER(kk - 1, MD) + S::O_U(MD), upre, v16);
-          load_rows<4>(SB, S::R_LAYER(kk - 1, MD) + S::O_Z(MD), zt, v16);
+          load_rows<HT>(SB, S::R_LAYER(kk - 1, MD) + S::O_Z(MD), zt, v16);
         } else load_rows<L * UT>(SB, S::R_W0 + UT, w0pre, v16);
         __builtin_amdgcn_sched_barrier(0);
         lx_lin<AR, EW, 4, true>(WB, wp, dom, dx, v16, ring, EpiNone{});
@@ -814,14 +838,21 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
 }
 
 // ---------------------------------------------------------------------------- host side
-// This file is compiled three times (Makefile): AHIP_LX_PART 0 = the host side and the 4-wave read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone
-// (fused_lx_r.o), 2 = the 8-wave instances alone, with AHIP_NO_ACC_PARK (fused_lx_w.o)
+// This file is compiled four times (Makefile): AHIP_LX_PART 0 = the host side and the 4-wave read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone
+// (fused_lx_r.o), 2 = the 8-wave instances alone, with AHIP_NO_ACC_PARK (fused_lx_w.o), 3 = the MLP-width-128 instances alone (fused_lx_m.o)
 #ifndef AHIP_LX_PART
 #define AHIP_LX_PART 0
 #endif
 void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
 void fusedlx_launch_w8(int nl, int ar, int var, int grid, hipStream_t s, const FusedLxArgs &A);
-#if AHIP_LX_PART == 1
+void fusedlx_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
+#if AHIP_LX_PART == 3
+void fusedlx_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // HT = 8: f16x2 only, 4-wave tiles, read-out depth 1, plain and per-atom virial, not profiled
+  dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    hipLaunchKernelGGL((k_fused_lx<4, nl, false, 3, v == VAR_VA, md, 1, 8>), dim3(grid), dim3(4 * 64), 0, s, A);
+  }, nl, var, md);
+}
+#elif AHIP_LX_PART == 1
 void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // f16x2 only, plain and per-atom virial, not profiled
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
     hipLaunchKernelGGL((k_fused_lx<4, nl, false, 3, v == VAR_VA, md, 2>), dim3(grid), dim3(4 * 64), 0, s, A);
@@ -846,7 +877,8 @@ static_assert(LX_MAXNL == 3, "fused_shapes.h: 1..3 layers");
 static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, Arith arith) {
   using S = ShapeX<4>;          // (the stream does not depend on the tile shape)
   constexpr int L = S::L, U = S::U, D = S::D;
-  const int NL = h.num_layers, MD = h.mlp_depth;      // latent MLP: lat.w0 ([x, scalars] -> 64), lat.w1 .. lat.w{MD-1} (64 -> 64), output linear lat.w{MD}
+  const int NL = h.num_layers, MD = h.mlp_depth;      // latent MLP: lat.w0 ([x, scalars] -> W), lat.w1 .. lat.w{MD-1} (W -> W), output linear lat.w{MD} (W -> 64)
+  const int W = h.mlp_width;                          // hidden width at the kernel's shape: 64 or 128 (fused_shapes.h: FUSED_WF, FUSED_WF2)
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
   auto frag = [&](const double *W, int K, int N, int ldw) {
@@ -874,8 +906,8 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
   for (int k = 0; k < NL; ++k) {
     const std::string lk = "l" + std::to_string(k + 1);
     fwd(T_(lk + ".env"), 64, U * (L + 1));
-    fwd(T_(lk + ".lat.w0"), 64 + U, 64);
-    for (int hl = 1; hl <= MD; ++hl) fwd(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64);
+    fwd(T_(lk + ".lat.w0"), 64 + U, W);
+    for (int hl = 1; hl <= MD; ++hl) fwd(T_(lk + ".lat.w" + std::to_string(hl)), W, hl < MD ? W : 64);
     if (k < NL - 1) {
       const double *mx = T_(lk + ".mix");            // [L+1][U][U]; block l serves its 2l+1 components
       for (int lm = 0; lm < D; ++lm) mixfrag(mx + (size_t)l_of_lm(lm) * U * U, lm, false);
@@ -889,8 +921,8 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
   bwd(T_("out.w0"), 64, 32);
   for (int k = NL - 1; k >= 0; --k) {
     const std::string lk = "l" + std::to_string(k + 1);
-    for (int hl = MD; hl >= 1; --hl) bwd(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64);
-    bwd(T_(lk + ".lat.w0"), 64 + U, 64);
+    for (int hl = MD; hl >= 1; --hl) bwd(T_(lk + ".lat.w" + std::to_string(hl)), W, hl < MD ? W : 64);
+    bwd(T_(lk + ".lat.w0"), 64 + U, W);
     if (k < NL - 1) {
       const double *mx = T_(lk + ".mix");
       for (int lm = 0; lm < D; ++lm) mixfrag(mx + (size_t)l_of_lm(lm) * U * U, lm, true);
@@ -905,9 +937,13 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
 bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
   const int max_slots = lx_max_tile_slots(m, FusedFamily::lx32);
   if (!lx_list_fits(m, why, max_slots)) return false;
-  FusedLxState &st = lx_prepare<ShapeX<4>>(m, m.fusedlx_state, nullptr, false, lx_stream, max_slots > LX_TILE_SLOTS ? 8 : 4);
+  const bool w128 = fused_WF(m.hm) == FUSED_WF2;       // MLP width 65..128: the HT = 8 instances, whose row map sizes the per-wave scratch
+  FusedLxState &st = w128 ? lx_prepare<ShapeX<4, 8>>(m, m.fusedlx_state, nullptr, false, lx_stream, 4)
+                          : lx_prepare<ShapeX<4>>(m, m.fusedlx_state, nullptr, false, lx_stream, max_slots > LX_TILE_SLOTS ? 8 : 4);
   static_assert(PX_N == LX_NPHASE, "profile phases");
   if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
+  if (st.ht != 4 && !(st.ht == 8 && st.arith == AR_F16X2 && st.rd == 1 && max_slots == LX_TILE_SLOTS))
+    throw UnsupportedError("wide fused kernels: MLP width 65..128 has f16x2 instances on 64-slot tiles with read-out depth 1 only");      // (likewise; lx_max_tile_slots keeps wide_tile=auto at 64 slots)
   // Tile shape (4 waves / 64 slots or 8 waves / 128 slots, option wide_tile=auto) from the largest degree of THIS list, as k_fused does (fused.hip: fused_run): on the
   // host where it is known or bounded by the list's rows, else both shapes are launched and the device word decides (nw = 0)
   int nw = 4;
@@ -918,6 +954,7 @@ bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
   }
   lx_run<ShapeX<4>, ShapeX<8>>(m, a, st, "fused_lx", [&](const FusedLxArgs &A, int grid, int var, int shape) {
     if (shape == 8) { fusedlx_launch_w8(A.NL, st.arith, var, grid, a.stream, A); return; }      // fused_lx_w.o
+    if (st.ht == 8) { fusedlx_launch_m(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_m.o
     if (st.rd == 2) { fusedlx_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_r.o
     dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
       if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)
