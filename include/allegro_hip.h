@@ -64,7 +64,9 @@ int ahip_model_meta(const ahip_model *m, double *r_max, int *num_types, const ch
  *                                                 and the per-atom edge counts allow it).  Fused shapes: l_max 1 or 2, up to 64 tensor features, up to 64
  *                                                 scalars, read-out width up to 32, MLP width up to 64 on every fused kernel and arithmetic, 65..128 on the
  *                                                 kernels for up to 32 tensor features (zero-padded to 128: f16x2 arithmetic with the tabulated two-body
- *                                                 embedding, read-out depth 1); narrower models run zero-padded
+ *                                                 embedding, read-out depth 1); read-out width 33..64 on every fused kernel (zero-padded to 64: f16x2
+ *                                                 arithmetic with the tabulated two-body embedding, MLP width up to 64, read-out depth 1; wider than 64:
+ *                                                 the layer-at-a-time kernels); narrower models run zero-padded
  *   "precision" = "model" | "float64"            compute dtype; float64 is the debug/parity build
  *   "chunk_edges" = "<n>"                        max edges processed per pass (workspace bound)
  *   "reserve_wgs" = "<n>"                        half-CU workgroup slots the persistent fused kernels leave unoccupied, so that
@@ -95,7 +97,7 @@ int ahip_model_meta(const ahip_model *m, double *r_max, int *num_types, const ch
  *                                                 shape of 128 slots (8 waves) as the l_max = 1 kernel does, so centres with 65..128 edges stay on the fused kernel and only
  *                                                 centres above 128 are heavy (the one-in-eight rule of "dense_centres" counts against 128 as well).  The second shape exists
  *                                                 for MLP depth 2, MLP width up to 64 and read-out depth 1 on the f32 and f16x2 arithmetics; for every other model (64 tensor features,
- *                                                 l_max = 1, other depths, MLP width 65..128) "auto" behaves as "64" and is not an error.  Measured on one MI355X, 108 000-atom
+ *                                                 l_max = 1, other depths, MLP width 65..128, read-out width 33..64) "auto" behaves as "64" and is not an error.  Measured on one MI355X, 108 000-atom
  *                                                 fcc box with 78 edges per centre, 3 layers, 32 tensor features (tools/wide_tile_cost.py): 79.5 ms per evaluation
  *                                                 with "auto" against 265 ms with "64" (every centre heavy), the latter equal to the release before the option.  Not
  *                                                 measured on other lists, which is why the default stays "64".

@@ -123,7 +123,7 @@ struct Model {
   ArithState arith;                         // option fused_arith (auto | f32 | f16x2 | bf16x3 | tf32eq) and what auto has decided so far: arith_policy.h
   DevBuf b_chk;                             // self-check: two force arrays + the 2-word reduction
   // A model narrower than a fused kernel's fixed widths runs on it zero-padded (round 6; model_io.h: pad_host_model): S <= 64 scalars, MLP width <= 64 (65..128: padded
-  // to the second hidden width 128 of k_fused / k_fused_lx, fused_shapes.h: fused_WF), read-out width <= 32, U <= 32 tensor features on k_fused / k_fused_lx, <= 64 on k_fused_lx2 (an l_max = 1 model with 33..64 features lifted to l_max = 2 as well:
+  // to the second hidden width 128 of k_fused / k_fused_lx, fused_shapes.h: fused_WF), read-out width <= 32 (33..64: padded to the second read-out width 64, fused_RF), U <= 32 tensor features on k_fused / k_fused_lx, <= 64 on k_fused_lx2 (an l_max = 1 model with 33..64 features lifted to l_max = 2 as well:
   // fused_shapes.h).  hm stays the model as loaded (layer-at-a-time kernels, metadata).
   HostModel hm_fused;
   bool hm_fused_ready = false;
@@ -292,9 +292,10 @@ inline const HostModel &fused_host_model(Model &m) {
   const HostModel &h = m.hm;
   const FusedFamily cls = fused_shape_class(h);
   const int WF = fused_WF(h);                // hidden width of the latent MLP: 64, or 128 for a model with mlp_width 65..128 (fused_shapes.h)
-  if (m.active.empty() && fused_shape_exact(h, cls, WF)) return h;
+  const int RF = fused_RF(h);                // width of the read-out MLP: 32, or 64 for a model with readout_width 33..64
+  if (m.active.empty() && fused_shape_exact(h, cls, WF, RF)) return h;
   if (!m.hm_fused_ready) {
-    m.hm_fused = m.active.empty() ? fused_shaped_model(h, cls, WF) : fused_shaped_model(subset_host_model(h, m.active), cls, WF);
+    m.hm_fused = m.active.empty() ? fused_shaped_model(h, cls, WF, RF) : fused_shaped_model(subset_host_model(h, m.active), cls, WF, RF);
     m.hm_fused_ready = true;
   }
   return m.hm_fused;
@@ -317,7 +318,7 @@ inline Arith resolve_arith(const Model &m, bool wide) {
 // skipped by the kernel, evaluated by heavy_generic) and against which the one-in-eight give-up rule counts.  128 under option wide_tile=auto where the 8-wave shape
 // of k_fused_lx exists for the model's arithmetic and depths, else 64.
 inline int lx_max_tile_slots(const Model &m, FusedFamily fam) {
-  return lx_tile_slots(m.opt_wide_tile == Model::WideTile::Auto && fused_has_wide_tile(fam, resolve_arith(m, true), m.hm.mlp_depth, m.hm.readout_depth, fused_WF(m.hm)));
+  return lx_tile_slots(m.opt_wide_tile == Model::WideTile::Auto && fused_has_wide_tile(fam, resolve_arith(m, true), m.hm.mlp_depth, m.hm.readout_depth, fused_WF(m.hm), fused_RF(m.hm)));
 }
 // the model computes in float64 (option precision, or the model file's own dtype): layer-at-a-time kernels only
 inline bool model_runs_f64(const Model &m) { return m.opt_precision == Model::Precision::Float64 || m.hm.is_f64(); }

@@ -25,7 +25,7 @@
 //            only for model files that set allow_tf32).
 //
 // Supported model shape (fused_shapes.h decides; others run the wide kernels or the generic path): l_max = 1, up to 32 tensor features (33..64: k_fused_lx2 on the lifted
-// model), up to 64 scalars, MLP width up to 64 (65..128: the WT = 8 instances, zero-padded to 128), read-out width up to 32 (narrower than the kernel's fixed 32 / 64 / 64 or 128 / 32: zero-padded by the host, model_io.cpp: pad_host_model),
+// model), up to 64 scalars, MLP width up to 64 (65..128: the WT = 8 instances, zero-padded to 128), read-out width up to 32 (33..64: the RT = 4 instances, zero-padded to 64; narrower than the kernel's fixed 32 / 64 / 64 or 128 / 32 or 64: zero-padded by the host, model_io.cpp: pad_host_model),
 // MLPs of 2 hidden layers x 64 (1 or 3 hidden layers on the f16x2 instances with the tabulated two-body embedding: template parameter MD, round 5),
 // read-out 1 x 32 (2 x 32 on the same f16x2 instances: template parameter RD), <= 3 layers, <= 16 types; any number of Bessel functions and any cutoff-polynomial order (the radial basis only
 // enters through the tabulated two-body embedding; fused_tb=mlp needs 8).  Reference graph:
@@ -49,8 +49,8 @@
 #include "fused_rows.h"
 #include "prims.h"
 
-// This file is compiled in five parts (Makefile; same options, divides the build time): AHIP_FUSED_PART 0 = the host side + the f32-input MFMA
-// instances of k_fused, AHIP_FUSED_PART 1 = the bf16-split instances, 2 = the f16x2 instances, 3 = their read-out-depth-2 twins, 4 = their MLP-width-128 twins.  (Rounds 2-3 gave part 1 other compiler options because it computed wrong
+// This file is compiled in six parts (Makefile; same options, divides the build time): AHIP_FUSED_PART 0 = the host side + the f32-input MFMA
+// instances of k_fused, AHIP_FUSED_PART 1 = the bf16-split instances, 2 = the f16x2 instances, 3 = their read-out-depth-2 twins, 4 = their MLP-width-128 twins, 5 = their read-out-width-64 twins.  (Rounds 2-3 gave part 1 other compiler options because it computed wrong
 // forces with part 0's: that was the store-data hazard described at fused_common.h: bstore, not the options.)
 #ifndef AHIP_FUSED_PART
 #define AHIP_FUSED_PART 0
@@ -102,7 +102,7 @@ struct FusedArgs {
   double *vatom;                          // [nall][9] per-atom virial (the VA instances only)
 };
 
-template <int NW, int NL = MAXNL> struct __attribute__((aligned(16))) Lds {
+template <int NW, int NL = MAXNL, int RT = 2> struct __attribute__((aligned(16))) Lds {
   static constexpr int SLOTS = 16 * NW;
   static constexpr int MAXA = NW == 4 ? 6 : 12;   // centre atoms per tile (LDS budget)
   float stage[SLOTS * STG_LD];
@@ -117,7 +117,7 @@ template <int NW, int NL = MAXNL> struct __attribute__((aligned(16))) Lds {
   float scale[16], shift[16];             // per-type energy scale / shift
   float res[NL][2];                       // residual update coefficients per layer
   int chunk[2];                           // first tile of the current / next claimed chunk
-  float wo1[32];                          // the read-out's final 32 -> 1 vector: read in every tile (a global load there drained the vector-memory queue behind `za`)
+  float wo1[RT == 2 ? 32 : 4]; __device__ __forceinline__ float *wo1v() { if constexpr (RT == 2) return wo1; else return tp[NL - 1] + 64; }      // the read-out's final 32 -> 1 vector: read in every tile (a global load there drained the vector-memory queue behind `za`).  RT = 4: the 64 -> 1 vector lives in tp[NL - 1][64 .. 127] instead, the last layer's path weights of the paths with l = 1 output, which no tile reads (the last layer computes its scalar outputs only); another 128 B here would put the 4-wave, 3-layer instance at 81 936 B, 16 B over half a CU's LDS: one workgroup per CU instead of two
 };
 
 // ---------------------------------------------------------------------------- device helpers
@@ -256,7 +256,7 @@ template <int RB> __device__ __forceinline__ void ring_prime_b(__amdgpu_buffer_r
 
 // Per-centre sum of the staged tile: dst[a][f] = scale * sum_{slots of a} stage[slot][f], f < 128.
 // 128 features x (NW/2) atoms per pass; 4 independent accumulators keep 4 LDS reads in flight.
-template <int NW, int NL> __device__ __forceinline__ void reduce_stage(const Lds<NW, NL> &lds, const int *aoff, float *dst, int na, float scale, int tid) {
+template <int NW, int NL, int RT> __device__ __forceinline__ void reduce_stage(const Lds<NW, NL, RT> &lds, const int *aoff, float *dst, int na, float scale, int tid) {
   const int fidx = tid & 127;
   for (int a = tid >> 7; a < na; a += NW / 2) {
     const int s0 = aoff[a], s1 = aoff[a + 1];
@@ -392,8 +392,8 @@ __device__ __forceinline__ void tile_fetch(const FusedArgs &A, const TileBounds 
 
 // VA: also the per-atom virial (output "atomic_virial"); instances launched only while that output is registered, so the default ones keep their code.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 + table only, built in fused_hr.o)
 // WT: 16-feature tiles of one hidden layer of the latent MLP: 4 (MLP width <= 64), or 8 (65..128, zero-padded to 128: f16x2 + table, read-out depth 1, not profiled; built in fused_hm.o).
-// Only the hidden vectors z, z2 / dh, du and their saved rows grow: no LDS array, table, latent x or environment row depends on it, so the LDS (two workgroups per CU at NW = 4) is the same.
-template <int NW, bool PROF, int AR, bool TBT, int NLT, int MD = 2, bool VA = false, int RD = 1, int WT = 4>
+// Only the hidden vectors z, z2 / dh, du and their saved rows grow: no LDS array, table, latent x or environment row depends on it, so the LDS (two workgroups per CU at NW = 4) is the same.  RT: 16-feature tiles of the read-out MLP's hidden layer: 2 (read-out width <= 32), or 4 (33..64, zero-padded to 64: f16x2 + table, WT = 4, read-out depth 1, not profiled; built in fused_hq.o): only the read-out vectors (zr, dzr) and the final R -> 1 vector in LDS (Lds::wo1v: inside the path-weight table, no byte more) grow, the two folded linears of the last layer become 64 x 64 blocks like every other linear of a WT = 4 instance, and the row maps and the per-wave scratch do not depend on it (the f16x2 instances save no z (W3 Wr) rows).
+template <int NW, bool PROF, int AR, bool TBT, int NLT, int MD = 2, bool VA = false, int RD = 1, int WT = 4, int RT = 2>
 __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   constexpr int NTHREADS = NW * 64, MAXA = Lds<NW>::MAXA;
   // f16x2 instances (round 5): the last hidden layer of the latent MLP saves its RAW pre-activation rows and the layer's output rows u are not saved at all: the backward
@@ -414,9 +414,11 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   static_assert(lin_frags_h(6, WT) % RINGH == 0 && lin_frags_h(WT, WT) % RINGH == 0 && lin_frags_h(WT, 4) % RINGH == 0 && lin_frags_h(4, WT) % RINGH == 0 && lin_frags_h(WT, 6) % RINGH == 0 &&
                     lin_frags_h(WT, 2) % RINGH == 0 && lin_frags_h(2, WT) % RINGH == 0,
                 "the weight ring stays in phase");
+  static_assert(RT == 2 || (RT == 4 && AR == 3 && TBT && !PROF && RD == 1 && WT == 4), "read-out width 64: f16x2 instances with the two-body table only, MLP width 64, read-out depth 1, not profiled");
+  static_assert(lin_frags_h(WT, RT) % RINGH == 0 && lin_frags_h(4, RT) % RINGH == 0 && lin_frags_h(RT, 4) % RINGH == 0 && lin_frags_h(RT, WT) % RINGH == 0, "the weight ring stays in phase");
   static_assert(MD >= 1 && MD <= 3 && (MD == 2 || (AR == 3 && TBT)), "latent MLP depth 1 / 3: f16x2 instances with the two-body table only");
   static_assert(RD == 1 || (RD == 2 && AR == 3 && TBT && !PROF), "read-out depth 2: f16x2 instances with the two-body table only, not profiled");
-  __shared__ Lds<NW, NLT> lds;
+  __shared__ Lds<NW, NLT, RT> lds;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
   const int v16 = lane * 16;
   // wave-uniform buffer descriptors (made provably uniform with readfirstlane)
@@ -431,6 +433,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   const float *__restrict__ Wb = A.wbase;
   for (int k = tid; k < A.NL * 160; k += NTHREADS) {      // path weights with their CG constants folded in
     const int pth = (k % 160) / 32;
+    if (RT != 2 && k >= (NLT - 1) * 160 + 64) continue;   // (RT = 4: the unread tail of the last layer's rows holds the read-out's final vector, Lds::wo1v)
     lds.tp[k / 160][k % 160] = Wb[A.o_tpl + k] * (pth == 1 ? C_P1 : pth == 4 ? C_P4 : 1.f);
   }
   const int ntiles = *A.ntiles;
@@ -457,7 +460,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
   if (A.T <= 4 && tid < A.T * A.T) lds.rc[tid] = (float)A.rcut[tid];
   if (tid < A.T) { lds.scale[tid] = Wb[A.o_scale + tid]; lds.shift[tid] = Wb[A.o_shift + tid]; }
   if (tid < 2 * A.NL) lds.res[tid >> 1][tid & 1] = Wb[A.o_res[tid >> 1] + (tid & 1)];
-  if (tid >= 64 && tid < 96) lds.wo1[tid - 64] = Wb[A.o_out1 + tid - 64];
+  if constexpr (RT == 2) { if (tid >= 64 && tid < 96) lds.wo1[tid - 64] = Wb[A.o_out1 + tid - 64]; }
+  else { if (tid >= 64 && tid < 64 + 16 * RT) lds.wo1v()[tid - 64] = Wb[A.o_out1 + tid - 64]; }
 
   const int s = wave * 16 + j;                 // this lane's edge slot
   float *const st = lds.stage + s * STG_LD;
@@ -586,7 +590,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     PHASE(PH_EMB);
 
     // ---------------- layers, forward ----------------
-    f32x4 zr[2];               // read-out pre-activations: produced by the last layer (see its latent MLP)
+    f32x4 zr[RT];              // read-out pre-activations: produced by the last layer (see its latent MLP)
 #pragma unroll
     for (int kk = 0; kk < NL; ++kk) {
       const bool last = (kk == NL - 1);
@@ -706,12 +710,22 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
           // Last layer: its new latent x' = ra x + rb fc (z2 W3) feeds nothing but the read-out's first linear, and no non-linearity
           // sits between the two, so  x' Wr = ra (x Wr) + rb fc (z2 (W3 Wr))  with W3 Wr multiplied out by the host in float64: two
           // 64 -> 32 linears instead of a 64 -> 64 and a 64 -> 32 one, here and (transposed) in the backward pass: 64 of the tile's
-          // 1472 MFMAs per wave and two saved rows less.  z2 first: it dies there.
-          f32x4 za[2], up[2];
-          if constexpr (SAVEZ) lin<AR, WT, 2, false, 0>(WB, wp, zl, up, v16t, ring, EpiNone{});
-          else lin<AR, WT, 2, false, 0>(WB, wp, zl, up, v16t, ring, EpiSave{SB, RL + OU, v16t});
-          lin<AR, 4, 2, false, 0>(WB, wp, x, za, v16t, ring, EpiNone{});
-          zr[0] = ra * za[0] + rbf * up[0]; zr[1] = ra * za[1] + rbf * up[1];
+          // 1472 MFMAs per wave and two saved rows less.  z2 first: it dies there.  (RT = 4: two 64 -> 64 linears instead of three)
+          if constexpr (RT == 2) {
+            f32x4 za[2], up[2];
+            if constexpr (SAVEZ) lin<AR, WT, 2, false, 0>(WB, wp, zl, up, v16t, ring, EpiNone{});
+            else lin<AR, WT, 2, false, 0>(WB, wp, zl, up, v16t, ring, EpiSave{SB, RL + OU, v16t});
+            lin<AR, 4, 2, false, 0>(WB, wp, x, za, v16t, ring, EpiNone{});
+            zr[0] = ra * za[0] + rbf * up[0]; zr[1] = ra * za[1] + rbf * up[1];
+          } else {
+            // 64 wide, the two terms meet in the accumulators: zr = rbf (z2 (W3 Wr)) out of the first linear's epilogue, then += (ra x) Wr -- no za / up beside zr (32
+            // registers this kernel does not have); x is dead behind this linear (the backward pass has its own dx), so it is scaled in place
+            static_assert(SAVEZ, "read-out width 64: f16x2 instances (no z2 (W3 Wr) rows saved)");
+            lin<AR, WT, RT, false, 0>(WB, wp, zl, zr, v16t, ring, EpiScale{rbf});
+#pragma unroll
+            for (int t = 0; t < 4; ++t) x[t] = ra * x[t];
+            lin<AR, 4, RT, true, 0>(WB, wp, x, zr, v16t, ring, EpiNone{});
+          }
         }
       }
       PHASE(PH_LAT);
@@ -722,25 +736,28 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     // round trip is an L2 miss: ~2 us): u and z2 of the last layer now, under the read-out MFMAs
     f32x4 upre[4], zt[WT], w0h[2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) if (!SAVEZ) upre[t] = bload(SB, v16t, (R_LAYER(NL - 1, MD, WT) + OU + t) * ROW * 4);       // the last layer saved two rows: z2 (W3 Wr)
+    for (int t = 0; t < RT; ++t) if (!SAVEZ) upre[t] = bload(SB, v16t, (R_LAYER(NL - 1, MD, WT) + OU + t) * ROW * 4);      // the last layer saved RT rows: z2 (W3 Wr)
     if (!STGROWS) load_rows<WT>(SB, R_LAYER(NL - 1, MD, WT) + OZL, zt, v16t);
     __builtin_amdgcn_sched_barrier(0);
-    f32x4 zr2[2];              // RD = 2: pre-activations of the read-out's second hidden layer
+    f32x4 zr2[RT];             // RD = 2: pre-activations of the read-out's second hidden layer
     if constexpr (RD == 2) {
-      f32x4 hr[2];
+      f32x4 hr[RT];
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < RT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) hr[t][r] = silu1(zr[t][r]);
-      lin<AR, 2, 2, false, 0>(WB, wp, hr, zr2, v16t, ring, EpiNone{});
+      lin<AR, RT, RT, false, 0>(WB, wp, hr, zr2, v16t, ring, EpiNone{});
     }
-    f32x4 (&zo)[2] = RD == 2 ? zr2 : zr;        // pre-activations of the last hidden layer
-    f32x4 wo1[2];              // the read-out's final 32 -> 1 vector (out.w1, or out.w2 of a depth-2 read-out)
+    f32x4 (&zo)[RT] = RD == 2 ? zr2 : zr;       // pre-activations of the last hidden layer
+    f32x4 wo1[RT];             // the read-out's final R -> 1 vector (out.w1, or out.w2 of a depth-2 read-out)
 #pragma unroll
-    for (int t = 0; t < 2; ++t) wo1[t] = *(const f32x4 *)(lds.wo1 + 16 * t + 4 * g);
+    for (int t = 0; t < RT; ++t) {
+      if constexpr (RT == 2) wo1[t] = *(const f32x4 *)(lds.wo1 + 16 * t + 4 * g);
+      else wo1[t] = *(const f32x4 *)(lds.wo1v() + 16 * t + 4 * g);
+    }
     float eps = 0.f;
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < RT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) eps += silu1(zo[t][r]) * wo1[t][r];
     eps = gsum(eps);
@@ -761,21 +778,28 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     }
     const float deps = valid ? lds.scale[ti] * A.cenv * bsc : 0.f;
     f32x4 dx[4];
-    f32x4 dzr[2];
+    f32x4 dzr[RT];
+    if constexpr (RT != 2) {
+      // the 64-wide vector is not held across the read-out (k_fused sits at 256 registers): read again, through a pointer the optimiser cannot see through
+      const float *wq = lds.wo1v() + 4 * g;
+      asm volatile("" : "+v"(wq));
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < RT; ++t) wo1[t] = *(const f32x4 *)(wq + 16 * t);
+    }
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) dzr[t][r] = deps * wo1[t][r] * dsilu1(zo[t][r]);
     if constexpr (RD == 2) {
       // dzr holds the gradient of zr2: back through out.w1^T (the second half-ring block) and the first hidden layer's SiLU; linear in deps, so the f16x2 scale passes through
-      f32x4 dhr[2];
-      lin<AR, 2, 2, false, 1>(WB, wp, dzr, dhr, v16t, ring, EpiNone{});
+      f32x4 dhr[RT];
+      lin<AR, RT, RT, false, 1>(WB, wp, dzr, dhr, v16t, ring, EpiNone{});
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < RT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) dzr[t][r] = dhr[t][r] * dsilu1(zr[t][r]);
     }
-    lin<AR, 2, 4, false, 0>(WB, wp, dzr, dx, v16t, ring, EpiNone{});               // dzr Wr^T = the gradient w.r.t. x' of the last layer
+    lin<AR, RT, 4, false, 0>(WB, wp, dzr, dx, v16t, ring, EpiNone{});              // dzr Wr^T = the gradient w.r.t. x' of the last layer
     if (STGROWS) {                                                                 // the last layer's rows of its last hidden layer, from the staging tile
 #pragma unroll
       for (int t = 0; t < WT; ++t) zt[t] = stg_load(st + 4 * g, ZQ + t);
@@ -806,7 +830,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
           if constexpr (MD >= 2) { if (!(STGROWS && STG2)) load_rows<WT>(SB, RL + OZL - WT, zt1, v16t); }      // (WT = 8: the staging row holds the last hidden layer alone)
           __builtin_amdgcn_sched_barrier(0);
           float ug = 0.f;
-          lin<AR, 2, WT, false, 0>(WB, wp, dzr, dh, v16t, ring, EpiMulSiluZ<WT>{zt, rb * fc, ug});
+          lin<AR, RT, WT, false, 0>(WB, wp, dzr, dh, v16t, ring, EpiMulSiluZ<WT>{zt, rb * fc, ug});
           dfc_part += rb * ug;
 #pragma unroll
           for (int t = 0; t < 4; ++t) dx[t] = ra * dx[t];
@@ -828,6 +852,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
           if constexpr (!SAVEZ) {
           // last layer (read-out folded in, see the forward pass): upre = the two rows z2 (W3 Wr); the z2 gradient comes straight
           // from dzr through (W3 Wr)^T
+          static_assert(SAVEZ || RT == 2, "the instances that save the z2 (W3 Wr) rows have read-out width 32");
           const float ra = lds.res[kk][0], rb = lds.res[kk][1];
           const f32x4 accv = upre[0] * dzr[0] + upre[1] * dzr[1];
           const float rbfc = rb * fc;
@@ -1161,6 +1186,15 @@ void fused_launch_bf16(int nw, bool prof, int arith, bool tbt, int grid, hipStre
 void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const FusedArgs &A);
 void fused_launch_f16_rd2(int nw, int md, int grid, hipStream_t s, const FusedArgs &A);
 void fused_launch_f16_w128(int nw, int md, int grid, hipStream_t s, const FusedArgs &A);
+void fused_launch_f16_r64(int nw, int md, int grid, hipStream_t s, const FusedArgs &A);
+#if AHIP_FUSED_PART == 5
+// the read-out-width-64 f16x2 instances (fused_hq.o; template parameter RT = 4): two-body table only, MLP width 64, latent MLP depth 1..3, read-out depth 1, plain and per-atom virial, not profiled
+void fused_launch_f16_r64(int nw, int md, int grid, hipStream_t s, const FusedArgs &A) {
+  dispatch<Choices<4, 8>, Choices<1, 2, 3>, Choices<1, 3, 2>, Choices<VAR_VA, VAR_PLAIN>>([&](auto nw, auto nl, auto md, auto var) {
+    hipLaunchKernelGGL((k_fused<nw, false, 3, true, nl, md, var == VAR_VA, 1, 4, 4>), dim3(grid), dim3(nw * 64), 0, s, A);
+  }, nw, A.NL, md, fused_variant(A.vatom, false));
+}
+#endif
 #if AHIP_FUSED_PART == 4
 // the MLP-width-128 f16x2 instances (fused_hm.o; template parameter WT = 8): two-body table only, latent MLP depth 1..3, read-out depth 1, plain and per-atom virial, not profiled
 void fused_launch_f16_w128(int nw, int md, int grid, hipStream_t s, const FusedArgs &A) {
@@ -1210,6 +1244,7 @@ struct FusedState {
   bool tbt = true;             // two-body embedding from the spline table (default) or evaluated as an MLP (option fused_tb=mlp)
   int md = 2;                  // hidden layers of the latent MLP (template parameter MD of k_fused)
   int rd = 1;                  // hidden layers of the read-out MLP (template parameter RD)
+  int rt = 2;                  // 16-feature tiles of the read-out MLP's hidden layer (template parameter RT: 2 = read-out width 32, 4 = 64)
   int wt = 4;                  // 16-feature tiles of a hidden layer of the latent MLP (template parameter WT: 4 = MLP width 64, 8 = 128)
   Arith arith = AR_F32;        // arith_policy.h: resolve_arith (every arithmetic has its k_fused instances)
   DevBuf prof, dbg;
@@ -1280,6 +1315,9 @@ static void fused_prepare(Model &m) {
   st.md = h.mlp_depth;
   st.rd = h.readout_depth;
   st.wt = W / 16;
+  const int RF = h.readout_width;                 // read-out width at the kernel's shape: 32 or 64 (fused_shapes.h: FUSED_RF, FUSED_RF2)
+  if (RF != FUSED_RF && RF != FUSED_RF2) throw UnsupportedError("fused kernels: read-out width " + std::to_string(RF) + " is not a width of the kernel");      // (fused_host_model pads to one)
+  st.rt = RF / 16;
   const int MD = st.md, RD = st.rd;
   const bool b3 = st.arith == AR_BF16X3 || st.arith == AR_TF32EQ, h2 = st.arith == AR_F16X2, tbt = st.tbt;
   const int nterm = st.arith == AR_BF16X3 ? 3 : 2;
@@ -1295,16 +1333,18 @@ static void fused_prepare(Model &m) {
   };
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
   const double *wc = w0.data.data() + (size_t)2 * T * W;        // Bessel block [8][W]
-  std::vector<double> w3r((size_t)W * 32, 0.0);                 // W3 (last layer, [W][64]) @ Wr (read-out), float64
+  std::vector<double> w3r((size_t)W * RF, 0.0);                 // W3 (last layer, [W][64]) @ Wr (read-out, [64][RF]), float64
   {
     const double *W3 = T_("l" + std::to_string(NL) + ".lat.w" + std::to_string(MD)), *Wr = T_("out.w0");
     for (int i = 0; i < W; ++i)
       for (int q = 0; q < 64; ++q)
-        for (int n = 0; n < 32; ++n) w3r[(size_t)i * 32 + n] += W3[(size_t)i * 64 + q] * Wr[(size_t)q * 32 + n];
+        for (int n = 0; n < RF; ++n) w3r[(size_t)i * RF + n] += W3[(size_t)i * 64 + q] * Wr[(size_t)q * RF + n];
   }
   if (!tbt && MD != 2) throw UnsupportedError("fused_tb=mlp needs MLP depth 2");
   if (RD != 1 && !h2) throw UnsupportedError("fused kernels: read-out depth 2 has f16x2 instances only");      // (fused_model_supported keeps such a model away)
   if (W != FUSED_WF && !(h2 && tbt && RD == 1)) throw UnsupportedError("fused kernels: MLP width 65..128 has f16x2 instances with the two-body table and read-out depth 1 only");      // (likewise)
+  if (RF != FUSED_RF && !(h2 && tbt && RD == 1 && W == FUSED_WF))
+    throw UnsupportedError("fused kernels: read-out width 33..64 has f16x2 instances with the two-body table, MLP width <= 64 and read-out depth 1 only");      // (likewise)
   if (!tbt) {
     fwd(wc, 8, 64);
     fwd(T_("tb.w1"), 64, 64);
@@ -1323,19 +1363,19 @@ static void fused_prepare(Model &m) {
     for (int hl = 1; hl < MD; ++hl) fwd(T_(lk + ".lat.w" + std::to_string(hl)), W, W);
     if (k < NL - 1) fwd(T_(lk + ".lat.w" + std::to_string(MD)), W, 64);
     else {            // last layer: the read-out's first linear applied, multiplied into W3, to z2 and then to x (k_fused, latent MLP)
-      fwd(w3r.data(), W, 32);
-      fwd(T_("out.w0"), 64, 32);
+      fwd(w3r.data(), W, RF);
+      fwd(T_("out.w0"), 64, RF);
     }
   }
   if (RD == 2) {      // the read-out's second hidden layer, forward and transposed: two half-ring blocks (k_fused: RD)
-    fwd(T_("out.w1"), 32, 32);
-    bwd(T_("out.w1"), 32, 32);
+    fwd(T_("out.w1"), RF, RF);
+    bwd(T_("out.w1"), RF, RF);
   }
-  bwd(T_("out.w0"), 64, 32);
+  bwd(T_("out.w0"), 64, RF);
   for (int k = NL - 1; k >= 0; --k) {
     const std::string lk = "l" + std::to_string(k + 1);
     if (k < NL - 1) bwd(T_(lk + ".lat.w" + std::to_string(MD)), W, 64);
-    else bwd(w3r.data(), W, 32);
+    else bwd(w3r.data(), W, RF);
     for (int hl = MD - 1; hl >= 1; --hl) bwd(T_(lk + ".lat.w" + std::to_string(hl)), W, W);
     bwd(T_(lk + ".lat.w0"), 96, W);
     if (k < NL - 1) {
@@ -1358,7 +1398,7 @@ static void fused_prepare(Model &m) {
   // two-body table (see k_fused), small tables, upload, scalar arguments, float16 range verdict: fused_common.h
   st.ncu = fused_prepare_tail(m, h, w, A, st.wbuf, tbt, 5, 32, nullptr, st.arith, h_flags);
   // Persistent workgroups, 8 waves per CU either way (two per SIMD, 256 registers each).
-  A.wave_scratch = (long long)R_TOTAL(NL, MD, st.wt) * ROW;
+  A.wave_scratch = (long long)R_TOTAL(NL, MD, st.wt) * ROW;       // (the read-out width does not enter: the RT = 4 instances are f16x2, which save no z (W3 Wr) rows -- and those would fit the layer's four u rows)
   st.scratch.reserve((size_t)st.ncu * 8 * A.wave_scratch * sizeof(float));
   A.scratch = st.scratch.as<float>();
   st.tiles.partial.reserve((size_t)st.ncu * 2 * 7 * sizeof(double));
@@ -1425,6 +1465,7 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
       // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
       A.tchunk = (nedges_est / (16 * shape) > (long long)g * 256) ? TCHUNK : 1;
       if (const char *tc = std::getenv("AHIP_TCHUNK")) A.tchunk = std::max(1, std::atoi(tc));       // experiments
+      if (st.arith == AR_F16X2 && st.rt == 4) { fused_launch_f16_r64(shape, st.md, g, s, A); continue; }                    // fused_hq.o (MLP width 64, read-out depth 1: fused_prepare)
       if (st.arith == AR_F16X2 && st.wt == 8) { fused_launch_f16_w128(shape, st.md, g, s, A); continue; }                   // fused_hm.o (read-out depth 1: fused_prepare)
       if (st.arith == AR_F16X2 && st.rd == 2) { fused_launch_f16_rd2(shape, st.md, g, s, A); continue; }                     // fused_hr.o
       if (st.arith == AR_F16X2) { fused_launch_f16(shape, st.prof_on, st.md, g, s, A); continue; }                        // fused_h.o

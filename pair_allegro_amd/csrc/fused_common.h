@@ -703,7 +703,7 @@ static int fused_prepare_tail(Model &m, const HostModel &h, std::vector<float> &
     const HostTensor &res = h.get("l" + std::to_string(k + 1) + ".res");
     A.o_res[k] = w_mark(w); w.push_back((float)res.data[0]); w.push_back((float)res.data[1]);
   }
-  A.o_out1 = w_mark(w); for (int u = 0; u < 32; ++u) w.push_back((float)h.get("out.w" + std::to_string(h.readout_depth)).data[u]);      // the read-out's final 32 -> 1 vector
+  A.o_out1 = w_mark(w); for (int u = 0; u < h.readout_width; ++u) w.push_back((float)h.get("out.w" + std::to_string(h.readout_depth)).data[u]);      // the read-out's final R -> 1 vector (R = 32 or 64: the padded model's)
   A.o_scale = w_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("scale").data[t]);
   A.o_shift = w_mark(w); for (int t = 0; t < T; ++t) w.push_back((float)h.get("shift").data[t]);
   w_mark(w);
@@ -725,4 +725,12 @@ static int fused_prepare_tail(Model &m, const HostModel &h, std::vector<float> &
   AHIP_CHECK(hipGetDeviceProperties(&prop, m.device));
   return prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 }
+// (an epilogue functor like those at the head of this file; it stands here, behind the kernels, so that their source positions in the committed resource files stay put)
+struct EpiScale {             // out = c * v, nothing saved
+  static constexpr bool STORES = false;
+  float c;
+  __device__ __forceinline__ void tile_done(int, const f32x4 &) const {}
+  __device__ __forceinline__ float apply(int, int, float v) const { return c * v; }
+  __device__ __forceinline__ void flush(int) const {}
+};
 }  // namespace ahip

@@ -34,7 +34,7 @@ namespace ahip {
 
 // The shape of k_fused_lx: l_max = 2, 2 16-feature tiles (32 tensor features); NW = 4 waves (one per SIMD, 64 edge slots) or 8 (two per SIMD, 128 slots:
 // centres with 65..128 edges, option wide_tile=auto); HT = 16-feature tiles of a hidden layer of the latent MLP: 4 (MLP width <= 64) or 8 (65..128, zero-padded to 128),
-// which only the saved-row map knows
+// which only the saved-row map knows (the read-out's tile count, template parameter RT of the kernel, touches neither the shape nor the rows)
 template <int NW_, int HT_ = 4> struct ShapeX {
   static_assert(NW_ == 4 || NW_ == 8, "4- or 8-wave tiles");
   static_assert(HT_ == 4 || HT_ == 8, "hidden layers of 64 or 128 features");
@@ -183,8 +183,8 @@ enum { PX_GEOM = 0, PX_EMB, PX_ENV, PX_TP, PX_LAT, PX_MIX, PX_OUT, PX_BLAT, PX_B
 // NW: waves per workgroup = 16-slot groups of a tile.  4: one wave per SIMD, the edge tensor parked in AGPRs.  8: two waves per SIMD, 256 registers each, no park
 // (compiled with AHIP_NO_ACC_PARK in an object of its own: fused_lx_w.o), one staging buffer; (MD, RD) = (2, 1), not profiled.
 // HT: 16-feature tiles of one hidden layer of the latent MLP: 4, or 8 for MLP width 65..128 zero-padded to 128 (f16x2, 4-wave tiles, read-out depth 1, not profiled; built in
-// fused_lx_m.o).  Only the hidden vectors and their saved rows grow (as in k_fused: template parameter WT); the LDS is that of HT = 4.
-template <int NW, int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1, int HT = 4>
+// fused_lx_m.o).  Only the hidden vectors and their saved rows grow (as in k_fused: template parameter WT); the LDS is that of HT = 4.  RT: 16-feature tiles of the read-out MLP's hidden layer: 2, or 4 for read-out width 33..64 zero-padded to 64 (f16x2, 4-wave tiles, HT = 4, read-out depth 1, not profiled; built in fused_lx_q.o).  Only the read-out vectors of the tile grow: the read-out saves no rows, so row map, scratch and LDS are those of RT = 2.
+template <int NW, int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1, int HT = 4, int RT = 2>
 __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
   using S = ShapeX<NW, HT>;
   using LdsT = LdsX<NW>;
@@ -201,6 +201,8 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
   constexpr int ZIMG = (MD == 1 || HT == 8) ? 0 : 4;
   static_assert(HT == 4 || (HT == 8 && NW == 4 && AR == 3 && RD == 1 && !PROF), "MLP width 128: f16x2 instances on 4-wave tiles, read-out depth 1, not profiled");
   static_assert(HT <= D, "the last hidden layer's images fit a staging slot");
+  static_assert(RT == 2 || (RT == 4 && NW == 4 && AR == 3 && RD == 1 && HT == 4 && !PROF), "read-out width 64: f16x2 instances on 4-wave tiles, MLP width 64, read-out depth 1, not profiled");
+  static_assert(lin_frags_h(4, RT) % RINGH == 0 && lin_frags_h(RT, 4) % RINGH == 0, "the weight ring stays in phase");
   // every linear whose shape depends on HT consumes whole rings of the weight stream: the ring phases of the mixing rows are those of HT = 4
   static_assert(lin_frags_h(4 + UT, HT) % RINGH == 0 && lin_frags_h(HT, HT) % RINGH == 0 && lin_frags_h(HT, 4) % RINGH == 0 && lin_frags_h(4, HT) % RINGH == 0 &&
                     lin_frags_h(HT, 4 + UT) % RINGH == 0, "the weight ring stays in phase");
@@ -481,24 +483,24 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
     f32x4 upre[4], zt[HT], w0pre[L * UT];
     if constexpr (!SAVEZ) load_rows<4>(SB, S::R_LAYER(NL - 1, MD) + S::O_U(MD), upre, v16);
     __builtin_amdgcn_sched_barrier(0);
-    f32x4 zr[2];
-    lx_lin<AR, 4, 2, false>(WB, wp, x, zr, v16, ring, EpiNone{});
-    f32x4 zr2[2];            // RD = 2: pre-activations of the read-out's second hidden layer
+    f32x4 zr[RT];
+    lx_lin<AR, 4, RT, false>(WB, wp, x, zr, v16, ring, EpiNone{});
+    f32x4 zr2[RT];           // RD = 2: pre-activations of the read-out's second hidden layer
     if constexpr (RD == 2) {
-      f32x4 hr[2];
+      f32x4 hr[RT];
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < RT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) hr[t][r] = silu1(zr[t][r]);
-      lx_lin<AR, 2, 2, false, 0>(WB, wp, hr, zr2, v16, ring, EpiNone{});
+      lx_lin<AR, RT, RT, false, 0>(WB, wp, hr, zr2, v16, ring, EpiNone{});
     }
-    f32x4 (&zo)[2] = RD == 2 ? zr2 : zr;        // pre-activations of the last hidden layer
-    f32x4 wo1[2];            // the read-out's final 32 -> 1 vector (out.w1, or out.w2 of a depth-2 read-out)
+    f32x4 (&zo)[RT] = RD == 2 ? zr2 : zr;       // pre-activations of the last hidden layer
+    f32x4 wo1[RT];           // the read-out's final R -> 1 vector (out.w1, or out.w2 of a depth-2 read-out), R = 16 RT
 #pragma unroll
-    for (int t = 0; t < 2; ++t) wo1[t] = *(const f32x4 *)(Wb + A.o_out1 + 16 * t + 4 * g);
+    for (int t = 0; t < RT; ++t) wo1[t] = *(const f32x4 *)(Wb + A.o_out1 + 16 * t + 4 * g);
     float eps = 0.f;
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < RT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) eps += silu1(zo[t][r]) * wo1[t][r];
     eps = gsum(eps);
@@ -518,21 +520,21 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
     const float deps = valid ? lds.scale[ti] * A.cenv * bsc : 0.f;
     f32x4 dx[4];
     {
-      f32x4 dzr[2];
+      f32x4 dzr[RT];
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < RT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) dzr[t][r] = deps * wo1[t][r] * dsilu1(zo[t][r]);
       if constexpr (RD == 2) {
         // dzr holds the gradient of zr2: back through out.w1^T and the first hidden layer's SiLU (linear in deps, so the f16x2 power-of-two scale passes through)
-        f32x4 dhr[2];
-        lx_lin<AR, 2, 2, false, 4>(WB, wp, dzr, dhr, v16, ring, EpiNone{});
+        f32x4 dhr[RT];
+        lx_lin<AR, RT, RT, false, 4>(WB, wp, dzr, dhr, v16, ring, EpiNone{});
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+        for (int t = 0; t < RT; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) dzr[t][r] = dhr[t][r] * dsilu1(zr[t][r]);
       }
-      lx_lin<AR, 2, 4, false>(WB, wp, dzr, dx, v16, ring, EpiNone{});
+      lx_lin<AR, RT, 4, false>(WB, wp, dzr, dx, v16, ring, EpiNone{});
     }
 #pragma unroll
     for (int t = 0; t < HT; ++t) zt[t] = stg_load(STQ(0), ZIMG + t);        // the last layer's last hidden layer rows, from the staging tile
@@ -838,15 +840,23 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
 }
 
 // ---------------------------------------------------------------------------- host side
-// This file is compiled four times (Makefile): AHIP_LX_PART 0 = the host side and the 4-wave read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone
-// (fused_lx_r.o), 2 = the 8-wave instances alone, with AHIP_NO_ACC_PARK (fused_lx_w.o), 3 = the MLP-width-128 instances alone (fused_lx_m.o)
+// This file is compiled five times (Makefile): AHIP_LX_PART 0 = the host side and the 4-wave read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone
+// (fused_lx_r.o), 2 = the 8-wave instances alone, with AHIP_NO_ACC_PARK (fused_lx_w.o), 3 = the MLP-width-128 instances alone (fused_lx_m.o), 4 = the read-out-width-64
+// instances alone (fused_lx_q.o)
 #ifndef AHIP_LX_PART
 #define AHIP_LX_PART 0
 #endif
 void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
 void fusedlx_launch_w8(int nl, int ar, int var, int grid, hipStream_t s, const FusedLxArgs &A);
 void fusedlx_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
-#if AHIP_LX_PART == 3
+void fusedlx_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
+#if AHIP_LX_PART == 4
+void fusedlx_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // RT = 4: f16x2 only, 4-wave tiles, MLP width 64, read-out depth 1, plain and per-atom virial, not profiled
+  dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    hipLaunchKernelGGL((k_fused_lx<4, nl, false, 3, v == VAR_VA, md, 1, 4, 4>), dim3(grid), dim3(4 * 64), 0, s, A);
+  }, nl, var, md);
+}
+#elif AHIP_LX_PART == 3
 void fusedlx_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // HT = 8: f16x2 only, 4-wave tiles, read-out depth 1, plain and per-atom virial, not profiled
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
     hipLaunchKernelGGL((k_fused_lx<4, nl, false, 3, v == VAR_VA, md, 1, 8>), dim3(grid), dim3(4 * 64), 0, s, A);
@@ -879,6 +889,7 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
   constexpr int L = S::L, U = S::U, D = S::D;
   const int NL = h.num_layers, MD = h.mlp_depth;      // latent MLP: lat.w0 ([x, scalars] -> W), lat.w1 .. lat.w{MD-1} (W -> W), output linear lat.w{MD} (W -> 64)
   const int W = h.mlp_width;                          // hidden width at the kernel's shape: 64 or 128 (fused_shapes.h: FUSED_WF, FUSED_WF2)
+  const int RF = h.readout_width;                     // read-out width at the kernel's shape: 32 or 64 (FUSED_RF, FUSED_RF2)
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
   auto frag = [&](const double *W, int K, int N, int ldw) {
@@ -913,12 +924,12 @@ static int lx_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, 
       for (int lm = 0; lm < D; ++lm) mixfrag(mx + (size_t)l_of_lm(lm) * U * U, lm, false);
     }
   }
-  fwd(T_("out.w0"), 64, 32);
-  if (h.readout_depth == 2) {      // the read-out's second hidden layer, forward and transposed: half a ring each (k_fused_lx: RD)
-    fwd(T_("out.w1"), 32, 32);
-    bwd(T_("out.w1"), 32, 32);
+  fwd(T_("out.w0"), 64, RF);
+  if (h.readout_depth == 2) {      // the read-out's second hidden layer, forward and transposed: half a ring each (k_fused_lx: RD; RF = 32 there)
+    fwd(T_("out.w1"), RF, RF);
+    bwd(T_("out.w1"), RF, RF);
   }
-  bwd(T_("out.w0"), 64, 32);
+  bwd(T_("out.w0"), 64, RF);
   for (int k = NL - 1; k >= 0; --k) {
     const std::string lk = "l" + std::to_string(k + 1);
     for (int hl = MD; hl >= 1; --hl) bwd(T_(lk + ".lat.w" + std::to_string(hl)), W, hl < MD ? W : 64);
@@ -944,6 +955,8 @@ bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
   if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
   if (st.ht != 4 && !(st.ht == 8 && st.arith == AR_F16X2 && st.rd == 1 && max_slots == LX_TILE_SLOTS))
     throw UnsupportedError("wide fused kernels: MLP width 65..128 has f16x2 instances on 64-slot tiles with read-out depth 1 only");      // (likewise; lx_max_tile_slots keeps wide_tile=auto at 64 slots)
+  if (st.rt != 2 && !(st.rt == 4 && st.arith == AR_F16X2 && st.rd == 1 && st.ht == 4 && max_slots == LX_TILE_SLOTS))
+    throw UnsupportedError("wide fused kernels: read-out width 33..64 has f16x2 instances on 64-slot tiles with MLP width <= 64 and read-out depth 1 only");      // (likewise)
   // Tile shape (4 waves / 64 slots or 8 waves / 128 slots, option wide_tile=auto) from the largest degree of THIS list, as k_fused does (fused.hip: fused_run): on the
   // host where it is known or bounded by the list's rows, else both shapes are launched and the device word decides (nw = 0)
   int nw = 4;
@@ -955,6 +968,7 @@ bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
   lx_run<ShapeX<4>, ShapeX<8>>(m, a, st, "fused_lx", [&](const FusedLxArgs &A, int grid, int var, int shape) {
     if (shape == 8) { fusedlx_launch_w8(A.NL, st.arith, var, grid, a.stream, A); return; }      // fused_lx_w.o
     if (st.ht == 8) { fusedlx_launch_m(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_m.o
+    if (st.rt == 4) { fusedlx_launch_q(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_q.o
     if (st.rd == 2) { fusedlx_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_r.o
     dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
       if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)

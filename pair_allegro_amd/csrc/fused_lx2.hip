@@ -213,8 +213,8 @@ enum { PP_GEOM = 0, PP_EMB, PP_ENV, PP_TP, PP_LAT, PP_MIX, PP_OUT, PP_BLAT, PP_B
 // ---------------------------------------------------------------------------- the kernel
 // VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
 // MD: hidden layers of the latent MLP (1..3; 1 and 3 on the f16x2 arithmetic only, as in k_fused and k_fused_lx).  Every hidden layer is split by output tile, so each
-// one beyond the first costs one more pair hand-over forward and one more backward; MD is a compile-time fact, so all eight waves still meet the same barriers.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 only, built in fused_lx2_r.o).
-template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1>
+// one beyond the first costs one more pair hand-over forward and one more backward; MD is a compile-time fact, so all eight waves still meet the same barriers.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 only, built in fused_lx2_r.o).  RT: 16-feature tiles of the read-out MLP's hidden layer: 2, or 4 for read-out width 33..64 zero-padded to 64 (f16x2, read-out depth 1, not profiled; built in fused_lx2_q.o).  Both waves of a pair evaluate the whole read-out, so only its vectors grow: row map, scratch and LDS are those of RT = 2.
+template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1, int RT = 2>
 __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
   using S = ShapeP;
   constexpr int NTHREADS = 512, D = S::D, U = S::U, HT = S::HT, EWH = S::EWH, MAXA = S::MAXA, STG_LD = S::STG_LD, ENVA = S::ENVA, NP = S::NP, L = S::L;
@@ -222,6 +222,8 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
   static_assert(MD >= 1 && MD <= 3 && (MD == 2 || AR == 3), "latent MLP depth 1 / 3: f16x2 instances only");
   static_assert(MD == 2 || !PROF, "profiled instances: depth 2");
   static_assert(RD == 1 || (RD == 2 && AR == 3 && !PROF), "read-out depth 2: f16x2 instances only, not profiled");
+  static_assert(RT == 2 || (RT == 4 && AR == 3 && RD == 1 && !PROF), "read-out width 64: f16x2 instances only, read-out depth 1, not profiled");
+  static_assert(lin_frags_h(4, RT) % RINGH == 0 && lin_frags_h(RT, 4) % RINGH == 0, "the weight ring stays in phase");
   __shared__ LdsP lds;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
@@ -474,24 +476,24 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
     if constexpr (!SAVEZ) load_rows<2>(SB, S::R_LAYER(NL - 1, MD) + S::O_U(MD), upre, V16());
     load_rows<2>(SB, S::R_LAYER(NL - 1, MD) + S::O_Z(MD), zt, V16());
     __builtin_amdgcn_sched_barrier(0);
-    f32x4 zr[2];
-    lx_lin<AR, 4, 2, false>(WB, wp, x, zr, V16(), ring, EpiNone{});
-    f32x4 zr2[2];            // RD = 2: pre-activations of the read-out's second hidden layer
+    f32x4 zr[RT];
+    lx_lin<AR, 4, RT, false>(WB, wp, x, zr, V16(), ring, EpiNone{});
+    f32x4 zr2[RT];           // RD = 2: pre-activations of the read-out's second hidden layer
     if constexpr (RD == 2) {
-      f32x4 hr[2];
+      f32x4 hr[RT];
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < RT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) hr[t][r] = silu1(zr[t][r]);
-      lx_lin<AR, 2, 2, false, 0>(WB, wp, hr, zr2, V16(), ring, EpiNone{});
+      lx_lin<AR, RT, RT, false, 0>(WB, wp, hr, zr2, V16(), ring, EpiNone{});
     }
-    f32x4 (&zo)[2] = RD == 2 ? zr2 : zr;        // pre-activations of the last hidden layer
-    f32x4 wo1[2];            // the read-out's final 32 -> 1 vector (out.w1, or out.w2 of a depth-2 read-out)
+    f32x4 (&zo)[RT] = RD == 2 ? zr2 : zr;       // pre-activations of the last hidden layer
+    f32x4 wo1[RT];           // the read-out's final R -> 1 vector (out.w1, or out.w2 of a depth-2 read-out), R = 16 RT
 #pragma unroll
-    for (int t = 0; t < 2; ++t) wo1[t] = *(const f32x4 *)(Wb + A.o_out1 + 16 * t + 4 * g);
+    for (int t = 0; t < RT; ++t) wo1[t] = *(const f32x4 *)(Wb + A.o_out1 + 16 * t + 4 * g);
     float eps = 0.f;
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < RT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) eps += silu1(zo[t][r]) * wo1[t][r];
     eps = gsum(eps);
@@ -511,21 +513,21 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
     const float deps = valid ? lds.scale[ti] * A.cenv * bsc : 0.f;
     f32x4 dx[4];             // dE/dx, all 64 features, own tiles first (replicated in the pair)
     {
-      f32x4 dzr[2];
+      f32x4 dzr[RT];
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+      for (int t = 0; t < RT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) dzr[t][r] = deps * wo1[t][r] * dsilu1(zo[t][r]);
       if constexpr (RD == 2) {
         // dzr holds the gradient of zr2: back through out.w1^T and the first hidden layer's SiLU (linear in deps, so the f16x2 power-of-two scale passes through)
-        f32x4 dhr[2];
-        lx_lin<AR, 2, 2, false, 4>(WB, wp, dzr, dhr, V16(), ring, EpiNone{});
+        f32x4 dhr[RT];
+        lx_lin<AR, RT, RT, false, 4>(WB, wp, dzr, dhr, V16(), ring, EpiNone{});
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+        for (int t = 0; t < RT; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) dzr[t][r] = dhr[t][r] * dsilu1(zr[t][r]);
       }
-      lx_lin<AR, 2, 4, false>(WB, wp, dzr, dx, V16(), ring, EpiNone{});
+      lx_lin<AR, RT, 4, false>(WB, wp, dzr, dx, V16(), ring, EpiNone{});
     }
     float dfc_part = 0.f;    // partial sums over the own channels / own latent tiles: they meet in lds.ych at the end of the tile
     float dY[D];
@@ -860,12 +862,20 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
 }
 
 // ---------------------------------------------------------------------------- host side
-// This file is compiled twice (Makefile): AHIP_LX_PART 0 = the host side and the read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone (fused_lx2_r.o)
+// This file is compiled three times (Makefile): AHIP_LX_PART 0 = the host side and the read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone (fused_lx2_r.o),
+// 2 = the read-out-width-64 instances alone (fused_lx2_q.o)
 #ifndef AHIP_LX_PART
 #define AHIP_LX_PART 0
 #endif
 void fusedlx2_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
-#if AHIP_LX_PART == 1
+void fusedlx2_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
+#if AHIP_LX_PART == 2
+void fusedlx2_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // RT = 4: f16x2 only, read-out depth 1, plain and per-atom virial, not profiled
+  dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    hipLaunchKernelGGL((k_fused_lx2<nl, false, 3, v == VAR_VA, md, 1, 4>), dim3(grid), dim3(ShapeP::NW * 64), 0, s, A);
+  }, nl, var, md);
+}
+#elif AHIP_LX_PART == 1
 void fusedlx2_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // f16x2 only, plain and per-atom virial, not profiled
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
     hipLaunchKernelGGL((k_fused_lx2<nl, false, 3, v == VAR_VA, md, 2>), dim3(grid), dim3(ShapeP::NW * 64), 0, s, A);
@@ -886,6 +896,9 @@ static std::vector<double> gather_tiles(const double *W, int ldw, const std::vec
 // k_fused_lx2's weight streams, one per wave half, in the order a tile consumes them (see k_fused_lx2)
 static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, Arith arith) {
   using S = ShapeP;
+  const int RF = h.readout_width;                     // read-out width at the kernel's shape: 32 or 64 (fused_shapes.h: FUSED_RF, FUSED_RF2)
+  std::vector<int> rt_all;                            // every 16-feature tile of the read-out's hidden layer: both waves of a pair evaluate it whole
+  for (int t = 0; t < RF / 16; ++t) rt_all.push_back(t);
   const int NL = h.num_layers, MD = h.mlp_depth, U = S::U, D = S::D, UT = S::UT;      // latent MLP: lat.w0, hidden lat.w1 .. lat.w{MD-1}, output linear lat.w{MD}
   auto T_ = [&](const std::string &name) -> const double * { return h.get(name).data.data(); };
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
@@ -924,12 +937,12 @@ static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h,
         for (int lm = 0; lm < D; ++lm) put(mx + (size_t)l_of_lm(lm) * U * U, U, xo, ownt);
       }
     }
-    put(T_("out.w0"), 32, xo, {0, 1});
-    if (h.readout_depth == 2) {      // the read-out's second hidden layer, forward and transposed, whole in both halves' streams: half a ring each (k_fused_lx2: RD)
-      put(T_("out.w1"), 32, {0, 1}, {0, 1});
-      putT(T_("out.w1"), 32, 32, {0, 1}, {0, 1});
+    put(T_("out.w0"), RF, xo, rt_all);
+    if (h.readout_depth == 2) {      // the read-out's second hidden layer, forward and transposed, whole in both halves' streams: half a ring each (k_fused_lx2: RD; RF = 32 there)
+      put(T_("out.w1"), RF, rt_all, rt_all);
+      putT(T_("out.w1"), RF, RF, rt_all, rt_all);
     }
-    putT(T_("out.w0"), 64, 32, {0, 1}, xo);
+    putT(T_("out.w0"), 64, RF, rt_all, xo);
     for (int k = NL - 1; k >= 0; --k) {
       const std::string lk = "l" + std::to_string(k + 1);
       for (int hl = MD; hl >= 1; --hl) putT(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64, xo, ownt);
@@ -951,7 +964,10 @@ bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
   FusedLxState &st = lx_prepare<ShapeP>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream);     // path weights x the path's base |c| (tp_g)
   static_assert(PP_N == LX_NPHASE, "profile phases");
   if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
+  if (st.rt != 2 && !(st.rt == 4 && st.arith == AR_F16X2 && st.rd == 1))
+    throw UnsupportedError("wide fused kernels: read-out width 33..64 has f16x2 instances with read-out depth 1 only");      // (likewise)
   lx_run<ShapeP>(m, a, st, "fused_lx2", [&](const FusedLxArgs &A, int grid, int var, int) {
+    if (st.rt == 4) { fusedlx2_launch_q(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_q.o
     if (st.rd == 2) { fusedlx2_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_r.o
     dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
       if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)

@@ -87,7 +87,7 @@ struct FusedLxState {
   int ncu = 256;
   int scratch_waves = 0;       // waves per workgroup the per-wave scratch holds
   int md = 2, rd = 1;          // hidden layers of the latent MLP and of the read-out MLP (template parameters MD, RD of the kernels)
-  int ht = 4;                  // 16-feature tiles of a hidden layer of the latent MLP (template parameter HT of k_fused_lx: 4 = MLP width 64, 8 = 128)
+  int ht = 4, rt = 2;          // 16-feature tiles of a hidden layer of the latent MLP (template parameter HT of k_fused_lx: 4 = MLP width 64, 8 = 128) and of the read-out MLP's hidden layer (RT of both kernels: 2 = read-out width 32, 4 = 64)
   Arith arith = AR_F32;        // AR_F32 or AR_F16X2 (arith_policy.h: resolve_arith, wide)
 };
 
@@ -109,8 +109,8 @@ static FusedLxState &lx_prepare(Model &m, FusedLxState *&slot, const double *cba
   int h_flags = stream(w, A, h, st.arith);
   if (st.arith == AR_F16X2 && tiny) h_flags |= model_tiny_linear(h);
   st.ncu = fused_prepare_tail(m, h, w, A, st.wbuf, true, S::NP, S::U, cbase, st.arith, h_flags);
-  st.md = h.mlp_depth; st.rd = h.readout_depth; st.ht = h.mlp_width / 16;
-  A.wave_scratch = (long long)S::R_TOTAL(NL, st.md) * ROW;
+  st.md = h.mlp_depth; st.rd = h.readout_depth; st.ht = h.mlp_width / 16; st.rt = h.readout_width / 16;
+  A.wave_scratch = (long long)S::R_TOTAL(NL, st.md) * ROW;       // (the read-out width does not enter: the read-out saves no rows)
   st.scratch.reserve((size_t)st.ncu * scratch_waves * A.wave_scratch * sizeof(float));
   st.scratch_waves = scratch_waves;
   A.scratch = st.scratch.as<float>();
