@@ -101,6 +101,13 @@ int ahip_model_meta(const ahip_model *m, double *r_max, int *num_types, const ch
  *                                                 fcc box with 78 edges per centre, 3 layers, 32 tensor features (tools/wide_tile_cost.py): 79.5 ms per evaluation
  *                                                 with "auto" against 265 ms with "64" (every centre heavy), the latter equal to the release before the option.  Not
  *                                                 measured on other lists, which is why the default stays "64".
+ *   "lx64_mlp_width" = "64" | "auto"             MLP width of the kernel for 33..64 tensor features (k_fused_lx2: l_max = 2, or l_max = 1 lifted): "64" (default) keeps it at MLP
+ *                                                 width up to 64, so such a model with mlp_width 65..128 runs on the layer-at-a-time kernels; "auto" lets it run on the kernel's
+ *                                                 width-128 instances, zero-padded to 128, under the rules of that width on the other kernels: f16x2 arithmetic, read-out
+ *                                                 depth 1, read-out width up to 32, and here allow_tf32 = 0 (anything else: the layer-at-a-time kernels, as without the
+ *                                                 option).  For every other model (MLP width up to 64, up to 32 tensor features) "auto" changes nothing.  Measured on one
+ *                                                 box and one model shape only (41 472-atom water, model L with 64 tensor features: tools/mlp_width_cost.py --configs 5:24,
+ *                                                 profiles/lx64_mlp_width_cost.txt), which is why the default stays "64".
  *   "timing"    = "0" | "1"                      record per-stage HIP events (ahip_get_timings)
  * Unknown keys and values are errors (AHIP_ERR_ARG).
  */

@@ -329,6 +329,9 @@ int ahip_set_option(ahip_model *m, const char *key, const char *value) {
     } else if (k == "wide_tile") {
       const Model::WideTile o = (Model::WideTile)word(Model::WIDE_TILE_WORDS);
       if (o != m->opt_wide_tile) { m->opt_wide_tile = o; fusedlx_free(*m); }      // the per-wave scratch is sized for the shapes the option admits (lx_prepare)
+    } else if (k == "lx64_mlp_width") {
+      const Model::Lx64MlpWidth o = (Model::Lx64MlpWidth)word(Model::LX64_MLP_WIDTH_WORDS);
+      if (o != m->opt_lx64_mlp_width) { m->opt_lx64_mlp_width = o; fusedlx_free(*m); }      // the per-wave scratch follows the row map of the instances the option admits (lx_prepare)
     } else if (k == "timing") {
       m->timing = (v == "1" || v == "on" || v == "true");
     } else throw ArgError("unknown option '" + k + "'");

@@ -117,6 +117,8 @@ struct Model {
   static constexpr const char *DENSE_CENTRES_WORDS = "whole|split";
   enum class WideTile { S64, Auto };
   static constexpr const char *WIDE_TILE_WORDS = "64|auto";
+  enum class Lx64MlpWidth { W64, Auto };
+  static constexpr const char *LX64_MLP_WIDTH_WORDS = "64|auto";
   Path opt_path = Path::Auto;
   Precision opt_precision = Precision::Model;
   FusedTb opt_fused_tb = FusedTb::Table;    // table | mlp: two-body embedding of the fused kernel from the spline table or as an MLP
@@ -145,6 +147,7 @@ struct Model {
   EdgeSchedule opt_edge_schedule = EdgeSchedule::Auto;   // auto | static | dynamic: unit schedule of the single-pass edge build (edges.hip)
   DenseCentres opt_dense_centres = DenseCentres::Whole;   // whole | split: a list with a few centres above a fused kernel's tile goes to the layer-at-a-time kernels as a whole, or only those centres do (allegro_hip.hip: run_model_once)
   WideTile opt_wide_tile = WideTile::S64;                 // 64 | auto: k_fused_lx on 64-slot tiles only, or on its 128-slot shape when the list's largest degree asks for it (fused_shapes.h: fused_has_wide_tile)
+  Lx64MlpWidth opt_lx64_mlp_width = Lx64MlpWidth::W64;    // 64 | auto: k_fused_lx2 (33..64 tensor features) at MLP width <= 64 only, or also on its MLP-width-128 instances for mlp_width 65..128 (fused_shapes.h: the gates' lx64_w128)
   bool cutoff_strict = false;               // edge kept iff rsq < cut^2 (the KOKKOS reference path) instead of rsq <= cut^2 (the host path)
 
   // weights
@@ -291,7 +294,8 @@ void fused_poll_alarm(Model &m);            // alarm_take + the policy: auto -> 
 inline const HostModel &fused_host_model(Model &m) {
   const HostModel &h = m.hm;
   const FusedFamily cls = fused_shape_class(h);
-  const int WF = fused_WF(h);                // hidden width of the latent MLP: 64, or 128 for a model with mlp_width 65..128 (fused_shapes.h)
+  const int WF = fused_WF(h);                // hidden width of the latent MLP: 64, or 128 for a model with mlp_width 65..128 (fused_shapes.h; a model of 33..64 tensor features
+                                             // gets here with such a width under option lx64_mlp_width=auto only: without it the wide gate refuses the model and nothing pads it)
   const int RF = fused_RF(h);                // width of the read-out MLP: 32, or 64 for a model with readout_width 33..64
   if (m.active.empty() && fused_shape_exact(h, cls, WF, RF)) return h;
   if (!m.hm_fused_ready) {
@@ -311,6 +315,7 @@ int inactive_take(Model &m);
 // the arithmetic policy (arith_policy.h) applied to a model: k_fused (wide = false) or the wide kernels
 inline bool arith_may_degrade(const Model &m) { return arith_may_degrade(m.arith); }
 inline bool fused_tb_is_table(const Model &m) { return fused_tb_is_table(m.opt_fused_tb); }
+inline bool fused_lx64_w128(const Model &m) { return m.opt_lx64_mlp_width == Model::Lx64MlpWidth::Auto; }      // the gates' trailing argument (fused_shapes.h)
 inline Arith resolve_arith(const Model &m, bool wide) {
   return resolve_arith(arith_effective(m.arith.opt), m.hm.allow_tf32 != 0, m.arith.degraded, m.arith.force_f32, fused_tb_is_table(m), wide);
 }

@@ -880,7 +880,7 @@ void fusedlx_launch_w8(int nl, int ar, int var, int grid, hipStream_t s, const F
 #else
 
 // the gate itself: fused_shapes.h
-bool fusedlx_model_supported(const Model &m, std::string *why) { return fused_wide_supported(m.hm, resolve_arith(m, true), why, fused_n_active(m)); }
+bool fusedlx_model_supported(const Model &m, std::string *why) { return fused_wide_supported(m.hm, resolve_arith(m, true), why, fused_n_active(m), fused_lx64_w128(m)); }
 static_assert(LX_MAXNL == 3, "fused_shapes.h: 1..3 layers");
 
 // k_fused_lx's weight stream, in the order one tile consumes it: whole-matrix fragments (see k_fused_lx)

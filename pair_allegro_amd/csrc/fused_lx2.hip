@@ -48,16 +48,19 @@
 
 namespace ahip {
 
-struct ShapeP {
+// WH_: 16-feature hidden tiles of the latent MLP a wave OWNS: 2 (hidden width 64) or 4 (128: the MLP-width-128 instances, option lx64_mlp_width=auto); only the row map depends on it
+template <int WH_ = 2> struct ShapePW {
+  static_assert(WH_ == 2 || WH_ == 4, "hidden layers of 64 or 128 features, half of them per wave");
+  static constexpr int WH = WH_;
   static constexpr int L = 2, D = 9, NLP = 3, UT = 4, HT = 2, U = 64, EWH = NLP * HT;    // EWH: own 16-feature tiles of an (l, u) weight vector
   static constexpr int NW = 8, SLOTS = 64, MAXA = 4;
   static constexpr int STG_LD = D * 16 + 4;             // one K-tile of a slot: [lm][16] + pad
   static constexpr int ENVA = D * U + 16;               // environment row of one centre: [lm][u] + pad.  ENVA = 16 (mod 64): the rows of the (<= 4) centres of a tile and the four lane groups (+ 4 g)
                                                         // start in 16 distinct 4-bank groups (round 6; with + 4 centre 1 / group 0 met centre 0 / group 1: 229.1 -> 227.7 ms on config 5)
   static constexpr int NP = CgX<2>::NP;
-  // scratch rows (per wave, 1 KiB each): d x0/dd 4 | w0 EWH | per layer: omega EWH, hidden layers 1..MD 2 each (own tiles), u 2, V_in D*HT  (fused_lx_rows.h; MD = latent MLP depth)
-  using R = RowsP;
-  static_assert(R::EW == EWH && R::HR == HT && R::NV == D * HT, "row map of this shape");
+  // scratch rows (per wave, 1 KiB each): d x0/dd 4 | w0 EWH | per layer: omega EWH, hidden layers 1..MD WH each (own tiles), u 2, V_in D*HT  (fused_lx_rows.h; MD = latent MLP depth)
+  using R = std::conditional_t<WH_ == 2, RowsP, RowsPM>;
+  static_assert(R::EW == EWH && R::HR == WH_ && R::UR == 2 && R::NV == D * HT, "row map of this shape");
   static constexpr int R_DX0 = R::R_DX0, R_W0 = R::R_W0, O_OM = R::O_OM;
   __host__ __device__ static constexpr int O_Z(int h) { return R::O_Z(h); }
   __host__ __device__ static constexpr int O_U(int MD) { return R::O_U(MD); }
@@ -66,6 +69,7 @@ struct ShapeP {
   __host__ __device__ static constexpr int R_LAYER(int kk, int MD) { return R::R_LAYER(kk, MD); }
   __host__ __device__ static constexpr int R_TOTAL(int NL, int MD) { return R::R_TOTAL(NL, MD); }
 };
+using ShapeP = ShapePW<>;      // everything but the row map: LDS, tile shape, staging, tensor product
 
 struct __attribute__((aligned(16))) LdsP {
   using S = ShapeP;
@@ -88,10 +92,7 @@ struct __attribute__((aligned(16))) LdsP {
 static_assert(sizeof(LdsP) <= 160 * 1024, "LDS budget of one CU");
 
 __device__ __forceinline__ unsigned lds_addr(const void *p) { return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void *)p; }
-// Per-centre sum of the two staged K-tiles (one per wave half): env[a][lm][16 (2 h + t) + f] = scale * sum_{slots of a} stage[h][slot][lm][f].
-// Work item = (centre, half, 4-feature column); 4 lanes per item take every 4th slot (see reduce_stage_x in fused_lx.hip for the lane mapping).
-// A lane's reads past its centre's last slot go to a 16-byte block of zeros behind the staging area (one select per read) instead of
-// being masked out of the sum value by value: 105 instead of 216 vector instructions per call, twelve calls per tile.
+// Per-centre sum of the two staged K-tiles (one per wave half): env[a][lm][16 (2 h + t) + f] = scale * sum_{slots of a} stage[h][slot][lm][f]. Work item = (centre, half, 4-feature column); 4 lanes per item take every 4th slot (see reduce_stage_x in fused_lx.hip for the lane mapping). A lane's reads past its centre's last slot go to a 16-byte block of zeros behind the staging area (one select per read) instead of being masked out of the sum value by value: 105 instead of 216 vector instructions per call, twelve calls per tile.
 __device__ __forceinline__ void reduce_stage_p(const float *stg, const float *zero16, const int *aoff, float *dst, int na, float scale, int t, int uwave) {
   using S = ShapeP;
   constexpr int LPI = 4, NC1 = S::D * 4, NC = 2 * NC1, PER_ROUND = S::NW * 64 / LPI, NRD = S::SLOTS / LPI;
@@ -140,11 +141,7 @@ __device__ __forceinline__ void reduce_stage_p(const float *stg, const float *ze
 }
 
 // ---- pair hand-over through LDS ----
-// send: own register images into this wave's buffer xb; after a workgroup barrier the partner's images are read from its buffer.
-// The buffers alternate (xb ^= 1 per hand-over): a buffer is rewritten two hand-overs later, i.e. after a barrier that the partner
-// passes only with its reads of the older contents complete (s_waitcnt lgkmcnt(0) precedes every s_barrier).
-// (A pair-only synchronisation -- per-wave counters in LDS, spin on the partner's -- was measured instead of the workgroup barrier:
-// 29.8 vs 29.3 ms on the 41k-atom water box, i.e. the eight waves arrive together anyway; dropped.)
+// send: own register images into this wave's buffer xb; after a workgroup barrier the partner's images are read from its buffer. The buffers alternate (xb ^= 1 per hand-over): a buffer is rewritten two hand-overs later, i.e. after a barrier that the partner passes only with its reads of the older contents complete (s_waitcnt lgkmcnt(0) precedes every s_barrier). (A pair-only synchronisation -- per-wave counters in LDS, spin on the partner's -- was measured instead of the workgroup barrier: 29.8 vs 29.3 ms on the 41k-atom water box, i.e. the eight waves arrive together anyway; dropped.)
 struct Xch {
   float *mine;            // lds.xch[wave]
   const float *theirs;    // lds.xch[partner wave]
@@ -171,11 +168,14 @@ template <int NT> __device__ __forceinline__ void x_swap(const Xch &X, int &xb, 
   x_recv<NT>(X, xb, in);
   xb ^= 1;
 }
+// Hand-over of a hidden vector split by output tile: NT own tiles -> all 2 NT, own tiles first.  A buffer holds two images, so a 128-wide layer (NT = 4) goes in two rounds, own tiles 0..1 then 2..3, the buffer index alternating per ROUND: the argument above is per buffer and per barrier, so it holds round by round (round 2 rewrites the buffer of the hand-over before round 1, behind round 1's barrier; the next hand-over rewrites round 1's buffer behind round 2's barrier).
+template <int NT> __device__ __forceinline__ void x_gather(const Xch &X, int &xb, const f32x4 (&own)[NT], f32x4 (&all)[2 * NT]) {
+  static_assert(NT == 2 || NT == 4, "rounds of two images");
+#pragma unroll
+  for (int r = 0; r < NT; r += 2) { const f32x4 snd[2] = {own[r], own[r + 1]}; f32x4 pr[2]; x_swap<2>(X, xb, snd, pr); all[r] = own[r]; all[r + 1] = own[r + 1]; all[NT + r] = pr[0]; all[NT + r + 1] = pr[1]; }
+}
 
-// Channel mixing with the row hand-over, one (l, m) row at a time, in place on the parked half tensor:
-//   V[lm][own] <- ([V[lm][own], V[lm][partner's]] @ M_l)[own]   (forward: the output rows are saved as the next layer's V_in)
-//   V[lm][own] <- the same with M_l^T (+ ds on the scalar row)  (backward)
-// Row lm + 1 is handed over before row lm's MFMAs are issued, so the partner's images are in LDS when the next barrier falls.
+// Channel mixing with the row hand-over, one (l, m) row at a time, in place on the parked half tensor: V[lm][own] <- ([V[lm][own], V[lm][partner's]] @ M_l)[own]   (forward: the output rows are saved as the next layer's V_in) V[lm][own] <- the same with M_l^T (+ ds on the scalar row)  (backward) Row lm + 1 is handed over before row lm's MFMAs are issued, so the partner's images are in LDS when the next barrier falls.
 template <int LM, bool FWD, int AR>
 __device__ __forceinline__ void mix_rows_p(float (&V)[9][2][4], __amdgpu_buffer_rsrc_t WB, int &wp, LxRing<AR> &ring,
                                            __amdgpu_buffer_rsrc_t SB, int row0, const f32x4 (&ds)[2], const Xch &X, int &xb) {
@@ -213,17 +213,20 @@ enum { PP_GEOM = 0, PP_EMB, PP_ENV, PP_TP, PP_LAT, PP_MIX, PP_OUT, PP_BLAT, PP_B
 // ---------------------------------------------------------------------------- the kernel
 // VA: also the per-atom virial (output "atomic_virial": fused_common.h, vatom_scatter); launched only while that output is registered
 // MD: hidden layers of the latent MLP (1..3; 1 and 3 on the f16x2 arithmetic only, as in k_fused and k_fused_lx).  Every hidden layer is split by output tile, so each
-// one beyond the first costs one more pair hand-over forward and one more backward; MD is a compile-time fact, so all eight waves still meet the same barriers.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 only, built in fused_lx2_r.o).  RT: 16-feature tiles of the read-out MLP's hidden layer: 2, or 4 for read-out width 33..64 zero-padded to 64 (f16x2, read-out depth 1, not profiled; built in fused_lx2_q.o).  Both waves of a pair evaluate the whole read-out, so only its vectors grow: row map, scratch and LDS are those of RT = 2.
-template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1, int RT = 2>
+// one beyond the first costs one more pair hand-over forward and one more backward; MD is a compile-time fact, so all eight waves still meet the same barriers.  RD: hidden layers of the read-out MLP (1; 2 on f16x2 only, built in fused_lx2_r.o).  RT: 16-feature tiles of the read-out MLP's hidden layer: 2, or 4 for read-out width 33..64 zero-padded to 64 (f16x2, read-out depth 1, not profiled; built in fused_lx2_q.o).  Both waves of a pair evaluate the whole read-out, so only its vectors grow: row map, scratch and LDS are those of RT = 2.  WH: 16-feature tiles of a hidden layer of the latent MLP a wave OWNS: 2, or 4 for MLP width 65..128 zero-padded to 128 (f16x2, read-out depth 1, RT = 2, not profiled; option lx64_mlp_width=auto; built in fused_lx2_m.o).  Only the hidden vectors of the latent MLP and their saved rows grow (row map RowsPM: 4 own rows per hidden layer); a hidden layer is handed over in two rounds (x_gather), so the LDS is that of WH = 2.
+template <int NLT, bool PROF, int AR, bool VA = false, int MD = 2, int RD = 1, int RT = 2, int WH = 2>
 __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
-  using S = ShapeP;
+  using S = ShapePW<WH>;
   constexpr int NTHREADS = 512, D = S::D, U = S::U, HT = S::HT, EWH = S::EWH, MAXA = S::MAXA, STG_LD = S::STG_LD, ENVA = S::ENVA, NP = S::NP, L = S::L;
   constexpr bool SAVEZ = AR == 3;          // f16x2: raw pre-activation rows of the last hidden layer instead of silu' rows, no u rows (see fused.hip)
   static_assert(MD >= 1 && MD <= 3 && (MD == 2 || AR == 3), "latent MLP depth 1 / 3: f16x2 instances only");
   static_assert(MD == 2 || !PROF, "profiled instances: depth 2");
   static_assert(RD == 1 || (RD == 2 && AR == 3 && !PROF), "read-out depth 2: f16x2 instances only, not profiled");
   static_assert(RT == 2 || (RT == 4 && AR == 3 && RD == 1 && !PROF), "read-out width 64: f16x2 instances only, read-out depth 1, not profiled");
-  static_assert(lin_frags_h(4, RT) % RINGH == 0 && lin_frags_h(RT, 4) % RINGH == 0, "the weight ring stays in phase");
+  static_assert(WH == 2 || (WH == 4 && AR == 3 && RD == 1 && RT == 2 && !PROF), "MLP width 128: f16x2 instances only, read-out depth 1, read-out width 32, not profiled");
+  // every linear whose shape depends on RT or WH consumes whole rings of the weight stream: no ring phase behind the read-out or the latent MLP moves
+  static_assert(lin_frags_h(4, RT) % RINGH == 0 && lin_frags_h(RT, 4) % RINGH == 0 && lin_frags_h(8, WH) % RINGH == 0 && lin_frags_h(2 * WH, WH) % RINGH == 0 &&
+                    lin_frags_h(2 * WH, 2) % RINGH == 0 && lin_frags_h(4, WH) % RINGH == 0 && lin_frags_h(2 * WH, 4) % RINGH == 0, "the weight ring stays in phase");
   __shared__ LdsP lds;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4, wave = tid >> 6;
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
@@ -428,40 +431,34 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
       PHASEP(PP_TP);
       // latent MLP on [x, scalars], split by output tile: hand-overs of the scalars, z1, z2 and the new x
       {
-        f32x4 cat[8], z[2], zin[4], z2[2], xn[2], pr[2];
+        f32x4 cat[8], z[WH], zin[2 * WH], z2[WH], xn[2], pr[2];      // hidden vectors: WH own tiles, 2 WH after the hand-over (own tiles first)
 #pragma unroll
         for (int t = 0; t < 4; ++t) cat[t] = x[t];
         x_swap<2>(X, xb, sc, pr);
         cat[4] = sc[0]; cat[5] = sc[1]; cat[6] = pr[0]; cat[7] = pr[1];
         if constexpr (MD == 2) {
-          lx_lin<AR, 8, 2, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(1), V16()});
-          x_swap<2>(X, xb, z, pr);
-          zin[0] = z[0]; zin[1] = z[1]; zin[2] = pr[0]; zin[3] = pr[1];
-          if constexpr (SAVEZ) lx_lin<AR, 4, 2, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z(2), V16()});
-          else lx_lin<AR, 4, 2, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(2), V16()});
-          x_swap<2>(X, xb, z2, pr);
-          zin[0] = z2[0]; zin[1] = z2[1]; zin[2] = pr[0]; zin[3] = pr[1];
+          lx_lin<AR, 8, WH, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(1), V16()});
+          x_gather<WH>(X, xb, z, zin);
+          if constexpr (SAVEZ) lx_lin<AR, 2 * WH, WH, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z(2), V16()});
+          else lx_lin<AR, 2 * WH, WH, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(2), V16()});
+          x_gather<WH>(X, xb, z2, zin);
         } else if constexpr (MD == 1) {
           // the only hidden layer is the last one: raw z rows; one hand-over fewer
-          lx_lin<AR, 8, 2, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z(1), V16()});
-          x_swap<2>(X, xb, z, pr);
-          zin[0] = z[0]; zin[1] = z[1]; zin[2] = pr[0]; zin[3] = pr[1];
+          lx_lin<AR, 8, WH, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z(1), V16()});
+          x_gather<WH>(X, xb, z, zin);
         } else {
           // hidden layers 1, 2: silu' rows; 3: raw z rows.  z / z2 ping-pong; one hand-over more
-          lx_lin<AR, 8, 2, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(1), V16()});
-          x_swap<2>(X, xb, z, pr);
-          zin[0] = z[0]; zin[1] = z[1]; zin[2] = pr[0]; zin[3] = pr[1];
-          lx_lin<AR, 4, 2, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(2), V16()});
-          x_swap<2>(X, xb, z2, pr);
-          zin[0] = z2[0]; zin[1] = z2[1]; zin[2] = pr[0]; zin[3] = pr[1];
-          lx_lin<AR, 4, 2, false>(WB, wp, zin, z, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z(3), V16()});
-          x_swap<2>(X, xb, z, pr);
-          zin[0] = z[0]; zin[1] = z[1]; zin[2] = pr[0]; zin[3] = pr[1];
+          lx_lin<AR, 8, WH, false>(WB, wp, cat, z, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(1), V16()});
+          x_gather<WH>(X, xb, z, zin);
+          lx_lin<AR, 2 * WH, WH, false>(WB, wp, zin, z2, V16(), ring, EpiSiluSaveD{SB, RL + S::O_Z(2), V16()});
+          x_gather<WH>(X, xb, z2, zin);
+          lx_lin<AR, 2 * WH, WH, false>(WB, wp, zin, z, V16(), ring, EpiSiluSaveZ{SB, RL + S::O_Z(3), V16()});
+          x_gather<WH>(X, xb, z, zin);
         }
         const float ra = lds.res[kk][0], rbf = lds.res[kk][1] * fc;
         f32x4 xo[2] = {x[0], x[1]};
-        if constexpr (SAVEZ) lx_lin<AR, 4, 2, false>(WB, wp, zin, xn, V16(), ring, EpiResidualNS<2>{xo, ra, rbf});
-        else lx_lin<AR, 4, 2, false>(WB, wp, zin, xn, V16(), ring, EpiResidual<2>{{SB, RL + S::O_U(MD), V16()}, xo, ra, rbf});
+        if constexpr (SAVEZ) lx_lin<AR, 2 * WH, 2, false>(WB, wp, zin, xn, V16(), ring, EpiResidualNS<2>{xo, ra, rbf});
+        else lx_lin<AR, 2 * WH, 2, false>(WB, wp, zin, xn, V16(), ring, EpiResidual<2>{{SB, RL + S::O_U(MD), V16()}, xo, ra, rbf});
         x_swap<2>(X, xb, xn, pr);
         x[0] = xn[0]; x[1] = xn[1]; x[2] = pr[0]; x[3] = pr[1];
       }
@@ -472,9 +469,9 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
     }
 
     // ---------------- read-out (both waves of a pair evaluate it) ----------------
-    f32x4 upre[2], zt[2], w0pre[L * HT];
+    f32x4 upre[2], zt[WH], w0pre[L * HT];
     if constexpr (!SAVEZ) load_rows<2>(SB, S::R_LAYER(NL - 1, MD) + S::O_U(MD), upre, V16());
-    load_rows<2>(SB, S::R_LAYER(NL - 1, MD) + S::O_Z(MD), zt, V16());
+    load_rows<WH>(SB, S::R_LAYER(NL - 1, MD) + S::O_Z(MD), zt, V16());
     __builtin_amdgcn_sched_barrier(0);
     f32x4 zr[RT];
     lx_lin<AR, 4, RT, false>(WB, wp, x, zr, V16(), ring, EpiNone{});
@@ -542,15 +539,15 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
       f32x4 ds[HT];
       f32x4 P[4];            // partial latent gradient: dE/dx^{kk-1} = P(this wave) + P(partner)
       {
-        f32x4 du[4], dh[2], din[4], pr[2];
-        f32x4 rows1[2];          // silu' of the hidden layer below the last (MD >= 2), own tiles: first used one linear from here
-        if constexpr (MD >= 2) load_rows<2>(SB, RL + S::O_Z(MD - 1), rows1, V16());
+        f32x4 du[4], dh[WH], din[2 * WH];
+        f32x4 rows1[WH];         // silu' of the hidden layer below the last (MD >= 2), own tiles: first used one linear from here
+        if constexpr (MD >= 2) load_rows<WH>(SB, RL + S::O_Z(MD - 1), rows1, V16());
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (SAVEZ) {
           // the u rows are not saved (fused.hip: SAVEZ): <u, g> over this wave's hidden tiles falls out of the epilogue of the first backward linear, fed with the unscaled gradient
           const float ra = lds.res[kk][0], rb = lds.res[kk][1];
           float ug = 0.f;
-          lx_lin<AR, 4, 2, false>(WB, wp, dx, dh, V16(), ring, EpiMulSiluZ<2>{zt, rb * fc, ug});
+          lx_lin<AR, 4, WH, false>(WB, wp, dx, dh, V16(), ring, EpiMulSiluZ<WH>{zt, rb * fc, ug});
           P[0] = ra * dx[0]; P[1] = ra * dx[1];
           P[2] = f32x4{0.f, 0.f, 0.f, 0.f}; P[3] = f32x4{0.f, 0.f, 0.f, 0.f};
           dfc_part += rb * ug;
@@ -565,33 +562,27 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
           P[2] = f32x4{0.f, 0.f, 0.f, 0.f}; P[3] = f32x4{0.f, 0.f, 0.f, 0.f};
           dfc_part += rb * hsum4(accv);
           pin(dfc_part);
-          lx_lin<AR, 4, 2, false>(WB, wp, du, dh, V16(), ring, EpiMulRows<2>{zt});
+          lx_lin<AR, 4, WH, false>(WB, wp, du, dh, V16(), ring, EpiMulRows<WH>{zt});
         }
         // down the hidden layers, each split by output tile: hand-over, g_{h-1} = (g_h W_h^T) * silu'(z_{h-1}) on the own tiles
         if constexpr (MD == 2) {
-          x_swap<2>(X, xb, dh, pr);
-          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
-          lx_lin<AR, 4, 2, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<2>{rows1});
-          x_swap<2>(X, xb, dh, pr);
-          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+          x_gather<WH>(X, xb, dh, din);
+          lx_lin<AR, 2 * WH, WH, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<WH>{rows1});
+          x_gather<WH>(X, xb, dh, din);
         } else if constexpr (MD == 1) {
-          x_swap<2>(X, xb, dh, pr);
-          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+          x_gather<WH>(X, xb, dh, din);
         } else {
-          f32x4 rows0[2];      // silu' of hidden layer 1, own tiles: requested one linear ahead
-          load_rows<2>(SB, RL + S::O_Z(1), rows0, V16());
+          f32x4 rows0[WH];     // silu' of hidden layer 1, own tiles: requested one linear ahead
+          load_rows<WH>(SB, RL + S::O_Z(1), rows0, V16());
           __builtin_amdgcn_sched_barrier(0);
-          x_swap<2>(X, xb, dh, pr);
-          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
-          lx_lin<AR, 4, 2, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<2>{rows1});
-          x_swap<2>(X, xb, dh, pr);
-          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
-          lx_lin<AR, 4, 2, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<2>{rows0});
-          x_swap<2>(X, xb, dh, pr);
-          din[0] = dh[0]; din[1] = dh[1]; din[2] = pr[0]; din[3] = pr[1];
+          x_gather<WH>(X, xb, dh, din);
+          lx_lin<AR, 2 * WH, WH, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<WH>{rows1});
+          x_gather<WH>(X, xb, dh, din);
+          lx_lin<AR, 2 * WH, WH, false>(WB, wp, din, dh, V16(), ring, EpiMulRows<WH>{rows0});
+          x_gather<WH>(X, xb, dh, din);
         }
         f32x4 dcat[4];       // own x tiles (2), own scalar tiles (2)
-        lx_lin<AR, 4, 4, false>(WB, wp, din, dcat, V16(), ring, EpiNone{});
+        lx_lin<AR, 2 * WH, 4, false>(WB, wp, din, dcat, V16(), ring, EpiNone{});
         P[0] += dcat[0]; P[1] += dcat[1];
         ds[0] = dcat[2]; ds[1] = dcat[3];
       }
@@ -710,7 +701,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
         lx_prime<AR>(WB, wp, V16(), ring);
         if (kk > 0) {
           if constexpr (!SAVEZ) load_rows<2>(SB, S::R_LAYER(kk - 1, MD) + S::O_U(MD), upre, V16());
-          load_rows<2>(SB, S::R_LAYER(kk - 1, MD) + S::O_Z(MD), zt, V16());
+          load_rows<WH>(SB, S::R_LAYER(kk - 1, MD) + S::O_Z(MD), zt, V16());
         } else load_rows<L * HT>(SB, S::R_W0 + HT, w0pre, V16());
         __builtin_amdgcn_sched_barrier(0);
         lx_lin<AR, EWH, 4, true>(WB, wp, dom, P, V16(), ring, EpiNone{});      // split by input tile: partial sums over the own channels
@@ -862,14 +853,21 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
 }
 
 // ---------------------------------------------------------------------------- host side
-// This file is compiled three times (Makefile): AHIP_LX_PART 0 = the host side and the read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone (fused_lx2_r.o),
-// 2 = the read-out-width-64 instances alone (fused_lx2_q.o)
+// This file is compiled four times (Makefile): AHIP_LX_PART 0 = the host side and the read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone (fused_lx2_r.o),
+// 2 = the read-out-width-64 instances alone (fused_lx2_q.o), 3 = the MLP-width-128 instances alone (fused_lx2_m.o)
 #ifndef AHIP_LX_PART
 #define AHIP_LX_PART 0
 #endif
 void fusedlx2_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
 void fusedlx2_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
-#if AHIP_LX_PART == 2
+void fusedlx2_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
+#if AHIP_LX_PART == 3
+void fusedlx2_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // WH = 4: f16x2 only, read-out depth 1, read-out width 32, plain and per-atom virial, not profiled
+  dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    hipLaunchKernelGGL((k_fused_lx2<nl, false, 3, v == VAR_VA, md, 1, 2, 4>), dim3(grid), dim3(ShapeP::NW * 64), 0, s, A);
+  }, nl, var, md);
+}
+#elif AHIP_LX_PART == 2
 void fusedlx2_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // RT = 4: f16x2 only, read-out depth 1, plain and per-atom virial, not profiled
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
     hipLaunchKernelGGL((k_fused_lx2<nl, false, 3, v == VAR_VA, md, 1, 4>), dim3(grid), dim3(ShapeP::NW * 64), 0, s, A);
@@ -897,6 +895,7 @@ static std::vector<double> gather_tiles(const double *W, int ldw, const std::vec
 static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h, Arith arith) {
   using S = ShapeP;
   const int RF = h.readout_width;                     // read-out width at the kernel's shape: 32 or 64 (fused_shapes.h: FUSED_RF, FUSED_RF2)
+  const int W = h.mlp_width, WH = W / 32;             // hidden width at the kernel's shape: 64 or 128 (FUSED_WF, FUSED_WF2); WH: the 16-feature hidden tiles a wave owns
   std::vector<int> rt_all;                            // every 16-feature tile of the read-out's hidden layer: both waves of a pair evaluate it whole
   for (int t = 0; t < RF / 16; ++t) rt_all.push_back(t);
   const int NL = h.num_layers, MD = h.mlp_depth, U = S::U, D = S::D, UT = S::UT;      // latent MLP: lat.w0, hidden lat.w1 .. lat.w{MD-1}, output linear lat.w{MD}
@@ -907,6 +906,9 @@ static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h,
     auto par = [&](int t) { return 2 * (1 - hf) + t; };
     const std::vector<int> xo = {own(0), own(1), par(0), par(1)};          // latent / 64-wide hidden tiles: own first
     const std::vector<int> ownt = {own(0), own(1)};
+    std::vector<int> hx, ownh;                                              // hidden tiles, own first (local tile k = global tile (k + WH hf) mod 2 WH), and the own ones; W = 64: xo and ownt
+    for (int t = 0; t < 2 * WH; ++t) hx.push_back((t + WH * hf) % (2 * WH));
+    for (int t = 0; t < WH; ++t) ownh.push_back(WH * hf + t);
     std::vector<int> lu;                                                    // own tiles of an (l, u) weight vector: [l][own t]
     for (int l = 0; l <= S::L; ++l)
       for (int t = 0; t < S::HT; ++t) lu.push_back(l * UT + own(t));
@@ -930,8 +932,8 @@ static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h,
     for (int k = 0; k < NL; ++k) {
       const std::string lk = "l" + std::to_string(k + 1);
       put(T_(lk + ".env"), U * 3, xo, lu);
-      put(T_(lk + ".lat.w0"), 64, cat_rows, ownt);
-      for (int hl = 1; hl <= MD; ++hl) put(T_(lk + ".lat.w" + std::to_string(hl)), 64, xo, ownt);      // every 64 -> 64 linear: inputs own tiles first, own output tiles
+      put(T_(lk + ".lat.w0"), W, cat_rows, ownh);                                                        // [128][W] -> [W][W] .. -> [W][64]: inputs own tiles first, own output tiles
+      for (int hl = 1; hl <= MD; ++hl) put(T_(lk + ".lat.w" + std::to_string(hl)), hl < MD ? W : 64, hx, hl < MD ? ownh : ownt);
       if (k < NL - 1) {
         const double *mx = T_(lk + ".mix");            // [L+1][U][U]; block l serves its 2l+1 components
         for (int lm = 0; lm < D; ++lm) put(mx + (size_t)l_of_lm(lm) * U * U, U, xo, ownt);
@@ -945,8 +947,8 @@ static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h,
     putT(T_("out.w0"), 64, RF, rt_all, xo);
     for (int k = NL - 1; k >= 0; --k) {
       const std::string lk = "l" + std::to_string(k + 1);
-      for (int hl = MD; hl >= 1; --hl) putT(T_(lk + ".lat.w" + std::to_string(hl)), 64, 64, xo, ownt);
-      putT(T_(lk + ".lat.w0"), 64 + U, 64, xo, cat_cols);
+      for (int hl = MD; hl >= 1; --hl) putT(T_(lk + ".lat.w" + std::to_string(hl)), W, hl < MD ? W : 64, hl < MD ? hx : xo, ownh);      // the transposed blocks: gradient tiles own first, own hidden tiles out
+      putT(T_(lk + ".lat.w0"), 64 + U, W, hx, cat_cols);
       if (k < NL - 1) {
         const double *mx = T_(lk + ".mix");
         for (int lm = 0; lm < D; ++lm) putT(mx + (size_t)l_of_lm(lm) * U * U, U, U, xo, ownt);
@@ -961,12 +963,17 @@ static int lx2_stream(std::vector<float> &w, FusedLxArgs &A, const HostModel &h,
 
 bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
   if (!lx_list_fits(m, why)) return false;
-  FusedLxState &st = lx_prepare<ShapeP>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream);     // path weights x the path's base |c| (tp_g)
+  const bool w128 = fused_WF(m.hm) == FUSED_WF2;       // MLP width 65..128 (option lx64_mlp_width=auto: the gate refuses it otherwise): the WH = 4 instances, whose row map sizes the per-wave scratch
+  FusedLxState &st = w128 ? lx_prepare<ShapePW<4>>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream)
+                          : lx_prepare<ShapeP>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream);     // path weights x the path's base |c| (tp_g)
   static_assert(PP_N == LX_NPHASE, "profile phases");
   if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
   if (st.rt != 2 && !(st.rt == 4 && st.arith == AR_F16X2 && st.rd == 1))
     throw UnsupportedError("wide fused kernels: read-out width 33..64 has f16x2 instances with read-out depth 1 only");      // (likewise)
+  if (st.ht != 4 && !(st.ht == 8 && fused_lx64_w128(m) && st.arith == AR_F16X2 && st.rd == 1 && st.rt == 2))
+    throw UnsupportedError("wide fused kernels: MLP width 65..128 with 33..64 tensor features has f16x2 instances with read-out depth 1 and read-out width <= 32 only, behind option lx64_mlp_width=auto");      // (likewise)
   lx_run<ShapeP>(m, a, st, "fused_lx2", [&](const FusedLxArgs &A, int grid, int var, int) {
+    if (st.ht == 8) { fusedlx2_launch_m(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_m.o
     if (st.rt == 4) { fusedlx2_launch_q(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_q.o
     if (st.rd == 2) { fusedlx2_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_r.o
     dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {

@@ -6,7 +6,7 @@
 //   d x0/dd 4 | w0 EW | per layer: omega EW | hidden layer 1..MD, HR rows each | u UR | V_in NV
 // Hidden layers 1..MD-1 hold silu'(z); the last one holds silu'(z) on the f32 instances and the raw z on the f16x2 instances (which then leave the u rows unused).
 // MD = 2 gives the maps the kernels have had since round 6.  UR (rows of the layer's output u, 64 scalars wide) defaults to HR: the two differ only on the MLP-width-128
-// instances of k_fused_lx, whose hidden layers are 8 rows and whose u stays 4 (RowsXM).
+// instances of k_fused_lx, whose hidden layers are 8 rows and whose u stays 4 (RowsXM), and on those of k_fused_lx2: 4 own rows per hidden layer, u 2 (RowsPM).
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -35,5 +35,7 @@ using RowsX = LxRows<6, 4, 18>;
 using RowsXM = LxRows<6, 8, 18, 4>;
 // k_fused_lx2: l_max = 2, 64 tensor features over a wave pair: each wave holds 3 x 2 own tiles, 2 own rows per hidden layer, 9 x 2 own tensor rows
 using RowsP = LxRows<6, 2, 18>;
+// ... with 128-wide hidden layers (4 own rows each; u stays at 2 own rows): R_TOTAL(NL, MD) = 10 + NL (26 + 4 MD), 124 rows for 3 layers at depth 3 against 106
+using RowsPM = LxRows<6, 4, 18, 2>;
 
 }  // namespace ahip

@@ -7,17 +7,19 @@
 //   k_fused   k_fused       l_max 1, 32 features      l_max = 1, U <= 32
 //   lx32      k_fused_lx    l_max 2, 32 features      l_max = 2, U <= 32
 //   lx64      k_fused_lx2   l_max 2, 64 features      l_max = 2, 33 <= U <= 64;  l_max = 1, 33 <= U <= 64 (lifted: model_io.h, lift_host_model)
-// all with S <= 64 scalars, MLP width <= 64 (k_fused and lx32 also 65..128: the width classes below), read-out width <= 64 (two width classes, below; narrower models run zero-padded: pad_host_model), 1..3 layers, <= 16 ACTIVE types.
+// all with S <= 64 scalars, MLP width <= 64 (k_fused and lx32 also 65..128, lx64 behind option lx64_mlp_width=auto: the width classes below), read-out width <= 64 (two width classes, below; narrower models run zero-padded: pad_host_model), 1..3 layers, <= 16 ACTIVE types.
 //
 // Width classes of the latent MLP (WF = the hidden width an instance runs at; the two-body MLP shares the model's mlp_width and is tabulated on the host):
 //   WF = 64    mlp_width <= 64          every family, every instance below
 //   WF = 128   65 <= mlp_width <= 128   k_fused and lx32 only, zero-padded to 128: f16x2 arithmetic (k_fused: with the tabulated two-body embedding), MLP depth 1..3,
 //                                       read-out depth 1, plain and per-atom-virial variants, both tile shapes of k_fused, the 64-slot shape of k_fused_lx
+//              the same                 lx64 behind option lx64_mlp_width=auto (the gates' trailing argument lx64_w128; default "64": refused): the same limits,
+//                                       allow_tf32 = 0, the one tile shape of k_fused_lx2
 // Width classes of the read-out MLP (RF = the width its hidden layers run at):
 //   RF = 32    readout_width <= 32          every family, every instance above
 //   RF = 64    33 <= readout_width <= 64    every family, zero-padded to 64: f16x2 arithmetic (k_fused: with the tabulated two-body embedding), MLP width <= 64 (WF = 64), MLP depth 1..3,
 //                                           read-out depth 1, plain and per-atom-virial variants, both tile shapes of k_fused, the 64-slot shape of k_fused_lx, the one shape of k_fused_lx2
-// S and the tensor features have one class each; lx64 (33..64 tensor features) has no WF = 128 instance; no instance combines WF = 128 with RF = 64.
+// S and the tensor features have one class each; lx64 (33..64 tensor features) runs its WF = 128 instances under option lx64_mlp_width=auto only; no instance combines WF = 128 with RF = 64.
 //
 // Active types: the model types the caller's type mapping can produce (engine.h: Model::active).  A fused evaluation runs on the model restricted to them
 // (model_io.h: subset_host_model; compact slots 0 .. A - 1 in ascending model-type order, 4 bits each in the packed edge types), so the gates count A, not the
@@ -80,13 +82,13 @@ inline HostModel fused_shaped_model(const HostModel &h, FusedFamily f, int WF = 
 }
 
 // a compiled instance of family f exists for this arithmetic (k_fused: and two-body mode) and these depths
-// (WF: the width class of the latent MLP; the WF = 128 instances: k_fused and lx32, f16x2, read-out depth 1.  RF: the width class of the read-out MLP; the RF = 64
+// (WF: the width class of the latent MLP; the WF = 128 instances: k_fused and lx32 -- lx64 too where lx64_w128 says so (option lx64_mlp_width=auto) --, f16x2, read-out depth 1.  RF: the width class of the read-out MLP; the RF = 64
 // instances: every family, f16x2, WF = 64, read-out depth 1)
-inline bool fused_instance_exists(FusedFamily f, Arith ar, bool tb_table, int MD, int RD, int WF = FUSED_WF, int RF = FUSED_RF) {
+inline bool fused_instance_exists(FusedFamily f, Arith ar, bool tb_table, int MD, int RD, int WF = FUSED_WF, int RF = FUSED_RF, bool lx64_w128 = false) {
   if (f == FusedFamily::none || MD < 1 || MD > 3 || RD < 1 || RD > 2) return false;
   if (RF == FUSED_RF2) return WF == FUSED_WF && ar == AR_F16X2 && RD == 1 && (fused_is_wide(f) || tb_table);
   if (RF != FUSED_RF) return false;
-  if (WF == FUSED_WF2) return (f == FusedFamily::k_fused || f == FusedFamily::lx32) && ar == AR_F16X2 && RD == 1 && (fused_is_wide(f) || tb_table);
+  if (WF == FUSED_WF2) return (f == FusedFamily::k_fused || f == FusedFamily::lx32 || (f == FusedFamily::lx64 && lx64_w128)) && ar == AR_F16X2 && RD == 1 && (fused_is_wide(f) || tb_table);
   if (WF != FUSED_WF) return false;
   if (MD == 2 && RD == 1) return fused_is_wide(f) ? (ar == AR_F32 || ar == AR_F16X2) : (ar != AR_F16X2 || tb_table);
   return ar == AR_F16X2 && (fused_is_wide(f) || tb_table);
@@ -110,6 +112,10 @@ inline constexpr const char *FUSED_WHY_W128_ARITH_WIDE = "MLP width 65..128 runs
 inline constexpr const char *FUSED_WHY_W128_RD = "MLP width 65..128 runs with read-out depth 1 only on the fused kernels (read-out depth 2 has instances of MLP width <= 64 only)";
 inline constexpr const char *FUSED_WHY_W128_LX64 =
     "MLP width 65..128 has no instance of the wide fused kernel for 33..64 tensor features (k_fused_lx2 holds MLP width 64; k_fused and k_fused_lx hold 128 with up to 32 tensor features)";
+// ... behind option lx64_mlp_width=auto: a TF32-licensed model stays refused.  The first-evaluation self-check of fused_arith=auto does not run for such a model
+// (allegro_hip.hip: run_model), and these f16x2-only instances have no float32 twin to be compared with or to fall back to but the layer-at-a-time kernels.
+inline constexpr const char *FUSED_WHY_W128_LX64_TF32 =
+    "MLP width 65..128 with 33..64 tensor features (option lx64_mlp_width=auto) runs on the f16x2 arithmetic for models with allow_tf32 = 0 only";
 
 // the refusals of the RF = 64 width class of the read-out
 inline constexpr const char *FUSED_WHY_R64_ARITH_NARROW =
@@ -168,8 +174,9 @@ inline bool fused_narrow_supported(const HostModel &h, Arith arith, bool tb_tabl
   return true;
 }
 
-// the wide kernels' gate: `arith` is what the options resolve to on them (resolve_arith, wide = true)
-inline bool fused_wide_supported(const HostModel &h, Arith arith, std::string *why, int n_active = -1) {
+// the wide kernels' gate: `arith` is what the options resolve to on them (resolve_arith, wide = true); lx64_w128: option lx64_mlp_width=auto (the WF = 128
+// instances of k_fused_lx2; a caller that leaves it out gets the default of the option, "64")
+inline bool fused_wide_supported(const HostModel &h, Arith arith, std::string *why, int n_active = -1, bool lx64_w128 = false) {
   auto no = [&](const char *msg) { if (why) *why = msg; return false; };
   if (h.l_max != 2 && !(h.l_max == 1 && h.U > 32)) return no("wide fused kernels are built for l_max = 2 (an l_max = 1 model runs on them lifted when it has 33..64 tensor features)");
   if (!fused_widths_fit(h, true, FUSED_WF2, FUSED_RF2))
@@ -180,8 +187,11 @@ inline bool fused_wide_supported(const HostModel &h, Arith arith, std::string *w
     if (arith != AR_F16X2) return no(FUSED_WHY_R64_ARITH_WIDE);
     if (h.readout_depth != 1) return no(FUSED_WHY_R64_RD);
   }
-  if (fused_WF(h) == FUSED_WF2) {   // the wider hidden layers: k_fused_lx only (template parameter HT), f16x2, read-out depth 1
-    if (fused_shape_class(h) != FusedFamily::lx32) return no(FUSED_WHY_W128_LX64);
+  if (fused_WF(h) == FUSED_WF2) {   // the wider hidden layers: k_fused_lx (template parameter HT), k_fused_lx2 behind its option (template parameter WH), f16x2, read-out depth 1
+    if (fused_shape_class(h) != FusedFamily::lx32) {
+      if (!lx64_w128) return no(FUSED_WHY_W128_LX64);
+      if (h.allow_tf32) return no(FUSED_WHY_W128_LX64_TF32);
+    }
     if (arith != AR_F16X2) return no(FUSED_WHY_W128_ARITH_WIDE);
     if (h.readout_depth != 1) return no(FUSED_WHY_W128_RD);
   }
@@ -206,18 +216,18 @@ struct FusedDecision {
   Arith arith = AR_F32;
   std::string why;
 };
-inline FusedDecision fused_decide(const HostModel &h, Arith arith_narrow, Arith arith_wide, bool tb_table, int n_active = -1) {
+inline FusedDecision fused_decide(const HostModel &h, Arith arith_narrow, Arith arith_wide, bool tb_table, int n_active = -1, bool lx64_w128 = false) {
   FusedDecision d;
   std::string why1, why2;
   if (fused_narrow_supported(h, arith_narrow, tb_table, &why1, n_active)) { d.family = FusedFamily::k_fused; d.arith = arith_narrow; }
-  else if (fused_wide_supported(h, arith_wide, &why2, n_active)) { d.family = fused_shape_class(h); d.arith = arith_wide; }
+  else if (fused_wide_supported(h, arith_wide, &why2, n_active, lx64_w128)) { d.family = fused_shape_class(h); d.arith = arith_wide; }
   else { d.why = why1 + "; " + why2; return d; }
   d.l_run = fused_l_run(d.family); d.UF = fused_UF(d.family); d.WF = fused_WF(h); d.RF = fused_RF(h);
   return d;
 }
 // the same from an effective option (arith_effective) and the state of fused_arith=auto
-inline FusedDecision fused_decide(const HostModel &h, ArithOpt opt, bool degraded, bool force_f32, bool tb_table, int n_active = -1) {
-  return fused_decide(h, resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, false), resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, true), tb_table, n_active);
+inline FusedDecision fused_decide(const HostModel &h, ArithOpt opt, bool degraded, bool force_f32, bool tb_table, int n_active = -1, bool lx64_w128 = false) {
+  return fused_decide(h, resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, false), resolve_arith(opt, h.allow_tf32 != 0, degraded, force_f32, tb_table, true), tb_table, n_active, lx64_w128);
 }
 
 }  // namespace ahip

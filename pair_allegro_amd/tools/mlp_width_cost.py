@@ -1,15 +1,18 @@
 """What a latent MLP of width 128 costs on the fused kernels, and what the fused kernels save such a model, on the device-resident call (ahip_compute_dev).
 
    python pair_allegro_amd/tools/mlp_width_cost.py [--configs 2,6:24] [--warmup 5] [--calls 20] [--out profiles/mlp_width_cost.txt]          (GPU box)
+   python pair_allegro_amd/tools/mlp_width_cost.py --configs 5:24 --out profiles/lx64_mlp_width_cost.txt                                     (the k_fused_lx2 case)
 
 Per box (bench.py workloads, `config[:cells per side]`: 2 = 10 648-atom bulk Si, model S on k_fused; 6:24 = 41 472-atom water of 24^3 molecules, the reference YAML's
-shape with 32 tensor features on k_fused_lx; 6 alone is bench.py's 499 125-atom box), three models at fixed positions on one GPU:
+shape with 32 tensor features on k_fused_lx; 6 alone is bench.py's 499 125-atom box; 5:24 = the same 41 472-atom box with model L, 64 tensor features, on k_fused_lx2,
+whose width-128 instances sit behind option lx64_mlp_width=auto: the tool sets it on the "W = 128 fused" model of such a shape), three models at fixed positions on one GPU:
    W = 64   fused             the model as bench.py builds it
    W = 128  fused             the same with mlp_width = 128 (the WT / HT = 8 instances)
    W = 128  path=generic      that file on the layer-at-a-time float32 kernels: what a model wider than 64 ran on before those instances existed
 The three are called ALTERNATELY (one call of each per round, after `warmup` rounds), so clock and thermal drift hit them alike; per mode the median over `calls` rounds of
 the host wall clock around the call (device synchronised after each) and the model kernel's own time where there is one (stage "model_fused", HIP events on the launch
-stream).  Prints the ratios generic / fused at W = 128 and fused W = 128 / fused W = 64, and one JSON line per box."""
+stream).  Prints the ratios generic / fused at W = 128 and fused W = 128 / fused W = 64, the run-to-run spread of every mode over the alternated calls (max - min and
+the 10th..90th percentile range) and whether the fused W = 128 model beats path=generic on the same file by more than the larger spread, and one JSON line per box."""
 import argparse
 import json
 import os
@@ -45,6 +48,8 @@ def one_config(lib, config, ncell, warmup, calls, emit):
             model.set_option("timing", "1")
             if path_opt:
                 model.set_option("path", path_opt)
+            elif width > 64 and cfg["num_tensor_features"] > 32:
+                model.set_option("lx64_mlp_width", "auto")        # the width-128 instances of k_fused_lx2 are opt-in (csrc/fused_shapes.h)
             backend = md.HipBackend(model, wl["masses"])
             vel = np.zeros((len(wl["pos"]), 3))
             sim = md.Simulation(backend, np.diag(wl["cell"]), cfg["r_max"], 1.0, wl["pos"], wl["mtype"], vel, device, dt=0.001, overlap=False)
@@ -73,8 +78,10 @@ def one_config(lib, config, ncell, warmup, calls, emit):
             model = r["model"]
             st, cnt = model.timings_and_counts()
             out[r["key"]] = dict(path=model.last_path, edges=model.nedges(), call_ms_median=float(np.median(r["wall"])), call_ms_min=float(np.min(r["wall"])),
+                                 call_ms_max=float(np.max(r["wall"])), call_ms_p10=float(np.percentile(r["wall"], 10)), call_ms_p90=float(np.percentile(r["wall"], 90)),
                                  model_ms=st.get("model_fused", 0.0) / max(cnt.get("model_fused", 1), 1))
-            emit(f"config {config} {r['key']:13s} path {model.last_path:12s} edges {model.nedges()} call {np.median(r['wall']):9.3f} ms (min {np.min(r['wall']):.3f})"
+            emit(f"config {config} {r['key']:13s} path {model.last_path:12s} edges {model.nedges()} call {np.median(r['wall']):9.3f} ms (min {np.min(r['wall']):.3f}, max {np.max(r['wall']):.3f},"
+                 f" p10..p90 {np.percentile(r['wall'], 10):.3f}..{np.percentile(r['wall'], 90):.3f})"
                  f"  model kernel {out[r['key']]['model_ms']:.3f} ms")
             model.close()
         del runs
@@ -84,6 +91,12 @@ def one_config(lib, config, ncell, warmup, calls, emit):
     out["fused_W128_over_W64_kernel"] = out["W128_fused"]["model_ms"] / out["W64_fused"]["model_ms"] if out["W64_fused"]["model_ms"] > 0 else float("nan")
     emit(f"config {config}: at W = 128 the layer-at-a-time kernels take {out['generic_over_fused_W128']:.2f} x the fused call; fused W = 128 takes "
          f"{out['fused_W128_over_W64']:.2f} x fused W = 64 (model kernel alone: {out['fused_W128_over_W64_kernel']:.2f} x)")
+    # the run-to-run spread over the alternated calls (max - min of a mode, the larger of the two modes compared) against the margin of the fused model over path=generic
+    out["spread_ms"] = max(out[k]["call_ms_max"] - out[k]["call_ms_min"] for k in ("W128_fused", "W128_generic"))
+    out["margin_ms"] = out["W128_generic"]["call_ms_median"] - out["W128_fused"]["call_ms_median"]
+    out["fused_beats_generic_beyond_spread"] = bool(out["W128_fused"]["path"].startswith("fused") and out["margin_ms"] > out["spread_ms"])
+    emit(f"config {config}: fused W = 128 is {out['margin_ms']:.3f} ms per call ahead of path=generic on the same file; run-to-run spread {out['spread_ms']:.3f} ms: "
+         f"{'beats it by more than the spread' if out['fused_beats_generic_beyond_spread'] else 'DOES NOT beat it by more than the spread'}")
     emit(json.dumps(out))
     return out
 
