@@ -108,6 +108,11 @@ int ahip_model_meta(const ahip_model *m, double *r_max, int *num_types, const ch
  *                                                 option).  For every other model (MLP width up to 64, up to 32 tensor features) "auto" changes nothing.  Measured on one
  *                                                 box and one model shape only (41 472-atom water, model L with 64 tensor features: tools/mlp_width_cost.py --configs 5:24,
  *                                                 profiles/lx64_mlp_width_cost.txt), which is why the default stays "64".
+ *   "env_backward" = "auto" | "centre" | "edge"  the transposed environment linear of k_fused's backward pass (l_max = 1 kernel, f16x2 arithmetic, 64-slot tiles): "auto"
+ *                                                 (default) evaluates it once per centre atom on tiles of up to 3 centres (one wave of the tile runs it on the centre's reduced
+ *                                                 gradient, every edge combines four vectors: DESIGN 4.2g) and per edge on tiles of 4..6 centres; "centre" is the same rule
+ *                                                 (tiles of more than 3 centres have no per-centre form); "edge" evaluates it per edge on every tile, as every other
+ *                                                 arithmetic, tile shape and kernel does.  The two forms differ in rounding order only.  For A/B runs and tests.
  *   "timing"    = "0" | "1"                      record per-stage HIP events (ahip_get_timings)
  * Unknown keys and values are errors (AHIP_ERR_ARG).
  */

@@ -332,6 +332,8 @@ int ahip_set_option(ahip_model *m, const char *key, const char *value) {
     } else if (k == "lx64_mlp_width") {
       const Model::Lx64MlpWidth o = (Model::Lx64MlpWidth)word(Model::LX64_MLP_WIDTH_WORDS);
       if (o != m->opt_lx64_mlp_width) { m->opt_lx64_mlp_width = o; fusedlx_free(*m); }      // the per-wave scratch follows the row map of the instances the option admits (lx_prepare)
+    } else if (k == "env_backward") {
+      m->opt_env_backward = (Model::EnvBackward)word(Model::ENV_BACKWARD_WORDS);
     } else if (k == "timing") {
       m->timing = (v == "1" || v == "on" || v == "true");
     } else throw ArgError("unknown option '" + k + "'");

@@ -119,6 +119,8 @@ struct Model {
   static constexpr const char *WIDE_TILE_WORDS = "64|auto";
   enum class Lx64MlpWidth { W64, Auto };
   static constexpr const char *LX64_MLP_WIDTH_WORDS = "64|auto";
+  enum class EnvBackward { Auto, Centre, Edge };
+  static constexpr const char *ENV_BACKWARD_WORDS = "auto|centre|edge";
   Path opt_path = Path::Auto;
   Precision opt_precision = Precision::Model;
   FusedTb opt_fused_tb = FusedTb::Table;    // table | mlp: two-body embedding of the fused kernel from the spline table or as an MLP
@@ -148,6 +150,7 @@ struct Model {
   DenseCentres opt_dense_centres = DenseCentres::Whole;   // whole | split: a list with a few centres above a fused kernel's tile goes to the layer-at-a-time kernels as a whole, or only those centres do (allegro_hip.hip: run_model_once)
   WideTile opt_wide_tile = WideTile::S64;                 // 64 | auto: k_fused_lx on 64-slot tiles only, or on its 128-slot shape when the list's largest degree asks for it (fused_shapes.h: fused_has_wide_tile)
   Lx64MlpWidth opt_lx64_mlp_width = Lx64MlpWidth::W64;    // 64 | auto: k_fused_lx2 (33..64 tensor features) at MLP width <= 64 only, or also on its MLP-width-128 instances for mlp_width 65..128 (fused_shapes.h: the gates' lx64_w128)
+  EnvBackward opt_env_backward = EnvBackward::Auto;       // auto | centre | edge: k_fused's transposed environment linear once per centre on tiles of <= 3 centres (f16x2, 4-wave tiles: the instances that have the form; auto and centre are the same rule), or per edge on every tile (fused.hip: FusedArgs::env_bwd; a kernel argument, no state depends on it)
   bool cutoff_strict = false;               // edge kept iff rsq < cut^2 (the KOKKOS reference path) instead of rsq <= cut^2 (the host path)
 
   // weights

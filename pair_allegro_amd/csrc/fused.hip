@@ -100,6 +100,7 @@ struct FusedArgs {
   float cp[6];                            // cutoff polynomial: a, b, c of f = 1 - a x^p + b x^(p+1) - c x^(p+2) and a p, b (p + 1), c (p + 2) of its derivative (scalar registers, not per-lane values held over a tile)
   int *err;                               // host-mapped word: set when an edge gradient comes out non-finite (float16 range exceeded)
   double *vatom;                          // [nall][9] per-atom virial (the VA instances only)
+  int env_bwd;                            // option env_backward (Model::EnvBackward): 0 auto, 1 centre, 2 edge -- the environment backward linear once per centre or per edge
 };
 
 template <int NW, int NL = MAXNL, int RT = 2> struct __attribute__((aligned(16))) Lds {
@@ -287,8 +288,9 @@ template <int AR> struct RingT {
   u32x4 b[AR == 0 ? 1 : (AR == 1 ? RINGB : AR == 2 ? RINGB2 : RINGH)];
 };
 // BR = false: the caller has tested ring.act itself, around a PAIR of one-step linears (see lin_mix).
+// jump: f16x2 only, see linear_h (the stream jump over a linear this wave will skip).
 template <int AR, int KT, int NT, bool ACC, int RPI, bool BR = true, class Epi>
-__device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in)[KT], f32x4 (&out)[NT], int v16, RingT<AR> &ring, Epi epi) {
+__device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in)[KT], f32x4 (&out)[NT], int v16, RingT<AR> &ring, Epi epi, int jump = 0) {
   if (BR && !ring.act) {             // (uniform) a wave without edges in this tile: no fragments, no MFMAs, no epilogue; finite outputs for the arithmetic around the linears
     if constexpr (!ACC) {
 #pragma unroll
@@ -302,7 +304,7 @@ __device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32
 #pragma unroll
     for (int ks = 0; ks < KT / 2; ++ks) b[0][ks] = split_pair_h(in[2 * ks], in[2 * ks + 1]);
     Epi ep[1] = {epi};
-    linear_h<1, KT / 2, NT, ACC, false, (4 * RPI) % RINGH, Epi, true>(W, wp, b, reinterpret_cast<f32x4 (&)[1][NT]>(out), unused, v16, ring.b, ep);
+    linear_h<1, KT / 2, NT, ACC, false, (4 * RPI) % RINGH, Epi, true>(W, wp, b, reinterpret_cast<f32x4 (&)[1][NT]>(out), unused, v16, ring.b, ep, jump);
   } else if constexpr (AR != 0) {
     static_assert(KT % 2 == 0, "K-steps are pairs of 16-feature tiles");
     constexpr int NTERM = AR == 1 ? 3 : 2;
@@ -321,7 +323,7 @@ __device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32
 // 8 KiB of fragments fewer per mixing block and direction and wave-tile.
 template <int RPI, bool BR = true, class Epi>
 __device__ __forceinline__ void lin_m3(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in0)[2], const f32x4 (&in1)[2], const f32x4 (&in2)[2], f32x4 (&out)[3][2], int v16,
-                                       RingT<3> &ring, Epi (&epi)[3]) {
+                                       RingT<3> &ring, Epi (&epi)[3], int jump = 0) {
   if (BR && !ring.act) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) { out[q][0] = f32x4{0.f, 0.f, 0.f, 0.f}; out[q][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -329,7 +331,7 @@ __device__ __forceinline__ void lin_m3(__amdgpu_buffer_rsrc_t W, int &wp, const 
   }
   Hop b[3][1], unused[3][1];
   b[0][0] = split_pair_h(in0[0], in0[1]); b[1][0] = split_pair_h(in1[0], in1[1]); b[2][0] = split_pair_h(in2[0], in2[1]);
-  linear_h<3, 1, 2, false, false, (4 * RPI) % RINGH, Epi, true>(W, wp, b, out, unused, v16, ring.b, epi);
+  linear_h<3, 1, 2, false, false, (4 * RPI) % RINGH, Epi, true>(W, wp, b, out, unused, v16, ring.b, epi, jump);
 }
 // A channel mixing on the f16x2 arithmetic is two ONE-step linears (the l = 0 block, then lin_m3).  They share one `ring.act` branch: a region that consumes a whole
 // ring (two steps) leaves every slot at the age it had on entry, whichever way the branch went.  With a branch each, the path "first skipped, second taken" -- which
@@ -337,15 +339,15 @@ __device__ __forceinline__ void lin_m3(__amdgpu_buffer_rsrc_t W, int &wp, const 
 // queue, and its first products wait behind s_waitcnt vmcnt(3..2) for everything older.
 template <class Epi0, class Epi3>
 __device__ __forceinline__ void lin_mix(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in0)[2], const f32x4 (&in1)[2], const f32x4 (&in2)[2], const f32x4 (&in3)[2], f32x4 (&out0)[2],
-                                        f32x4 (&out)[3][2], int v16, RingT<3> &ring, Epi0 epi0, Epi3 (&epi)[3]) {
+                                        f32x4 (&out)[3][2], int v16, RingT<3> &ring, Epi0 epi0, Epi3 (&epi)[3], int jump = 0) {
   if (!ring.act) {
     out0[0] = f32x4{0.f, 0.f, 0.f, 0.f}; out0[1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int q = 0; q < 3; ++q) { out[q][0] = f32x4{0.f, 0.f, 0.f, 0.f}; out[q][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     return;
   }
-  lin<3, 2, 2, false, 0, false>(W, wp, in0, out0, v16, ring, epi0);
-  lin_m3<1, false>(W, wp, in1, in2, in3, out, v16, ring, epi);
+  lin<3, 2, 2, false, 0, false>(W, wp, in0, out0, v16, ring, epi0, jump);       // (both one-step linears request fragments of the linear behind the pair)
+  lin_m3<1, false>(W, wp, in1, in2, in3, out, v16, ring, epi, jump);
 }
 
 // MD: hidden layers of the latent MLP (allegro_mlp_hidden_layers_depth of /root/reference/tests/test_data/test_repro_allegro.yaml:94; 2 there).  1 and 3 exist for the
@@ -450,7 +452,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     for (int k = 0; k < PH_N; ++k) pacc[k] = 0;
     tprev = clock64();
   }
-  float *const pk = lds.park[wave];
+  float *const pk0 = lds.park[wave];
   RingT<AR> ring;                              // the weight-fragment stream (see linear_s / linear_b)
   int wp = A.o_stream;
   if constexpr (AR != 0) ring_prime_b(WB, wp, v16, ring.b);
@@ -502,10 +504,32 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     // a condition that is always true (profiles/r05_w_last_experiments.md §6): a wave-uniform branch around each linear makes it a scheduling / allocation region of
     // its own (spills of the headline instance 304 -> 120 B per lane).  The wide kernels lose with the same branch (fused_lx2: 20.3 -> 21.9 ms): their linears are
     // ordered by hand across each other.
-    const int wact = __builtin_amdgcn_readfirstlane(e0 + wave * 16 < e1 ? 1 : 0);
+    // (the per-centre instances, CEN below, form the wave index per tile, as a scalar, from an opaque copy of the thread index: what hangs on it -- the slot range, the
+    // park rows, the table offset, the virial partials -- is then not held across the tile loop; with the per-centre form in the kernel those four values went to scratch)
+    constexpr bool CEN = AR == 3 && NW == 4;
+    int tq = tid, lq_ = lane, wvq = wave;
+    if constexpr (CEN) {
+      asm volatile("" : "+v"(tq));
+      wvq = __builtin_amdgcn_readfirstlane(tq >> 6);
+      lq_ = tq & 63;
+    }
+    float *const pk = CEN ? lds.park[wvq] : pk0;
+    const int wact = __builtin_amdgcn_readfirstlane(e0 + wvq * 16 < e1 ? 1 : 0);
     ring.act = wact;
     const int v16t = wact ? v16 : 0x7ffffff0;
     const int na = a1 - a0;
+    // Environment backward once per CENTRE (f16x2, 4 waves).  The transposed environment linear acts on dom_e = [d0_i ; Y1_e d1_i + Y2_e d2_i + Y3_e d3_i], and
+    // d0..d3 (lds.denv) belong to the centre: dom_e W^T = P0_i + Y1_e P1_i + Y2_e P2_i + Y3_e P3_i with four 64-vectors P per centre.  A tile of <= 3 centres has
+    // <= 12 of them, one wave's 16 MFMA columns: wave 0 (which always holds edges) runs the linear on them, the other waves skip it -- 16 KiB of fragments and 48 MFMAs
+    // fewer per wave and layer -- and every lane combines its centre's four vectors from LDS.  Tiles of 4..6 centres take the per-edge linear.
+    // cen (wave-uniform): 0 per edge; 1 this wave computes P; 2 this wave skips the linear; 3 a wave without edges (barrier only).
+    int cen = 0;
+    if constexpr (CEN) {
+      if (A.env_bwd != 2 && na <= 3) cen = !wact ? 3 : wvq == 0 ? 1 : 2;
+    }
+    // The skipping waves JUMP the stream (form (a) of the two ways to keep their ring in phase): the last RINGH requests of the linear in front of the skipped one -- the
+    // backward channel mixing, or the last layer's dcat linear -- read 16 fragments further on, so the ring holds the first fragments of the linear behind it.
+    const int cjump = cen == 2 ? 16 * 1024 : 0;
     par ^= 1;
     int *const aoffp = lds.aoff[par];
     const int e = e0 + s;
@@ -545,7 +569,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
 #ifdef ABL_NOTBGATHER   // timing experiment only (results are wrong): every edge reads the same table entry
       const int tb_off = (A.o_tbtab + 4 * g) * 4;
 #else
-      const int tb_off = (A.o_tbtab + ((ti * A.T + tj) * A.tb_nk + kq) * 256 + 4 * g) * 4;
+      const int tb_off = (A.o_tbtab + ((ti * A.T + tj) * A.tb_nk + kq) * 256 + 4 * (lq_ >> 4)) * 4;       // (lq_ >> 4 = g)
 #endif
       const float vm = (valid && xx < 1.f) ? 1.f : 0.f;
 #pragma unroll
@@ -781,7 +805,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     f32x4 dzr[RT];
     if constexpr (RT != 2) {
       // the 64-wide vector is not held across the read-out (k_fused sits at 256 registers): read again, through a pointer the optimiser cannot see through
-      const float *wq = lds.wo1v() + 4 * g;
+      const float *wq = lds.wo1v() + 4 * (lq_ >> 4);       // (lq_ >> 4 = g)
       asm volatile("" : "+v"(wq));
 #pragma unroll
       for (int t = 0; t < RT; ++t) wo1[t] = *(const f32x4 *)(wq + 16 * t);
@@ -883,15 +907,16 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
         __builtin_amdgcn_sched_barrier(0);
         // down the hidden layers: g_{k-1} = (g_k W_k^T) * silu'(z_{k-1}), then dcat = g_0 W_0^T
         f32x4 dcat[6];
-        if constexpr (MD == 1) lin<AR, WT, 6, false, 0>(WB, wp, dh, dcat, v16t, ring, EpiNone{});
+        const int dj = last ? cjump : 0;            // the last layer has no channel mixing: its dcat linear is the one in front of the environment backward
+        if constexpr (MD == 1) lin<AR, WT, 6, false, 0>(WB, wp, dh, dcat, v16t, ring, EpiNone{}, dj);
         else {
           f32x4 zt0[WT];
           if constexpr (MD == 3) load_rows<WT>(SB, RL + R_OZ(1, WT), zt0, v16t);
           lin<AR, WT, WT, false, 0>(WB, wp, dh, du, v16t, ring, EpiMulRows<WT>{zt1});
           if constexpr (MD == 3) {
             lin<AR, WT, WT, false, 0>(WB, wp, du, dh, v16t, ring, EpiMulRows<WT>{zt0});
-            lin<AR, WT, 6, false, 0>(WB, wp, dh, dcat, v16t, ring, EpiNone{});
-          } else lin<AR, WT, 6, false, 0>(WB, wp, du, dcat, v16t, ring, EpiNone{});
+            lin<AR, WT, 6, false, 0>(WB, wp, dh, dcat, v16t, ring, EpiNone{}, dj);
+          } else lin<AR, WT, 6, false, 0>(WB, wp, du, dcat, v16t, ring, EpiNone{}, dj);
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) dx[t] += dcat[t];
@@ -922,7 +947,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
                 i3[2] = {park_load(pk, 6, lane), park_load(pk, 7, lane)};
           f32x4 o3[3][2];
           EpiNone ep[3];
-          lin_mix(WB, wp, in2, i1, i2, i3, o2, o3, v16t, ring, EpiNone{}, ep);
+          lin_mix(WB, wp, in2, i1, i2, i3, o2, o3, v16t, ring, EpiNone{}, ep, cjump);
           dVp[0][0] += o2[0]; dVp[0][1] += o2[1];
 #pragma unroll
           for (int q = 0; q < 3; ++q) { dVp[1 + q][0] = o3[q][0]; dVp[1 + q][1] = o3[q][1]; }
@@ -980,20 +1005,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
       }
       __builtin_amdgcn_sched_barrier(0);
       PHASE(PH_BTP);
-      {
-        f32x4 dom[4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const int b = 16 * t + 4 * g;
-          const f32x4 d0 = *(const f32x4 *)(denvrow + b), d1 = *(const f32x4 *)(denvrow + 32 + b), d2 = *(const f32x4 *)(denvrow + 64 + b),
-                      d3 = *(const f32x4 *)(denvrow + 96 + b);
-          dom[t] = d0;
-          dom[2 + t] = d1 * Y1 + d2 * Y2 + d3 * Y3;
-          const f32x4 p1 = d1 * om1[t], p2 = d2 * om1[t], p3 = d3 * om1[t];
-          dY1 += (p1[0] + p1[1]) + (p1[2] + p1[3]); dY2 += (p2[0] + p2[1]) + (p2[2] + p2[3]); dY3 += (p3[0] + p3[1]) + (p3[2] + p3[3]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        asm volatile("" : "+v"(dY1), "+v"(dY2), "+v"(dY3));      // summed HERE: sunk to their use at the end of the tile, the sums keep a gradient row alive (in scratch) across the linear below
+      // the saved rows of the next iteration (the layer below, or the embedding), requested in front of this layer's environment backward
+      auto next_rows = [&]() __attribute__((always_inline)) {
         if (kk > 0) {                                                      // next iteration's u and z2 rows
           if (!SAVEZ) load_rows<4>(SB, R_LAYER(kk - 1, MD, WT) + OU, upre, v16t);
           load_rows<WT>(SB, R_LAYER(kk - 1, MD, WT) + OZL, zt, v16t);
@@ -1008,8 +1021,98 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
           }
           load_rows<2>(SB, R_W0() + 2, w0h, v16t);
         }
+      };
+      if constexpr (!CEN) {
+        f32x4 dom[4];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int b = 16 * t + 4 * g;
+          const f32x4 d0 = *(const f32x4 *)(denvrow + b), d1 = *(const f32x4 *)(denvrow + 32 + b), d2 = *(const f32x4 *)(denvrow + 64 + b),
+                      d3 = *(const f32x4 *)(denvrow + 96 + b);
+          dom[t] = d0;
+          dom[2 + t] = d1 * Y1 + d2 * Y2 + d3 * Y3;
+          const f32x4 p1 = d1 * om1[t], p2 = d2 * om1[t], p3 = d3 * om1[t];
+          dY1 += (p1[0] + p1[1]) + (p1[2] + p1[3]); dY2 += (p2[0] + p2[1]) + (p2[2] + p2[3]); dY3 += (p3[0] + p3[1]) + (p3[2] + p3[3]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        asm volatile("" : "+v"(dY1), "+v"(dY2), "+v"(dY3));      // summed HERE: sunk to their use at the end of the tile, the sums keep a gradient row alive (in scratch) across the linear below
+        next_rows();
         __builtin_amdgcn_sched_barrier(0);
         lin<AR, 4, 4, true, 0>(WB, wp, dom, dx, v16t, ring, EpiNone{});
+      } else {
+        // The instances with the per-centre form (cen, see the top of the tile).  ONE build of the operand and ONE call site of the linear serve the per-edge form
+        // (cen = 0: accumulating into dx) and wave 0's per-centre form (cen = 1: into zeros, which gives P): the operand is  [m0 D0 ; m1 D1 + m2 D2 + m3 D3]  of four rows
+        // D of lds.denv either way -- per edge the rows of the lane's centre with m = (1, Y1, Y2, Y3), exactly dom_e; per centre the rows of the column's centre
+        // c = j >> 2 with m = the unit vector of its component q = j & 3, or zeros where c >= na.  With a linear in each arm of a branch the ring's registers differ
+        // between the arms and the join in front of them copies the in-flight fragments behind s_waitcnt vmcnt(0); with the operand built in each arm,
+        // one of its tiles goes to scratch.  The rows of the next iteration are requested in front of every branch here for the same reason.
+        // P lives in this layer's environment rows: their last reader, the tensor product above, lies in front of both reduction barriers and their next writer is the
+        // next tile's forward reduction; a centre's four 64-vectors at a stride of two rows (2 x 132 >= 4 x 64), so that a lane finds them through envrow.
+        float *const pm = lds.env[0] + kk * (MAXA * ENV_LD);
+        static_assert(2 * ENV_LD >= 4 * 64 && 3 * 2 * ENV_LD <= Lds<NW>::MAXA * ENV_LD, "the per-centre products of three centres fit a layer's environment rows");
+        // what needs only lds.denv and om1: in front of the linear, or, on wave 0 while the others wait for its P, behind the barrier
+        auto dy_sums = [&]() __attribute__((always_inline)) {
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const int b = 16 * t + 4 * g;
+            const f32x4 p1 = *(const f32x4 *)(denvrow + 32 + b) * om1[t], p2 = *(const f32x4 *)(denvrow + 64 + b) * om1[t], p3 = *(const f32x4 *)(denvrow + 96 + b) * om1[t];
+            dY1 += (p1[0] + p1[1]) + (p1[2] + p1[3]); dY2 += (p2[0] + p2[1]) + (p2[2] + p2[3]); dY3 += (p3[0] + p3[1]) + (p3[2] + p3[3]);
+          }
+          asm volatile("" : "+v"(dY1), "+v"(dY2), "+v"(dY3));
+        };
+        next_rows();
+        if (cen != 1) dy_sums();
+        if (cen < 2) {
+          const float *dr = denvrow + 4 * g;
+          float m0 = 1.f, m1 = Y1, m2 = Y2, m3 = Y3;
+          int pcol = 0;
+          if (cen == 1) {
+            int lq = lane;         // (opaque: the column's addresses are formed here, layer by layer, not once per kernel and held in scratch)
+            asm volatile("" : "+v"(lq));
+            const int c = (lq >> 2) & 3, q = lq & 3, gq = lq >> 4;
+            const bool on = c < na;
+            dr = lds.denv + c * ENV_LD + 4 * gq;                 // (c <= 3 < MAXA: a row of the array for every lane)
+            m0 = on && q == 0 ? 1.f : 0.f; m1 = on && q == 1 ? 1.f : 0.f; m2 = on && q == 2 ? 1.f : 0.f; m3 = on && q == 3 ? 1.f : 0.f;
+            pcol = c < 3 ? c * (2 * ENV_LD) + 64 * q + 4 * gq : -1;       // (the four columns without a centre have no row)
+            // wave 0's own gradient waits in its slots of the staging tile (floats 0..63 of a slot's row: idle between the reduction above and the next layer's tensor
+            // product, and no other wave touches them): a second accumulator set beside dx costs 16 registers the kernel does not have
+#pragma unroll
+            for (int t = 0; t < 4; ++t) { *(f32x4 *)(st + 16 * t + 4 * g) = dx[t]; dx[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+          }
+          f32x4 dom[4];
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            const f32x4 d0 = *(const f32x4 *)(dr + 16 * t), d1 = *(const f32x4 *)(dr + 32 + 16 * t), d2 = *(const f32x4 *)(dr + 64 + 16 * t), d3 = *(const f32x4 *)(dr + 96 + 16 * t);
+            dom[t] = d0 * m0;                                    // (per edge: d0 * 1 and d1 Y1 + d2 Y2 + d3 Y3, the values of the per-edge instances)
+            dom[2 + t] = d1 * m1 + d2 * m2 + d3 * m3;
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          lin<AR, 4, 4, true, 0>(WB, wp, dom, dx, v16t, ring, EpiNone{});        // the same 16 fragments at the same stream position in both forms
+          if (cen == 1) {
+            if (pcol >= 0) {
+#pragma unroll
+              for (int t = 0; t < 4; ++t) *(f32x4 *)(pm + pcol + 16 * t) = dx[t];
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) dx[t] = *(const f32x4 *)(st + 16 * t + 4 * g);
+          }
+        } else if (cen == 2) {
+          wp += lin_frags_h(4, 4) * 256;           // the skipped linear's fragments: the stream jump (cjump) has put the next linear's first RINGH into the ring
+          pin_s(wp);
+        }
+        if (cen) {
+          __syncthreads();
+          if (cen == 1) dy_sums();
+          if (cen != 3) {
+            const float *pr = pm + 2 * (envrow - lds.env[0]) + 4 * g;          // = pm + aloc * (2 * ENV_LD)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              const f32x4 p0 = *(const f32x4 *)(pr + 16 * t), p1 = *(const f32x4 *)(pr + 64 + 16 * t), p2 = *(const f32x4 *)(pr + 128 + 16 * t),
+                          p3 = *(const f32x4 *)(pr + 192 + 16 * t);
+              dx[t] += p0 + Y1 * p1 + Y2 * p2 + Y3 * p3;
+            }
+          }
+        }
       }
       PHASE(PH_BENV);
     }
@@ -1123,7 +1226,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
       }
       if (lane < 6) {         // after the butterfly every lane holds the 6 totals: lane c owns component c
         const float mine = lane == 0 ? w6[0] : lane == 1 ? w6[1] : lane == 2 ? w6[2] : lane == 3 ? w6[3] : lane == 4 ? w6[4] : w6[5];
-        lds.virw[wave][lane] += (double)mine;
+        lds.virw[wvq][lq_] += (double)mine;
       }
       if constexpr (VA) vatom_scatter(A.vatom, jat, g, valid, rx, ry, rz, gx, gy, gz);
     }
@@ -1218,7 +1321,22 @@ void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const 
 #ifndef AHIP_ASM_NW
 #define AHIP_ASM_NW 4
 #endif
-  hipLaunchKernelGGL((k_fused<AHIP_ASM_NW, false, 3, true, 2, 2>), dim3(grid), dim3(AHIP_ASM_NW * 64), 0, s, A);
+#ifndef AHIP_ASM_NL       // (layers, latent MLP depth, per-atom virial of the instance to look at: AHIP_NL=3 AHIP_MD=1 AHIP_VA=true tools/asm_k_fused.sh)
+#define AHIP_ASM_NL 2
+#endif
+#ifndef AHIP_ASM_MD
+#define AHIP_ASM_MD 2
+#endif
+#ifndef AHIP_ASM_VA
+#define AHIP_ASM_VA false
+#endif
+#ifndef AHIP_ASM_WT       // (AHIP_WT=8: an MLP-width-128 instance; AHIP_RT=4: a read-out-width-64 one)
+#define AHIP_ASM_WT 4
+#endif
+#ifndef AHIP_ASM_RT
+#define AHIP_ASM_RT 2
+#endif
+  hipLaunchKernelGGL((k_fused<AHIP_ASM_NW, false, 3, true, AHIP_ASM_NL, AHIP_ASM_MD, AHIP_ASM_VA, 1, AHIP_ASM_WT, AHIP_ASM_RT>), dim3(grid), dim3(AHIP_ASM_NW * 64), 0, s, A);
 #else
   dispatch<Choices<4, 8>, Choices<1, 2, 3>, Choices<1, 3, 2>, Variants>([&](auto nw, auto nl, auto md, auto var) {
     if constexpr (var != VAR_PROF || md == 2) hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, 3, true, nl, md, var == VAR_VA>), dim3(grid), dim3(nw * 64), 0, s, A);
@@ -1440,6 +1558,7 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
   FusedArgs A = st.args;
   fused_tile_args(m, st.tiles, a, A, tile_slots, maxa, maxdeg_sel, nw == 4);       // (the edge build packs 4-wave tiles only)
   A.maxdeg_sel = maxdeg_sel;
+  A.env_bwd = (int)m.opt_env_backward;
   const long long nedges_est = fused_nedges_estimate(m);
   // persistent workgroups fill every CU; reserve_wgs leaves a few slots free so that the exchange kernels of another stream
   // (ghost pack / unpack, RCCL send / recv) can be scheduled while this kernel runs (md.py, overlapped schedule)

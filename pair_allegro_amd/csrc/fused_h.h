@@ -71,9 +71,11 @@ template <class E> __device__ __forceinline__ f32x2 epi_apply2(E &e, int ot, int
 // Streamed linear, f16x2.  in[g][ks]: KS K-steps (pairs of 16-feature tiles, split) per group; out[g][t]: NT f32 tiles through the epilogue functors of
 // fused_common.h (one functor per group); SPLIT additionally emits the outputs as the next linear's B operands.  Fragments per (tile pair p, K-step):
 // hi0 hi1 lo0 lo1, 1 KiB each, in consumption order, RINGH of them in flight.  The 8 G epilogue elements of pair p-1 are spread over the MFMAs of pair p.
+// jump (bytes, wave-uniform): added to the stream offset of the requests of the last two steps, i.e. of the RINGH fragments that lie BEHIND this linear: the wave
+// will skip the linear that follows (k_fused: the per-centre environment backward) and meets the one after it with that one's first fragments in its ring.
 template <int G, int KS, int NT, bool ACC, bool SPLIT, int RP, class Epi, bool LATE_OK = false>
 __device__ __forceinline__ void linear_h(__amdgpu_buffer_rsrc_t W, int &wp, const Hop (&in)[G][KS], f32x4 (&out)[G][NT], Hop (&outb)[G][NT / 2],
-                                         int v16, u32x4 (&ring)[RINGH], Epi (&epi)[G]) {
+                                         int v16, u32x4 (&ring)[RINGH], Epi (&epi)[G], int jump = 0) {
   static_assert(NT % 2 == 0, "output tiles are processed in pairs");
   constexpr int RB = RINGH, NF = 4, NP = NT / 2, NSTEP = NP * KS, NS = NF * NSTEP;
   constexpr int MF = 6 * G;                        // MFMAs per step
@@ -104,12 +106,13 @@ __device__ __forceinline__ void linear_h(__amdgpu_buffer_rsrc_t W, int &wp, cons
     u32x4 a[NF];
 #pragma unroll
     for (int i = 0; i < NF; ++i) a[i] = ring[(RP + NF * s + i) % RB];
+    const int wr = s >= NSTEP - 2 ? wo + jump : wo;      // where this step's requests read
     if (!LATE) {
       // (LATE_OK: lo before hi, the order of consumption and of the late form: a slot's age in the in-order queue is then the same after every linear)
 #pragma unroll
       for (int q = 0; q < NF; ++q) {
         const int i = LATE_OK ? (q + 2) % NF : q;
-        ring[(RP + NF * s + i) % RB] = __builtin_bit_cast(u32x4, bload_w(W, v16 + i * 1024, wo));      // + i KiB: the instruction's immediate offset
+        ring[(RP + NF * s + i) % RB] = __builtin_bit_cast(u32x4, bload_w(W, v16 + i * 1024, wr));      // + i KiB: the instruction's immediate offset
       }
     }
     if (!LATE) {
@@ -129,7 +132,7 @@ __device__ __forceinline__ void linear_h(__amdgpu_buffer_rsrc_t W, int &wp, cons
           if (LATE && g == G - 1 && m != 1) {
             // the last product that reads this fragment has been issued: its slot is requested again now, into the slot's own registers
             const int i = m == 0 ? 2 + hh : hh;
-            ring[(RP + NF * s + i) % RB] = __builtin_bit_cast(u32x4, bload_w(W, v16 + i * 1024, wo));
+            ring[(RP + NF * s + i) % RB] = __builtin_bit_cast(u32x4, bload_w(W, v16 + i * 1024, wr));
           }
           if (p > 0) {
             // the 4 G register pairs of the previous tile pair, spread over this pair's MFMAs
