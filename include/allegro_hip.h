@@ -328,6 +328,43 @@ int ahip_borders_local_dev(ahip_model *m, int nlocal, const double *x_dev, const
                            const double *box, double rc, int capacity, double *xg_dev, int *mtg_dev, long long *src_dev, double *shift_dev,
                            int *nghost, void *stream);
 
+/* ---- any periodic cell, one rank: triclinic cells, cells thinner than the cutoff, open axes ----
+ * Conventions: `cell` is a HOST row-major double[9] whose rows are the lattice vectors (any orientation, not only LAMMPS' lower-triangular form), `pbc` a HOST
+ * int[3] (non-zero = periodic axis), s = x . cell^-1 the fractional coordinates, h_d the height of the cell along d and m_d = rc / h_d.  A singular cell or one
+ * with a non-finite entry is AHIP_ERR_ARG before any launch. */
+
+/* LAMMPS' Domain::remap at a re-neighboring, for a general cell: adds to every position the integer lattice combination that brings s_d into [0, 1) on every
+ * periodic axis; the fractional components of open axes are left alone, and an atom already inside comes back bit for bit.  One launch on `stream`, no host
+ * synchronisation. */
+int ahip_wrap_cell_dev(ahip_model *m, int n, double *x_dev, const double *cell, const int *pbc, void *stream);
+
+/* Ghost atoms of ONE rank that owns the whole cell -- LAMMPS' Comm::borders on a 1 x 1 x 1 grid of a triclinic or thin box, where ahip_borders_local_dev needs an
+ * orthogonal box with box_d >= rc.  For wrapped positions the image n = (n1, n2, n3) != 0 of atom i is a ghost iff for every d: n_d == 0 on an open axis,
+ * -m_d <= s_id + n_d < 1 + m_d on a periodic one (LAMMPS' slab criterion in fractional coordinates: every image within rc of an atom of the cell satisfies it, and
+ * on an orthogonal box with box_d >= rc it is the rule of ahip_borders_local_dev).  Any number of images per direction.  Writes, per ghost, its position
+ * x_i + n . cell, the model type of i, the index i (int64) and the shift n . cell (what ahip_comm_set_plan_local takes), ordered by ascending source atom and, within
+ * an atom, by (n1, n2, n3) ascending with n3 fastest.  Output contract of ahip_borders_local_dev: *nghost is the number of images and may exceed `capacity` (then
+ * only the first `capacity` rows were written: call again with larger arrays).  nlocal x prod_d (2 ceil(m_d) + 1) must fit 32 bits (AHIP_ERR_ARG before any
+ * launch otherwise).  Synchronises `stream` (one 4-byte read-back). */
+int ahip_borders_cell_dev(ahip_model *m, int nlocal, const double *x_dev, const int *mtype_dev, const double *cell, const int *pbc, double rc, int capacity,
+                          double *xg_dev, int *mtg_dev, long long *src_dev, double *shift_dev, int *nghost, void *stream);
+
+/* One-call evaluation without LAMMPS -- "cell, positions, species in; energy, forces, virial out" -- i.e. everything LAMMPS does for the reference around
+ * PairNequIPAllegro::compute on one rank (Domain::remap, Comm::borders, the full neighbor list, the reverse communication of newton_pair on,
+ * pair_nequip_allegro.cpp:143-149,366-377).  HOST pointers.
+ *   x      [natoms][3] positions, wrapped or not            mtype  [natoms] MODEL types, 0-based (a value outside the model's types: AHIP_ERR_ARG)
+ *   skin   >= 0: only inflates the ghost shell and the list (rc = largest model cutoff + skin); the cutoffs are the model's own (r_max or its per-edge-type matrix)
+ *   f      [natoms][3] and eatom [natoms] (or NULL) are WRITTEN, not accumulated, in the caller's atom order (ghost forces already added to their sources)
+ *   eng    energy;  virial [6] or NULL: xx,yy,zz,xy,xz,yz in LAMMPS order and sign, as ahip_compute
+ * Steps: upload, ahip_wrap_cell_dev, ahip_borders_cell_dev (retried with a larger capacity when needed), ahip_build_neighbors_dev over the bounding box of the
+ * cell's eight corners +- rc, the evaluation of ahip_compute_dev, ghost forces added to their sources, download.  Nothing is reused between calls.  A model of more
+ * than 16 types takes its active set from the types present.  ahip_last_path, ahip_get_edges and the other accessors keep working afterwards; their rows are the
+ * atoms followed by the ghosts, and ahip_last_cell_rows maps every row to its atom (nrows = natoms + ghosts; row_atom: room for nrows entries, or NULL for the
+ * count alone). */
+int ahip_compute_cell(ahip_model *m, int natoms, const double *x, const int *mtype, const double *cell, const int *pbc, double skin, double *f,
+                      double *eatom, double *eng, double *virial);
+int ahip_last_cell_rows(ahip_model *m, int *nrows, long long *row_atom);
+
 /* v += dtf*f/m ; x += dt*v  style velocity-Verlet half steps on device arrays (NVE).
  *   mode 0: v += 0.5*dt*f*ftm2v/mass[type]; x += dt*v      (initial_integrate)
  *   mode 1: v += 0.5*dt*f*ftm2v/mass[type]                  (final_integrate)

@@ -38,6 +38,7 @@ SYMBOLS = [
     "ahip_comm_forward", "ahip_comm_reverse", "ahip_comm_allreduce", "ahip_comm_selftest", "ahip_fill_zero_dev", "ahip_borders_local_dev", "ahip_arith_note", "ahip_comm_borders", "ahip_comm_migrate",
     "ahip_debug_scan_i32", "ahip_debug_sum_columns_f64", "ahip_debug_max_i32", "ahip_debug_gemm_f32",
     "ahip_set_active_types", "ahip_get_active_types",
+    "ahip_wrap_cell_dev", "ahip_borders_cell_dev", "ahip_compute_cell", "ahip_last_cell_rows",
 ]
 
 
@@ -333,6 +334,62 @@ class Model:
         self.L.check(self.L.lib.ahip_borders_local_dev(self.h, nlocal, x_ptr or None, mtype_ptr or None, _p(a[0], C.c_double), _p(a[1], C.c_double), _p(a[2], C.c_double),
                                                         float(rc), capacity, xg_ptr or None, mtg_ptr or None, src_ptr or None, shift_ptr or None, C.byref(ng), stream or None))
         return int(ng.value)
+
+    # ---- any periodic cell (include/allegro_hip.h: cell = rows of lattice vectors, pbc = three flags) ----------
+    @staticmethod
+    def _cell_args(cell, pbc):
+        c = np.ascontiguousarray(cell, dtype=np.float64)
+        if c.shape != (3, 3):
+            raise ValueError(f"cell must be a 3x3 matrix of lattice vectors (rows), got shape {c.shape}")
+        p = np.ascontiguousarray([1 if b else 0 for b in pbc], dtype=np.int32)
+        if p.shape != (3,):
+            raise ValueError("pbc must have three entries")
+        return c, p
+
+    def wrap_cell_dev(self, n: int, x_ptr: int, cell, pbc=(True, True, True), stream: int = 0) -> None:
+        """positions back into the cell along its periodic axes, in place, no host synchronisation (ahip_wrap_cell_dev)"""
+        c, p = self._cell_args(cell, pbc)
+        self.L.lib.ahip_wrap_cell_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p]
+        self.L.check(self.L.lib.ahip_wrap_cell_dev(self.h, n, x_ptr or None, _p(c, C.c_double), _p(p, C.c_int), stream or None))
+
+    def borders_cell_dev(self, nlocal: int, x_ptr: int, mtype_ptr: int, cell, pbc, rc: float, capacity: int, xg_ptr: int, mtg_ptr: int,
+                         src_ptr: int, shift_ptr: int, stream: int = 0) -> int:
+        """periodic images of a single rank's own atoms within rc of a general cell (ahip_borders_cell_dev); returns their number (> capacity: retry with larger arrays)"""
+        c, p = self._cell_args(cell, pbc)
+        ng = C.c_int(0)
+        self.L.lib.ahip_borders_cell_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_double, C.c_int,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+        self.L.check(self.L.lib.ahip_borders_cell_dev(self.h, nlocal, x_ptr or None, mtype_ptr or None, _p(c, C.c_double), _p(p, C.c_int), float(rc), capacity,
+                                                       xg_ptr or None, mtg_ptr or None, src_ptr or None, shift_ptr or None, C.byref(ng), stream or None))
+        return int(ng.value)
+
+    def compute_cell(self, x: np.ndarray, mtype: np.ndarray, cell, pbc=(True, True, True), skin: float = 0.0, want_eatom: bool = True):
+        """One evaluation from host arrays (ahip_compute_cell): returns (energy, forces [n][3], atomic energies [n] or None, virial [6])."""
+        c, p = self._cell_args(cell, pbc)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        mt = np.ascontiguousarray(mtype, dtype=np.int32).reshape(-1)
+        if len(mt) != len(x):
+            raise ValueError("positions and types differ in length")
+        n = len(x)
+        f = np.zeros((n, 3))
+        ea = np.zeros(n) if want_eatom else None
+        eng = C.c_double(0)
+        vir = np.zeros(6)
+        self.L.lib.ahip_compute_cell.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_double,
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        self.L.check(self.L.lib.ahip_compute_cell(self.h, n, _p(x, C.c_double), _p(mt, C.c_int), _p(c, C.c_double), _p(p, C.c_int), float(skin),
+                                                   _p(f, C.c_double), _p(ea, C.c_double), C.byref(eng), _p(vir, C.c_double)))
+        return eng.value, f, ea, vir
+
+    def last_cell_rows(self) -> np.ndarray:
+        """atom index of every row (atoms, then ghosts) of the last compute_cell (ahip_last_cell_rows)"""
+        n = C.c_int(0)
+        self.L.lib.ahip_last_cell_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+        self.L.check(self.L.lib.ahip_last_cell_rows(self.h, C.byref(n), None))
+        out = np.zeros(n.value, dtype=np.int64)
+        if n.value:
+            self.L.check(self.L.lib.ahip_last_cell_rows(self.h, C.byref(n), _p(out, C.c_longlong)))
+        return out
 
     def nve_dev(self, mode: int, n: int, x_ptr: int, v_ptr: int, f_ptr: int, mtype_ptr: int, mass_by_mtype,
                 dt: float, ftm2v: float, stream: int = 0) -> None:

@@ -253,7 +253,7 @@ void ahip_model_free(ahip_model *m) {
   for (DevBuf *b : {&m->b_flagwork, &m->b_ilist, &m->b_nloff, &m->b_nlj, &m->b_x, &m->b_ftype, &m->b_mtype, &m->b_f, &m->b_eatom,
                     &m->b_engvir, &m->b_cutsq, &m->b_cnt, &m->b_eoff, &m->b_eii, &m->b_ej, &m->b_rvec, &m->b_ett, &m->b_partial,
                     &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom,
-                    &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist})
+                    &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist, &m->c_x, &m->c_mtype, &m->c_f, &m->c_eatom, &m->c_src, &m->c_shift, &m->c_engvir})
     b->release();
   for (auto &t : m->slots) for (auto &e : t.ring) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (hipEvent_t e : m->f_events) (void)hipEventDestroy(e);
@@ -1357,6 +1357,132 @@ int ahip_borders_local_dev(ahip_model *m, int nlocal, const double *x_dev, const
       throw ArgError("ahip_borders_local_dev: bad argument");
     AHIP_CHECK(hipSetDevice(m->device));
     *nghost = borders_local(*m, nlocal, x_dev, mtype_dev, lo, hi, box, rc, capacity, xg_dev, mtg_dev, src_dev, shift_dev, (hipStream_t)stream);
+  });
+}
+
+int ahip_wrap_cell_dev(ahip_model *m, int n, double *x_dev, const double *cell, const int *pbc, void *stream) {
+  return guarded([&] {
+    require_model(m);
+    if (n < 0 || !cell || !pbc || (n > 0 && !x_dev)) throw ArgError("ahip_wrap_cell_dev: bad argument");
+    AHIP_CHECK(hipSetDevice(m->device));
+    wrap_cell(*m, n, x_dev, cell, pbc, (hipStream_t)stream);
+  });
+}
+
+int ahip_borders_cell_dev(ahip_model *m, int nlocal, const double *x_dev, const int *mtype_dev, const double *cell, const int *pbc, double rc, int capacity,
+                          double *xg_dev, int *mtg_dev, long long *src_dev, double *shift_dev, int *nghost, void *stream) {
+  return guarded([&] {
+    require_model(m);
+    if (nlocal < 0 || capacity < 0 || !cell || !pbc || !nghost || !(rc > 0.0) || !std::isfinite(rc) || (nlocal > 0 && (!x_dev || !mtype_dev)) ||
+        (capacity > 0 && (!xg_dev || !mtg_dev || !src_dev || !shift_dev)))
+      throw ArgError("ahip_borders_cell_dev: bad argument");
+    AHIP_CHECK(hipSetDevice(m->device));
+    *nghost = borders_cell(*m, nlocal, x_dev, mtype_dev, cell, pbc, rc, capacity, xg_dev, mtg_dev, src_dev, shift_dev, (hipStream_t)stream);
+  });
+}
+
+// the error of a nested C-ABI call, thrown again as what it was
+static void rethrow_code(int rc) {
+  if (rc == AHIP_OK) return;
+  const std::string err = g_err;
+  if (rc == AHIP_ERR_ARG) throw ArgError(err);
+  if (rc == AHIP_ERR_STATE) throw StateError(err);
+  if (rc == AHIP_ERR_UNSUPPORTED) throw UnsupportedError(err);
+  throw HipError(err);
+}
+
+int ahip_compute_cell(ahip_model *m, int natoms, const double *x, const int *mtype, const double *cell, const int *pbc, double skin, double *f,
+                      double *eatom, double *eng, double *virial) {
+  return guarded([&] {
+    require_model(m);
+    if (natoms < 0 || !cell || !pbc || !eng || (natoms > 0 && (!x || !mtype || !f))) throw ArgError("ahip_compute_cell: bad argument");
+    if (!(skin >= 0.0) || !std::isfinite(skin)) throw ArgError("ahip_compute_cell: skin must be a finite number >= 0");
+    const int T = m->hm.num_types;
+    std::vector<int> present;
+    for (int i = 0; i < natoms; ++i) {
+      if (mtype[i] < 0 || mtype[i] >= T)
+        throw ArgError("ahip_compute_cell: atom " + std::to_string(i) + " has model type " + std::to_string(mtype[i]) + ", outside the model's " + std::to_string(T) + " types");
+      present.push_back(mtype[i]);
+    }
+    std::sort(present.begin(), present.end());
+    present.erase(std::unique(present.begin(), present.end()), present.end());
+    const double rc = *std::max_element(m->rcut_model_host.begin(), m->rcut_model_host.end()) + skin;
+    AHIP_CHECK(hipSetDevice(m->device));
+    hipStream_t s = nullptr;
+    *eng = 0;
+    if (virial) for (int k = 0; k < 6; ++k) virial[k] = 0;
+    // upload, wrap, ghosts: rows [0, natoms) of c_x / c_mtype are the atoms, the images go behind them.  The first capacity is the last call's count when the
+    // system has the same size, else none (the call then only counts); a grown buffer loses its content, so the one retry uploads again
+    int cap = natoms == m->cell_natoms ? m->cell_nghost_last + m->cell_nghost_last / 8 : 0, ng = 0;
+    m->cell_src_host.clear(); m->cell_natoms = natoms;
+    double lo[3], hi[3];
+    cell_bounding_box(cell, rc + 1e-6, lo, hi);
+    for (;;) {
+      const size_t rows = (size_t)natoms + (size_t)cap;
+      m->c_x.reserve(std::max<size_t>(rows, 1) * 3 * sizeof(double));
+      m->c_mtype.reserve(std::max<size_t>(rows, 1) * sizeof(int));
+      m->c_src.reserve(std::max<size_t>((size_t)cap, 1) * sizeof(long long));
+      m->c_shift.reserve(std::max<size_t>((size_t)cap, 1) * 3 * sizeof(double));
+      if (natoms > 0) {
+        copy_h2d(m->c_x.p, x, (size_t)natoms * 3 * sizeof(double));
+        copy_h2d(m->c_mtype.p, mtype, (size_t)natoms * sizeof(int));
+      }
+      wrap_cell(*m, natoms, m->c_x.as<double>(), cell, pbc, s);
+      ng = borders_cell(*m, natoms, m->c_x.as<double>(), m->c_mtype.as<int>(), cell, pbc, rc, cap, m->c_x.as<double>() + 3 * (size_t)natoms,
+                        m->c_mtype.as<int>() + natoms, m->c_src.as<long long>(), m->c_shift.as<double>(), s);
+      if (ng <= cap) break;
+      cap = ng;
+    }
+    m->cell_nghost_last = ng;
+    if ((long long)natoms + ng > 2147483647LL) throw ArgError("ahip_compute_cell: atoms + ghosts exceed 2^31 - 1 rows");
+    const int nall = natoms + ng;
+    m->cell_src_host.resize((size_t)ng);
+    if (ng > 0) copy_d2h(m->cell_src_host.data(), m->c_src.p, (size_t)ng * sizeof(long long));
+    m->active_mapped = present;               // a model of more than 16 types runs on the types present (run_model: resolve_active)
+    neigh_build(*m, natoms, nall, m->c_x.as<double>(), lo, hi, rc, s);
+    m->c_f.reserve((size_t)std::max(nall, 1) * 3 * sizeof(double));
+    m->c_eatom.reserve((size_t)std::max(nall, 1) * sizeof(double));
+    m->c_engvir.reserve(8 * sizeof(double));
+    // (twice at most: an evaluation whose f16x2 kernels raise the float16-range alarm under fused_arith=auto is repeated on the float32 instance, as in ahip_compute)
+    for (int attempt = 0;; ++attempt) {
+      AHIP_CHECK(hipMemsetAsync(m->c_f.p, 0, (size_t)std::max(nall, 1) * 3 * sizeof(double), s));
+      AHIP_CHECK(hipMemsetAsync(m->c_eatom.p, 0, (size_t)std::max(nall, 1) * sizeof(double), s));
+      rethrow_code(ahip_compute_dev(m, natoms, ng, m->c_x.as<double>(), m->c_mtype.as<int>(), nullptr, m->c_f.as<double>(), m->c_eatom.as<double>(),
+                                    m->c_engvir.as<double>(), s));
+      comm_scatter_local(ng, natoms, m->c_src.as<long long>(), m->c_f.as<double>(), s);      // ghost forces go home (newton on)
+      AHIP_CHECK(hipGetLastError());
+      AHIP_CHECK(hipStreamSynchronize(s));
+      if (const int bad = inactive_take(*m)) throw ArgError("ahip_compute_cell: " + inactive_message(*m, bad, "this evaluation") + " (nothing was written to f)");
+      if (alarm_take(*m)) {
+        if (arith_may_degrade(*m) && attempt == 0) {
+          arith_degrade(*m, "an activation left float16's range (non-finite edge gradient on the f16x2 arithmetic); the evaluation was repeated");
+          continue;
+        }
+        throw StateError("fused_arith=f16x2: an edge gradient was not finite (an activation left float16's range, or the input was not finite): the forces of this "
+                         "evaluation are invalid and were not written to f; set option fused_arith=f32 (or auto) for this model");
+      }
+      break;
+    }
+    double ev[7];
+    copy_d2h(ev, m->c_engvir.p, 7 * sizeof(double));
+    if (natoms > 0) {
+      copy_d2h(f, m->c_f.p, (size_t)natoms * 3 * sizeof(double));
+      if (eatom) copy_d2h(eatom, m->c_eatom.p, (size_t)natoms * sizeof(double));
+    }
+    *eng = ev[0];
+    if (virial) for (int k = 0; k < 6; ++k) virial[k] = ev[1 + k];
+  });
+}
+
+int ahip_last_cell_rows(ahip_model *m, int *nrows, long long *row_atom) {
+  return guarded([&] {
+    require_model(m);
+    if (!nrows) throw ArgError("ahip_last_cell_rows: nrows is NULL");
+    if (m->cell_natoms < 0) throw StateError("ahip_last_cell_rows called before ahip_compute_cell");
+    *nrows = m->cell_natoms + (int)m->cell_src_host.size();
+    if (!row_atom) return;
+    for (int i = 0; i < m->cell_natoms; ++i) row_atom[i] = i;
+    std::copy(m->cell_src_host.begin(), m->cell_src_host.end(), row_atom + m->cell_natoms);
   });
 }
 

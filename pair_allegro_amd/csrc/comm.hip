@@ -212,10 +212,14 @@ static void comm_forward(Comm &c, double *x, hipStream_t s) {
   }
 }
 
+// the reverse exchange of the local plan; also what ahip_compute_cell (allegro_hip.hip) returns its ghost forces with (engine.h)
+void comm_scatter_local(int nghost, int nlocal, const long long *src, double *f, hipStream_t s) {
+  if (nghost > 0) hipLaunchKernelGGL(k_comm_scatter_local, dim3((nghost + 255) / 256), dim3(256), 0, s, nghost, nlocal, src, f);
+}
+
 static void comm_reverse(Comm &c, double *f, hipStream_t s) {
   if (c.local_plan) {
-    if (c.loc_nghost > 0)
-      hipLaunchKernelGGL(k_comm_scatter_local, dim3((c.loc_nghost + 255) / 256), dim3(256), 0, s, c.loc_nghost, c.loc_nlocal, c.loc_src, f);
+    comm_scatter_local(c.loc_nghost, c.loc_nlocal, c.loc_src, f, s);
     return;
   }
   const int n = (int)c.swaps.size();

@@ -175,6 +175,12 @@ struct Model {
   std::vector<double> h_x, h_f, h_eatom, h_cutsq_dev;      // h_cutsq_dev: what b_cutsq currently holds (device path); h_x: page-locked copy of the caller's positions
   std::map<const void *, std::pair<void *, size_t>> pinned;   // host vectors currently page-locked (allegro_hip.hip: pin_host)
 
+  // ahip_compute_cell: rows = atoms then ghosts (positions, model types, forces, per-atom energies), the ghosts' source atoms and shifts, the 7 sums; the
+  // ghost count of the last call (first capacity guess of the next) and its sources on the host (ahip_last_cell_rows)
+  DevBuf c_x, c_mtype, c_f, c_eatom, c_src, c_shift, c_engvir;
+  int cell_nghost_last = 0, cell_natoms = -1;
+  std::vector<long long> cell_src_host;
+
   // edge list + workspace
   DevBuf b_cnt, b_eoff, b_eii, b_ej, b_rvec, b_partial, b_ws, b_misc;
   DevBuf b_ett;                              // per-edge packed model types (centre << 4 | neighbour), fused path only
@@ -423,6 +429,15 @@ void neigh_free(Model &m);
 // periodic images of a single rank's own atoms inside the halo (neigh.hip); returns their number (may exceed `capacity`: then the arrays hold the first `capacity`)
 int borders_local(Model &m, int nlocal, const double *x, const int *mtype, const double *lo, const double *hi, const double *box, double rc, int capacity,
                   double *xg, int *mtg, long long *src, double *shift, hipStream_t s);
+// any periodic cell (neigh.hip; cell: row-major double[9], rows = lattice vectors; pbc: int[3]).  wrap_cell: one launch, no synchronisation.  borders_cell: the
+// images n != 0 of the rank's own atoms with -rc / h_d <= s_d + n_d < 1 + rc / h_d on every periodic axis, same output contract as borders_local.
+// cell_bounding_box: the eight corners of the cell, widened by `margin`.  All three throw ArgError for a singular or non-finite cell, before any launch.
+void wrap_cell(Model &m, int n, double *x, const double *cell, const int *pbc, hipStream_t s);
+int borders_cell(Model &m, int nlocal, const double *x, const int *mtype, const double *cell, const int *pbc, double rc, int capacity,
+                 double *xg, int *mtg, long long *src, double *shift, hipStream_t s);
+void cell_bounding_box(const double *cell, double margin, double *lo, double *hi);
+// one rank, ghost g (row nlocal + g) an image of local row src[g]: f[src[g]] += f[nlocal + g] (comm.hip: the reverse exchange of the local plan)
+void comm_scatter_local(int nghost, int nlocal, const long long *src, double *f, hipStream_t s);
 void nve_first_step(Model &m, int n, int nall, double *x, double *v, double *f, const int *mtype, const double *mass_host, int ntypes, double dt, double ftm2v,
                     hipStream_t s);
 void nve_step(Model &m, int mode, int n, double *x, double *v, const double *f, const int *mtype, const double *mass_dev_or_host,

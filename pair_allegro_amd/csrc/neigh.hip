@@ -323,6 +323,149 @@ int borders_local(Model &m, int nlocal, const double *x, const int *mtype, const
   return tot;             // > capacity: nothing beyond the capacity was written; the caller retries with larger arrays
 }
 
+// ---- any periodic cell: wrap (LAMMPS' Domain::remap) and the ghost shell of one rank (Comm::borders on a 1 x 1 x 1 grid of a triclinic or thin box) ----
+// cell rows are lattice vectors, s = x . cell^-1 the fractional coordinates, h_d the cell height along d, m_d = rc / h_d.  The image n = (n1, n2, n3) != 0 of
+// atom i is a ghost iff for every d: n_d == 0 where the axis is open, -m_d <= s_id + n_d < 1 + m_d where it is periodic -- LAMMPS' slab criterion in fractional
+// coordinates.  It is complete (every j + n . cell within rc of a wrapped atom satisfies it), reduces to the rule of border_dirs on an orthogonal box with
+// box_d >= rc, and allows any number of images per direction (a 3.61 A cell at rc = 16 has 856 per atom).
+// The admissible n_d are an integer interval [lo_d, hi_d], so the count is closed-form per atom; the fill runs one thread per OUTPUT row (a thread per atom would
+// serialise 856 images on four lanes): binary search of the scanned offsets for the source atom, n decoded from the rank inside the atom's image box, n3 fastest,
+// the zero image skipped.  Order: ascending source atom, then (n1, n2, n3) lexicographic.
+struct CellGeom {
+  double h[9];        // lattice vectors (rows)
+  double inv[9];      // cell^-1: s_d = sum_k x_k inv[3 k + d]
+  double m[3];        // rc / height (borders only)
+  int pbc[3];
+};
+// explicit fma chain: the count and the fill kernel must see the very same s
+__device__ __host__ inline double cell_frac(const CellGeom &g, const double *x, int d) {
+  return fma(x[2], g.inv[6 + d], fma(x[1], g.inv[3 + d], x[0] * g.inv[d]));
+}
+__device__ __host__ inline int cell_clamp_int(double v) { return v < -1073741824.0 ? -1073741824 : (v > 1073741824.0 ? 1073741824 : (int)v); }
+// images admitted along d: lo <= n_d <= hi (an open axis: 0 only); returns their number
+__device__ __host__ inline int cell_image_range(const CellGeom &g, const double *x, int d, int *lo) {
+  if (!g.pbc[d]) { *lo = 0; return 1; }
+  const double s = cell_frac(g, x, d);
+  const int l = cell_clamp_int(ceil(-g.m[d] - s)), h = cell_clamp_int(ceil(1.0 + g.m[d] - s)) - 1;      // -m <= s + n  and  s + n < 1 + m
+  *lo = l;
+  return h >= l ? h - l + 1 : 0;
+}
+// the image box of one atom: lo[3], count[3]; returns the number of ghosts (the box without the zero image) and the rank `zero` of that image in it (-1: outside)
+__device__ __host__ inline long long cell_image_box(const CellGeom &g, const double *x, int *lo, int *c, long long *zero) {
+  for (int d = 0; d < 3; ++d) c[d] = cell_image_range(g, x, d, &lo[d]);
+  const long long tot = (long long)c[0] * c[1] * c[2];
+  bool in = tot > 0;
+  for (int d = 0; d < 3; ++d) in = in && lo[d] <= 0 && -lo[d] < c[d];
+  *zero = in ? ((long long)(-lo[0]) * c[1] + (-lo[1])) * c[2] + (-lo[2]) : -1;
+  return in ? tot - 1 : tot;
+}
+__global__ void k_cell_count(int n, const double *x, CellGeom g, int *cnt) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int lo[3], c[3];
+  long long zero;
+  const long long k = cell_image_box(g, x + 3 * i, lo, c, &zero);
+  cnt[i] = k > 2147483647LL ? 2147483647 : (int)k;      // (the host has bounded the sum for wrapped input; a far-away atom saturates instead of wrapping)
+}
+__global__ void k_cell_fill(int n, const double *x, const int *mtype, CellGeom g, const int *off, int capacity, double *xg, int *mtg, long long *src, double *shift) {
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= capacity || k >= off[n]) return;
+  int a = 0, b = n;                                       // largest a with off[a] <= k (off[a] <= k < off[b] throughout)
+  while (b - a > 1) {
+    const int mid = a + (b - a) / 2;
+    if (off[mid] <= (int)k) a = mid; else b = mid;
+  }
+  const double *xi = x + 3 * (long long)a;
+  int lo[3], c[3];
+  long long zero;
+  if (cell_image_box(g, xi, lo, c, &zero) <= 0) return;    // (cannot happen behind a consistent scan: no row belongs to an atom without images)
+  long long r = k - off[a];
+  if (zero >= 0 && r >= zero) ++r;
+  const int n3 = lo[2] + (int)(r % c[2]);
+  r /= c[2];
+  const int n2 = lo[1] + (int)(r % c[1]), n1 = lo[0] + (int)(r / c[1]);
+  for (int d = 0; d < 3; ++d) {
+    const double sh = n1 * g.h[d] + n2 * g.h[3 + d] + n3 * g.h[6 + d];
+    shift[3 * k + d] = sh;
+    xg[3 * k + d] = xi[d] + sh;
+  }
+  mtg[k] = mtype[a];
+  src[k] = a;
+}
+// x += (the integer lattice combination that brings s_d into [0, 1) on every periodic axis); an atom already inside is not touched
+__global__ void k_cell_wrap(int n, double *x, CellGeom g) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double *xi = x + 3 * i;
+  double k[3];
+  for (int d = 0; d < 3; ++d) k[d] = g.pbc[d] ? -floor(cell_frac(g, xi, d)) : 0.0;
+  if (k[0] == 0.0 && k[1] == 0.0 && k[2] == 0.0) return;
+  for (int d = 0; d < 3; ++d) xi[d] += k[0] * g.h[d] + k[1] * g.h[3 + d] + k[2] * g.h[6 + d];
+}
+// cell (row-major, rows = lattice vectors), its inverse and rc / height; ArgError for a singular or non-finite cell
+static CellGeom cell_geometry(const char *who, const double *cell, const int *pbc, double rc) {
+  CellGeom g;
+  double scale = 0.0;
+  for (int k = 0; k < 9; ++k) {
+    if (!std::isfinite(cell[k])) throw ArgError(std::string(who) + ": the cell has a non-finite entry");
+    g.h[k] = cell[k];
+    scale = std::max(scale, std::fabs(cell[k]));
+  }
+  const double *a = g.h, *b = g.h + 3, *c = g.h + 6;
+  const double bc[3] = {b[1] * c[2] - b[2] * c[1], b[2] * c[0] - b[0] * c[2], b[0] * c[1] - b[1] * c[0]};
+  const double ca[3] = {c[1] * a[2] - c[2] * a[1], c[2] * a[0] - c[0] * a[2], c[0] * a[1] - c[1] * a[0]};
+  const double ab[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+  const double det = a[0] * bc[0] + a[1] * bc[1] + a[2] * bc[2];
+  if (!std::isfinite(det) || !(std::fabs(det) > 1e-12 * scale * scale * scale)) throw ArgError(std::string(who) + ": the cell is singular");
+  const double *cr[3] = {bc, ca, ab};                      // column d of cell^-1 = (cross product of the other two rows) / det
+  for (int d = 0; d < 3; ++d) {
+    double nrm = 0.0;
+    for (int k = 0; k < 3; ++k) { g.inv[3 * k + d] = cr[d][k] / det; nrm += cr[d][k] * cr[d][k]; }
+    g.m[d] = rc * std::sqrt(nrm) / std::fabs(det);         // rc / h_d,  h_d = volume / |cross product|
+    g.pbc[d] = pbc[d] != 0;
+  }
+  return g;
+}
+void wrap_cell(Model &m, int n, double *x, const double *cell, const int *pbc, hipStream_t s) {
+  const CellGeom g = cell_geometry("ahip_wrap_cell_dev", cell, pbc, 0.0);
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_cell_wrap, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, x, g);
+  AHIP_CHECK(hipGetLastError());
+}
+int borders_cell(Model &m, int nlocal, const double *x, const int *mtype, const double *cell, const int *pbc, double rc, int capacity,
+                 double *xg, int *mtg, long long *src, double *shift, hipStream_t s) {
+  const CellGeom g = cell_geometry("ahip_borders_cell_dev", cell, pbc, rc);
+  double most = (double)nlocal;                            // images of a wrapped atom: at most 2 ceil(m_d) + 1 along a periodic axis
+  for (int d = 0; d < 3; ++d) if (g.pbc[d]) most *= 2.0 * std::ceil(g.m[d]) + 1.0;
+  if (!(most <= 2147483647.0)) throw ArgError("ahip_borders_cell_dev: nlocal x images per atom exceeds 2^31 - 1 (the offsets are 32-bit); the cell is too thin for this cutoff");
+  if (nlocal <= 0) return 0;
+  if (!m.nb_state) m.nb_state = new NbState();
+  NbState &st = *(NbState *)m.nb_state;
+  st.cnt.reserve(((size_t)nlocal + 1) * sizeof(int));
+  st.off.reserve(((size_t)nlocal + 2) * sizeof(int));
+  const unsigned B = 256;
+  hipLaunchKernelGGL(k_cell_count, dim3((unsigned)((nlocal + B - 1) / B)), dim3(B), 0, s, nlocal, x, g, st.cnt.as<int>());
+  AHIP_CHECK(prim_exclusive_scan_i32(m.prim, st.cnt.as<int>(), st.off.as<int>(), nlocal, s));
+  int tot = 0;
+  AHIP_CHECK(hipMemcpyAsync(&tot, st.off.as<int>() + nlocal, sizeof(int), hipMemcpyDeviceToHost, s));
+  // one thread per row the caller has room for; the threads beyond the total (known on the device only, so far) leave at once
+  if (capacity > 0)
+    hipLaunchKernelGGL(k_cell_fill, dim3((unsigned)(((long long)capacity + B - 1) / B)), dim3(B), 0, s, nlocal, x, mtype, g, st.off.as<int>(), capacity, xg, mtg, src, shift);
+  AHIP_CHECK(hipStreamSynchronize(s));
+  AHIP_CHECK(hipGetLastError());
+  if (tot < 0) throw ArgError("ahip_borders_cell_dev: more than 2^31 - 1 images (positions far outside the cell: wrap them first)");
+  return tot;             // > capacity: nothing beyond the capacity was written; the caller retries with larger arrays
+}
+// bounding box of the cell's eight corners, widened by `margin`: what the list build bins over (a ghost outside it is farther than the margin from the cell in
+// one coordinate, hence nobody's neighbour; bin_coord clamps it into an edge bin)
+void cell_bounding_box(const double *cell, double margin, double *lo, double *hi) {
+  for (int d = 0; d < 3; ++d) {
+    double l = 0.0, h = 0.0;
+    for (int k = 0; k < 3; ++k) { l += std::min(cell[3 * k + d], 0.0); h += std::max(cell[3 * k + d], 0.0); }
+    lo[d] = l - margin; hi[d] = h + margin;
+  }
+}
+
 void neigh_free(Model &m) {
   if (!m.nb_state) return;
   NbState *st = (NbState *)m.nb_state;

@@ -99,6 +99,15 @@ class HipBackend:
         return self.model.borders_local_dev(nlocal, x.data_ptr(), mtype.data_ptr(), lo, hi, box, rc, capacity, xg.data_ptr(), mtg.data_ptr(),
                                             src.data_ptr(), shift.data_ptr())
 
+    def wrap_cell(self, n: int, x, cell, pbc) -> None:
+        """the first n rows of x back into a general cell along its periodic axes, in place (ahip_wrap_cell_dev)"""
+        self.model.wrap_cell_dev(n, x.data_ptr(), cell, pbc)
+
+    def borders_cell(self, nlocal: int, x, mtype, cell, pbc, rc: float, capacity: int, xg, mtg, src, shift) -> int:
+        """ghosts of a single rank in a general cell -- triclinic, thinner than rc, open axes (ahip_borders_cell_dev)"""
+        return self.model.borders_cell_dev(nlocal, x.data_ptr(), mtype.data_ptr(), cell, pbc, rc, capacity, xg.data_ptr(), mtg.data_ptr(),
+                                           src.data_ptr(), shift.data_ptr())
+
     def reneighbor_flag(self, n: int, x, x_hold, v, dt: float, half_skin: float, flag) -> None:
         """flag[0] = max displacement since the last build + 2 dt max|v| > half_skin (ahip_reneighbor_flag_dev)."""
         self.model.reneighbor_flag_dev(n, x.data_ptr(), x_hold.data_ptr() if n else 0, v.data_ptr(), dt, half_skin, flag.data_ptr())
@@ -121,7 +130,9 @@ class Simulation:
     def __init__(self, backend, box: Sequence[float], r_max: float, skin: float, x_global: np.ndarray,
                  mtype_global: np.ndarray, v_global: Optional[np.ndarray], device: torch.device,
                  grid: Tuple[int, int, int] = (1, 1, 1), rank: int = 0, dist=None, dt: float = 0.001, overlap: Optional[bool] = None,
-                 neigh_every: int = 1, neigh_delay: int = 0, neigh_check: bool = True):
+                 neigh_every: int = 1, neigh_delay: int = 0, neigh_check: bool = True, pbc: Sequence[bool] = (True, True, True)):
+        """`box`: the three edge lengths of an orthogonal periodic box (brick decomposition over `grid`, every brick at least r_max + skin thick), or a 3x3
+        matrix whose rows are the lattice vectors of ANY cell -- triclinic, thinner than the cutoff, with open axes (`pbc`) -- on one rank."""
         self.backend = backend
         # Overlapped schedule (SURVEY 8e): local atoms are ordered interior-first at every re-neighboring; the first half of
         # the interior centres is evaluated while ghost positions travel (forward comm), then the boundary centres, and the
@@ -130,6 +141,22 @@ class Simulation:
         # Default: overlapped when there is an exchange between ranks to hide; one rank evaluates all centres in one call (three
         # launches instead of one cost 2.5 % at 1 M atoms on one GPU: profiles/r02_a_overlap_1gpu.md).
         nranks = int(grid[0]) * int(grid[1]) * int(grid[2])
+        # General-cell mode (a 3x3 `box`): one rank owns every atom; wrap and ghosts come from the library (ahip_wrap_cell_dev, ahip_borders_cell_dev), the
+        # per-step exchange is the local plan.  A 3-vector `box` takes none of these branches.
+        self.cell = None
+        self.pbc = tuple(bool(p) for p in pbc)
+        if len(self.pbc) != 3:
+            raise ValueError("pbc must have three entries")
+        if np.asarray(box).shape == (3, 3):
+            if nranks != 1 or overlap:
+                raise ValueError("a 3x3 box (general cell) runs on one rank only, grid (1, 1, 1), with overlap off")
+            if not (hasattr(backend, "wrap_cell") and hasattr(backend, "borders_cell")):
+                raise ValueError("a 3x3 box (general cell) needs a backend with wrap_cell and borders_cell")
+            self.cell = np.ascontiguousarray(box, dtype=np.float64)
+            if not np.all(np.isfinite(self.cell)) or abs(np.linalg.det(self.cell)) <= 1e-12 * np.abs(self.cell).max() ** 3:
+                raise ValueError("a 3x3 box (general cell) must be a non-singular matrix of lattice vectors")
+        elif not all(self.pbc):
+            raise ValueError("open axes (pbc) need a 3x3 box")
         self.overlap = (nranks > 1 if overlap is None else bool(overlap)) and hasattr(backend, "compute_range")
         self.comm_stream = torch.cuda.Stream(device) if (self.overlap and device.type == "cuda") else None
         if self.comm_stream is not None and nranks > 1 and hasattr(backend, "model"):
@@ -158,13 +185,19 @@ class Simulation:
         self.dt = dt
         self.nranks = self.grid[0] * self.grid[1] * self.grid[2]
         self.coord = (rank // (self.grid[1] * self.grid[2]), (rank // self.grid[2]) % self.grid[1], rank % self.grid[2])
-        self.lo = np.array([self.box[d] * self.coord[d] / self.grid[d] for d in range(3)])
-        self.hi = np.array([self.box[d] * (self.coord[d] + 1) / self.grid[d] for d in range(3)])
-        for d in range(3):
-            if self.hi[d] - self.lo[d] < self.rc:
-                raise ValueError("sub-domain thinner than r_max+skin: use fewer ranks along that dimension")
         xg = np.asarray(x_global, dtype=np.float64)
-        own = np.all((xg >= self.lo) & (xg < self.hi), axis=1)
+        if self.cell is not None:
+            # lo / hi: the bounding box of the cell's eight corners (the list build bins over it, widened by rc); every atom is owned, wrapped or not
+            self.lo = np.minimum(self.cell, 0.0).sum(axis=0)
+            self.hi = np.maximum(self.cell, 0.0).sum(axis=0)
+            own = np.ones(len(xg), dtype=bool)
+        else:
+            self.lo = np.array([self.box[d] * self.coord[d] / self.grid[d] for d in range(3)])
+            self.hi = np.array([self.box[d] * (self.coord[d] + 1) / self.grid[d] for d in range(3)])
+            for d in range(3):
+                if self.hi[d] - self.lo[d] < self.rc:
+                    raise ValueError("sub-domain thinner than r_max+skin: use fewer ranks along that dimension")
+            own = np.all((xg >= self.lo) & (xg < self.hi), axis=1)
         idx = np.flatnonzero(own)
         self.natoms_global = len(xg)
         self.nlocal = len(idx)
@@ -405,7 +438,41 @@ class Simulation:
         self.nall = nall
         self._ghost_src = self._ghost_shift = None
 
+    def _migrate_cell(self) -> None:
+        """General cell, one rank: nobody changes owner, the atoms only go back into the cell along its periodic axes (one launch, nothing read back)."""
+        n = self.nlocal
+        self.x, self.v, self.tag, self.mtype = self.x[:n], self.v[:n], self.tag[:n], self.mtype[:n]
+        self.backend.wrap_cell(n, self.x, self.cell, self.pbc)
+
+    def _borders_cell(self) -> None:
+        """General cell, one rank: the ghosts are the images n != 0 of the rank's own atoms with -rc / h_d <= s_d + n_d < 1 + rc / h_d on every periodic axis
+        (ahip_borders_cell_dev: any number of images per direction), with the capacity-retry protocol of _borders_local."""
+        nl = self.nlocal
+        if getattr(self, "_cell_margin", None) is None:
+            inv = np.linalg.inv(self.cell)
+            self._cell_margin = self.rc * np.linalg.norm(inv, axis=0)        # rc / height per axis
+        shell = np.prod([1.0 + 2.0 * m for m, p in zip(self._cell_margin, self.pbc) if p])
+        cap = max(1024, int(1.25 * getattr(self, "_nghost_last", 0)) or int(nl * (shell - 1.0) * 1.25) + 1024)
+        while True:                                            # locals and images in one allocation: the call writes the images behind the locals
+            xa = torch.empty((nl + cap, 3), dtype=torch.float64, device=self.dev)
+            mta = torch.empty(nl + cap, dtype=torch.int32, device=self.dev)
+            src = torch.empty(cap, dtype=torch.long, device=self.dev)
+            shv = torch.empty((cap, 3), dtype=torch.float64, device=self.dev)
+            ng = self.backend.borders_cell(nl, self.x, self.mtype, self.cell, self.pbc, self.rc, cap, xa[nl:], mta[nl:], src, shv)
+            if ng <= cap:
+                break
+            cap = int(1.1 * ng) + 64
+        self._nghost_last = ng
+        self.swaps = []
+        xa[:nl] = self.x[:nl]
+        mta[:nl] = self.mtype[:nl]
+        self.x, self.mtype = xa[: nl + ng], mta[: nl + ng]
+        self.nall = nl + ng
+        self._ghost_src, self._ghost_shift = (src[:ng], shv[:ng]) if ng else (None, None)
+
     def _migrate(self) -> None:
+        if self.cell is not None:
+            return self._migrate_cell()
         if self._lib_reneighbor():
             return self._migrate_lib()
         n = self.nlocal
@@ -468,6 +535,8 @@ class Simulation:
 
     def _borders(self) -> None:
         self._lib_plan = False
+        if self.cell is not None:
+            return self._borders_cell()
         if self._borders_local():
             return
         if self._lib_reneighbor():
