@@ -365,6 +365,35 @@ int ahip_compute_cell(ahip_model *m, int natoms, const double *x, const int *mty
                       double *eatom, double *eng, double *virial);
 int ahip_last_cell_rows(ahip_model *m, int *nrows, long long *row_atom);
 
+/* A BATCH of structures in one call: what ahip_compute_cell computes for each of `nstruct` structures alone, with one upload, one ghost build, one neighbor
+ * list and one evaluation for all of them (a data set of small cells is launch- and synchronisation-bound one structure at a time).  HOST pointers.
+ *   first  [nstruct + 1], first[0] = 0, non-decreasing: structure s owns the atoms first[s] .. first[s+1] - 1 (an empty structure is allowed; nstruct == 0 too)
+ *   x      [first[nstruct]][3], mtype [first[nstruct]]      cells [nstruct][9], pbc [nstruct][3]: per structure, the conventions of ahip_compute_cell
+ *   f, eatom (or NULL): WRITTEN in the caller's atom order, ghost forces already added to their sources
+ *   eng    [nstruct];  virial [nstruct][6] or NULL: xx,yy,zz,xy,xz,yz in LAMMPS order and sign.  An empty structure gives 0.
+ * How: every structure keeps its own frame for the wrap and for its ghost images (per structure exactly the rows, order, sources and shifts of
+ * ahip_borders_cell_dev; one scan over all atoms).  Before the list build every row is translated by its structure's origin: uniform slots of the largest extent
+ * of any structure plus rc + 1e-6 on a near-cubic grid, so that the batch is ONE non-periodic cloud in which no edge joins two structures (the model is
+ * translation-invariant, positions and edge vectors are float64).  eng[s] is the sum of the per-atom energies of s; virial[s] is the sum of x_row (x) F_row over
+ * the atoms and ghosts of s in its own frame, before the ghost forces go home -- the same number on every kernel path.  Three synchronisations besides the staged
+ * copies (one packed upload; the downloads of the sums, f, eatom and the ghost sources, each of which waits for its own copy): the ghost total, the one inside
+ * the list build, the final one.
+ * Errors are AHIP_ERR_ARG before any launch and before anything is written, and name the structure: a singular or non-finite cell, a non-finite position, a type
+ * outside the model's, `first` not non-decreasing, atoms + images beyond 2^31 - 1 rows.  One error comes late, behind the evaluation, with eng / virial already
+ * zeroed and f not written: an explicit active set (ahip_set_active_types) that leaves out a type in use (AHIP_ERR_ARG), like the float16-range alarm below.  RULE: the list is binned over all slots, so a very uneven batch (one
+ * large cell among many small ones) wastes bins; when the grid would exceed 2^26 bins the call returns AHIP_ERR_ARG with "split the batch" in the message --
+ * call again with fewer, or more even, structures.  The float16-range alarm is handled as in ahip_compute_cell: under fused_arith=auto the WHOLE batch is
+ * evaluated again on the float32 instance; under an explicit f16x2 the call returns AHIP_ERR_STATE and f is not written.  A model of more than 16 types takes its
+ * active set from the union of the types present.  ahip_last_path, ahip_get_edges and ahip_last_cell_rows keep working: the rows are all atoms of the batch
+ * followed by all ghosts (grouped by structure, in order), row_atom is the atom's index in the batch.  ahip_last_cells_ghosts gives the ghosts per structure of
+ * the last batch (nghost: room for nstruct entries, or NULL for the count alone).  Both are set when a call has SUCCEEDED: a call refused for its arguments leaves
+ * them as they were, a call that fails later leaves nothing to report (AHIP_ERR_STATE from both until the next success).  ahip_last_cells_ghosts is not reset by
+ * a later ahip_compute_cell: it keeps describing the last successful batch.  A batch without atoms launches nothing: rows and ghost counts are 0, while the
+ * neighbor list and the edges (ahip_get_edges) stay those of the evaluation before. */
+int ahip_compute_cells(ahip_model *m, int nstruct, const int *first, const double *x, const int *mtype, const double *cells, const int *pbc, double skin,
+                       double *f, double *eatom, double *eng, double *virial);
+int ahip_last_cells_ghosts(ahip_model *m, int *nstruct, long long *nghost);
+
 /* v += dtf*f/m ; x += dt*v  style velocity-Verlet half steps on device arrays (NVE).
  *   mode 0: v += 0.5*dt*f*ftm2v/mass[type]; x += dt*v      (initial_integrate)
  *   mode 1: v += 0.5*dt*f*ftm2v/mass[type]                  (final_integrate)

@@ -4,6 +4,7 @@
     from pair_allegro_amd.calculator import Calculator
     calc = Calculator("model.nequip.pth")
     out = calc.compute(cell, positions, symbols)          # out["energy"], out["forces"], out["stress"]
+    outs = calc.compute_many([(cell, positions, symbols), ...])      # a data set: one library call for many structures (ahip_compute_cells)
 
 Any cell works: triclinic, thinner than the cutoff (several images per direction), open axes.  No ASE import: an ASE calculator is three lines
 around `compute(atoms.cell.array, atoms.positions, atoms.get_chemical_symbols(), atoms.pbc)`.
@@ -63,3 +64,68 @@ class Calculator:
             stress = -vm / abs(np.linalg.det(cell))
         info = dict(path=self.model.last_path, nghost=int(len(rows) - len(pos)), nedges=self.model.nedges(), row_atom=rows)
         return dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, info=info)
+
+    def compute_many(self, structures: Sequence, max_atoms: int = 1 << 20) -> list:
+        """A data set in as few library calls as possible (ahip_compute_cells: one upload, one ghost build, one neighbor list and one evaluation per call,
+        where `compute` pays all of them per structure).  `structures`: a sequence of (cell, positions, symbols) or (cell, positions, symbols, pbc), each
+        as in `compute`; an empty structure is allowed.
+
+        Returns a list of dicts, one per structure, in order: energy, forces, atomic_energy, virial, stress (None unless all three axes are periodic) and info:
+        path, nghost, batch (the index of the library call that evaluated it).  The sequence is cut into consecutive calls of at most `max_atoms` atoms (a single
+        larger structure goes alone); a call the library refuses as too uneven for one neighbor grid ("split the batch") is halved and repeated.  An unknown
+        symbol is a ValueError that names the structure and the symbol, before any call."""
+        if max_atoms < 1:
+            raise ValueError("max_atoms must be >= 1")
+        items = []
+        for k, st in enumerate(structures):
+            if len(st) not in (3, 4):
+                raise ValueError(f"structure {k}: expected (cell, positions, symbols[, pbc])")
+            cell = np.asarray(st[0], dtype=np.float64)
+            pos = np.asarray(st[1], dtype=np.float64).reshape(-1, 3)
+            if cell.shape != (3, 3):
+                raise ValueError(f"structure {k}: cell must be a 3x3 matrix of lattice vectors (rows), got shape {cell.shape}")
+            if len(st[2]) != len(pos):
+                raise ValueError(f"structure {k}: positions and symbols differ in length")
+            pbc = tuple(bool(p) for p in (st[3] if len(st) == 4 else (True, True, True)))
+            if len(pbc) != 3:
+                raise ValueError(f"structure {k}: pbc must have three entries")
+            try:
+                mt = self.model_types(st[2])
+            except ValueError as e:
+                raise ValueError(f"structure {k}: {e}") from None
+            items.append((cell, pos, mt, pbc))
+        chunks, lo = [], 0
+        while lo < len(items):                     # consecutive chunks of at most max_atoms atoms, at least one structure each
+            hi, n = lo + 1, len(items[lo][1])
+            while hi < len(items) and n + len(items[hi][1]) <= max_atoms:
+                n += len(items[hi][1])
+                hi += 1
+            chunks.append((lo, hi))
+            lo = hi
+        results, ncall = [None] * len(items), 0
+        while chunks:
+            lo, hi = chunks.pop(0)
+            part = items[lo:hi]
+            first = np.concatenate([[0], np.cumsum([len(p[1]) for p in part])]).astype(np.int32)
+            x = np.concatenate([p[1] for p in part]) if part else np.zeros((0, 3))
+            mt = np.concatenate([p[2] for p in part]) if part else np.zeros(0, np.int32)
+            try:
+                eng, f, ea, vir = self.model.compute_cells(first, x, mt, np.stack([p[0] for p in part]), np.array([p[3] for p in part]), self.skin)
+            except capi.AhipError as e:
+                if e.code == capi.AHIP_ERR_ARG and "split the batch" in e.msg and hi - lo > 1:
+                    mid = lo + (hi - lo) // 2
+                    chunks[:0] = [(lo, mid), (mid, hi)]
+                    continue
+                raise
+            ghosts, path = self.model.last_cells_ghosts(), self.model.last_path
+            for k, (cell, pos, _, pbc) in enumerate(part):
+                a, b = int(first[k]), int(first[k + 1])
+                v = vir[k].copy()
+                stress = None
+                if all(pbc):
+                    vm = np.array([[v[0], v[3], v[4]], [v[3], v[1], v[5]], [v[4], v[5], v[2]]])
+                    stress = -vm / abs(np.linalg.det(cell))
+                results[lo + k] = dict(energy=float(eng[k]), forces=f[a:b].copy(), atomic_energy=ea[a:b].copy(), virial=v, stress=stress,
+                                       info=dict(path=path, nghost=int(ghosts[k]), batch=ncall))
+            ncall += 1
+        return results

@@ -39,6 +39,7 @@ SYMBOLS = [
     "ahip_debug_scan_i32", "ahip_debug_sum_columns_f64", "ahip_debug_max_i32", "ahip_debug_gemm_f32",
     "ahip_set_active_types", "ahip_get_active_types",
     "ahip_wrap_cell_dev", "ahip_borders_cell_dev", "ahip_compute_cell", "ahip_last_cell_rows",
+    "ahip_compute_cells", "ahip_last_cells_ghosts",
 ]
 
 
@@ -389,6 +390,46 @@ class Model:
         out = np.zeros(n.value, dtype=np.int64)
         if n.value:
             self.L.check(self.L.lib.ahip_last_cell_rows(self.h, C.byref(n), _p(out, C.c_longlong)))
+        return out
+
+    def compute_cells(self, first, x: np.ndarray, mtype: np.ndarray, cells, pbc, skin: float = 0.0, want_eatom: bool = True, f: Optional[np.ndarray] = None):
+        """A batch of structures in one call (ahip_compute_cells).  `first` [B + 1] (first[0] = 0, non-decreasing): structure s owns the atoms first[s] .. first[s+1] - 1
+        of `x` / `mtype`; `cells` [B][3][3] (rows are lattice vectors), `pbc` [B][3].  Returns (energies [B], forces [n][3], atomic energies [n] or None, virials [B][6]).
+        `f`: an own C-contiguous float64 [n][3] array to receive the forces (an argument error leaves it as it was)."""
+        first = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        if len(first) < 1:
+            raise ValueError("first needs at least one entry (first[0] = 0)")
+        B = len(first) - 1
+        c = np.ascontiguousarray(cells, dtype=np.float64).reshape(-1)
+        p = np.ascontiguousarray(np.asarray(pbc).astype(bool), dtype=np.int32).reshape(-1)
+        if c.size != 9 * B or p.size != 3 * B:
+            raise ValueError(f"cells must be [{B}][3][3] and pbc [{B}][3]")
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        mt = np.ascontiguousarray(mtype, dtype=np.int32).reshape(-1)
+        if len(mt) != len(x) or len(x) != max(int(first[-1]), 0):
+            raise ValueError("positions, types and first[-1] differ in length")
+        n = len(x)
+        if f is None:
+            f = np.zeros((n, 3))
+        elif f.dtype != np.float64 or f.shape != (n, 3) or not f.flags.c_contiguous:
+            raise ValueError("f must be a C-contiguous float64 array of shape [n][3]")
+        ea = np.zeros(n) if want_eatom else None
+        eng = np.zeros(B)
+        vir = np.zeros((B, 6))
+        self.L.lib.ahip_compute_cells.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                                  C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        self.L.check(self.L.lib.ahip_compute_cells(self.h, B, _p(first, C.c_int), _p(x, C.c_double), _p(mt, C.c_int), _p(c, C.c_double), _p(p, C.c_int), float(skin),
+                                                    _p(f, C.c_double), _p(ea, C.c_double), _p(eng, C.c_double), _p(vir, C.c_double)))
+        return eng, f, ea, vir
+
+    def last_cells_ghosts(self) -> np.ndarray:
+        """ghost images per structure of the last compute_cells (ahip_last_cells_ghosts)"""
+        n = C.c_int(0)
+        self.L.lib.ahip_last_cells_ghosts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+        self.L.check(self.L.lib.ahip_last_cells_ghosts(self.h, C.byref(n), None))
+        out = np.zeros(n.value, dtype=np.int64)
+        if n.value:
+            self.L.check(self.L.lib.ahip_last_cells_ghosts(self.h, C.byref(n), _p(out, C.c_longlong)))
         return out
 
     def nve_dev(self, mode: int, n: int, x_ptr: int, v_ptr: int, f_ptr: int, mtype_ptr: int, mass_by_mtype,

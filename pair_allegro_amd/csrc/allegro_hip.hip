@@ -253,7 +253,7 @@ void ahip_model_free(ahip_model *m) {
   for (DevBuf *b : {&m->b_flagwork, &m->b_ilist, &m->b_nloff, &m->b_nlj, &m->b_x, &m->b_ftype, &m->b_mtype, &m->b_f, &m->b_eatom,
                     &m->b_engvir, &m->b_cutsq, &m->b_cnt, &m->b_eoff, &m->b_eii, &m->b_ej, &m->b_rvec, &m->b_ett, &m->b_partial,
                     &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom,
-                    &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist, &m->c_x, &m->c_mtype, &m->c_f, &m->c_eatom, &m->c_src, &m->c_shift, &m->c_engvir})
+                    &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist, &m->c_x, &m->c_mtype, &m->c_f, &m->c_eatom, &m->c_src, &m->c_shift, &m->c_engvir, &m->c_in, &m->c_xp, &m->c_out})
     b->release();
   for (auto &t : m->slots) for (auto &e : t.ring) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (hipEvent_t e : m->f_events) (void)hipEventDestroy(e);
@@ -1478,11 +1478,143 @@ int ahip_last_cell_rows(ahip_model *m, int *nrows, long long *row_atom) {
   return guarded([&] {
     require_model(m);
     if (!nrows) throw ArgError("ahip_last_cell_rows: nrows is NULL");
-    if (m->cell_natoms < 0) throw StateError("ahip_last_cell_rows called before ahip_compute_cell");
+    if (m->cell_natoms < 0) throw StateError("ahip_last_cell_rows called before ahip_compute_cell (or after an ahip_compute_cells that failed)");
     *nrows = m->cell_natoms + (int)m->cell_src_host.size();
     if (!row_atom) return;
     for (int i = 0; i < m->cell_natoms; ++i) row_atom[i] = i;
     std::copy(m->cell_src_host.begin(), m->cell_src_host.end(), row_atom + m->cell_natoms);
+  });
+}
+
+int ahip_compute_cells(ahip_model *m, int nstruct, const int *first, const double *x, const int *mtype, const double *cells, const int *pbc, double skin,
+                       double *f, double *eatom, double *eng, double *virial) {
+  return guarded([&] {
+    require_model(m);
+    // ---- everything that can be refused is refused here: no launch before, nothing written before
+    if (nstruct < 0 || (nstruct > 0 && (!first || !cells || !pbc || !eng))) throw ArgError("ahip_compute_cells: bad argument");
+    if (!(skin >= 0.0) || !std::isfinite(skin)) throw ArgError("ahip_compute_cells: skin must be a finite number >= 0");
+    if (nstruct > 0 && first[0] != 0) throw ArgError("ahip_compute_cells: first[0] must be 0");
+    for (int s = 0; s < nstruct; ++s)
+      if (first[s + 1] < first[s])
+        throw ArgError("ahip_compute_cells: first is not non-decreasing: structure " + std::to_string(s) + " would have " + std::to_string(first[s + 1] - first[s]) + " atoms");
+    const int natoms = nstruct > 0 ? first[nstruct] : 0;
+    if (natoms > 0 && (!x || !mtype || !f)) throw ArgError("ahip_compute_cells: bad argument");
+    const int T = m->hm.num_types;
+    std::vector<int> sidx((size_t)natoms), present;
+    std::vector<char> seen((size_t)T, 0);
+    for (int s = 0; s < nstruct; ++s)
+      for (int i = first[s]; i < first[s + 1]; ++i) {
+        if (mtype[i] < 0 || mtype[i] >= T)
+          throw ArgError("ahip_compute_cells: structure " + std::to_string(s) + ", atom " + std::to_string(i - first[s]) + " has model type " + std::to_string(mtype[i]) +
+                         ", outside the model's " + std::to_string(T) + " types");
+        for (int d = 0; d < 3; ++d)
+          if (!std::isfinite(x[3 * (size_t)i + d])) throw ArgError("ahip_compute_cells: structure " + std::to_string(s) + ", atom " + std::to_string(i - first[s]) + ": a position is not finite");
+        seen[(size_t)mtype[i]] = 1;
+        sidx[(size_t)i] = s;
+      }
+    for (int t = 0; t < T; ++t) if (seen[(size_t)t]) present.push_back(t);       // the union of the types present: the active set of a model of more than 16 types
+    const double rc = *std::max_element(m->rcut_model_host.begin(), m->rcut_model_host.end()) + skin;
+    std::vector<unsigned char> table;
+    double lo[3], hi[3];
+    const size_t entry = cells_plan(nstruct, first, x, cells, pbc, rc, table, lo, hi);
+    // ---- accepted
+    for (int s = 0; s < nstruct; ++s) eng[s] = 0;
+    if (virial) for (size_t k = 0; k < 6 * (size_t)nstruct; ++k) virial[k] = 0;
+    // what the accessors report (ahip_last_cell_rows, ahip_last_cells_ghosts) is set when the call has succeeded; from here to there they have nothing to report,
+    // because the row buffers are being overwritten
+    const int guess = natoms == m->cell_natoms ? m->cell_nghost_last + m->cell_nghost_last / 8 : 0;
+    m->cell_natoms = -1; m->cells_nstruct = -1;
+    m->cell_src_host.clear();
+    if (natoms == 0) {                        // a batch without atoms: nothing is launched; the neighbor list and the edges of an earlier evaluation stay as they are
+      m->cell_natoms = 0; m->cell_nghost_last = 0;
+      m->cells_nstruct = nstruct; m->cells_nghost_host.assign((size_t)nstruct, 0);
+      return;
+    }
+    AHIP_CHECK(hipSetDevice(m->device));
+    hipStream_t s = nullptr;
+    // ONE upload: positions | structure table | model types | atom -> structure (packed on the host first: a second pass over the input, O(atoms), instead of
+    // four staged copies with a synchronisation each)
+    const size_t o_tab = (size_t)natoms * 3 * sizeof(double), o_mt = o_tab + table.size(), o_sidx = o_mt + (size_t)natoms * sizeof(int),
+                 n_in = o_sidx + (size_t)natoms * sizeof(int);
+    if (entry % 8 != 0) throw StateError("ahip_compute_cells: structure table entries are not 8-byte multiples");      // (the int arrays follow the table)
+    std::vector<unsigned char> in(n_in);
+    std::memcpy(in.data(), x, o_tab);
+    std::memcpy(in.data() + o_tab, table.data(), table.size());
+    std::memcpy(in.data() + o_mt, mtype, (size_t)natoms * sizeof(int));
+    std::memcpy(in.data() + o_sidx, sidx.data(), (size_t)natoms * sizeof(int));
+    m->c_in.reserve(n_in);
+    copy_h2d(m->c_in.p, in.data(), n_in);
+    const char *base = m->c_in.as<char>();
+    const double *x_in = (const double *)base;
+    const void *tab = base + o_tab;
+    const int *mt_in = (const int *)(base + o_mt), *sidx_dev = (const int *)(base + o_sidx);
+    // wrap, count, scan (one read-back: the ghost total), fill.  The rows are the atoms of the batch, then its ghosts; the first guess of their number is the
+    // last call's, and a grown buffer loses its content, so the wrap runs again behind it (the counts depend on the wrapped positions alone)
+    auto room = [&](size_t ghosts) {
+      m->c_x.reserve(((size_t)natoms + ghosts) * 3 * sizeof(double));
+      m->c_mtype.reserve(((size_t)natoms + ghosts) * sizeof(int));
+      cells_wrap(natoms, x_in, mt_in, sidx_dev, tab, m->c_x.as<double>(), m->c_mtype.as<int>(), s);
+    };
+    room((size_t)guess);
+    const int ng = cells_count(*m, natoms, m->c_x.as<double>(), sidx_dev, tab, s);
+    if (ng > guess) room((size_t)ng);
+    const int nall = natoms + ng;             // (cells_plan has bounded atoms + images by 2^31 - 1 for any wrapped position)
+    m->c_src.reserve(std::max<size_t>((size_t)ng, 1) * sizeof(long long));
+    m->c_shift.reserve(std::max<size_t>((size_t)ng, 1) * 3 * sizeof(double));
+    m->c_xp.reserve((size_t)nall * 3 * sizeof(double));
+    cells_fill(*m, natoms, ng, m->c_x.as<double>(), m->c_mtype.as<int>(), sidx_dev, tab, m->c_x.as<double>() + 3 * (size_t)natoms, m->c_mtype.as<int>() + natoms,
+               m->c_src.as<long long>(), m->c_shift.as<double>(), s);
+    cells_place(natoms, nall, m->c_x.as<double>(), sidx_dev, m->c_src.as<long long>(), tab, m->c_xp.as<double>(), s);
+    m->active_mapped = present;               // (run_model: resolve_active)
+    neigh_build(*m, natoms, nall, m->c_xp.as<double>(), lo, hi, rc, s);
+    m->c_f.reserve((size_t)nall * 3 * sizeof(double));
+    m->c_eatom.reserve((size_t)nall * sizeof(double));
+    m->c_engvir.reserve(8 * sizeof(double));
+    m->c_out.reserve((size_t)nstruct * 8 * sizeof(double));
+    // (twice at most, as in ahip_compute_cell: under fused_arith=auto a float16-range alarm repeats the whole batch on the float32 instance)
+    for (int attempt = 0;; ++attempt) {
+      AHIP_CHECK(hipMemsetAsync(m->c_f.p, 0, (size_t)nall * 3 * sizeof(double), s));
+      AHIP_CHECK(hipMemsetAsync(m->c_eatom.p, 0, (size_t)nall * sizeof(double), s));
+      rethrow_code(ahip_compute_dev(m, natoms, ng, m->c_xp.as<double>(), m->c_mtype.as<int>(), nullptr, m->c_f.as<double>(), m->c_eatom.as<double>(),
+                                    m->c_engvir.as<double>(), s));
+      cells_reduce(*m, nstruct, natoms, tab, m->c_x.as<double>(), m->c_f.as<double>(), m->c_eatom.as<double>(), m->c_out.as<double>(), s);
+      comm_scatter_local(ng, natoms, m->c_src.as<long long>(), m->c_f.as<double>(), s);      // ghost forces go home (newton on), behind the row sums
+      AHIP_CHECK(hipGetLastError());
+      AHIP_CHECK(hipStreamSynchronize(s));
+      if (const int bad = inactive_take(*m)) throw ArgError("ahip_compute_cells: " + inactive_message(*m, bad, "this evaluation") + " (nothing was written to f)");
+      if (alarm_take(*m)) {
+        if (arith_may_degrade(*m) && attempt == 0) {
+          arith_degrade(*m, "an activation left float16's range (non-finite edge gradient on the f16x2 arithmetic); the evaluation was repeated");
+          continue;
+        }
+        throw StateError("fused_arith=f16x2: an edge gradient was not finite (an activation left float16's range, or the input was not finite): the forces of this "
+                         "batch are invalid and were not written to f; set option fused_arith=f32 (or auto) for this model");
+      }
+      break;
+    }
+    std::vector<double> out((size_t)nstruct * 8);
+    copy_d2h(out.data(), m->c_out.p, out.size() * sizeof(double));
+    copy_d2h(f, m->c_f.p, (size_t)natoms * 3 * sizeof(double));
+    if (eatom) copy_d2h(eatom, m->c_eatom.p, (size_t)natoms * sizeof(double));
+    m->cell_src_host.resize((size_t)ng);
+    if (ng > 0) copy_d2h(m->cell_src_host.data(), m->c_src.p, (size_t)ng * sizeof(long long));
+    m->cell_natoms = natoms; m->cell_nghost_last = ng;
+    m->cells_nstruct = nstruct; m->cells_nghost_host.assign((size_t)nstruct, 0);
+    for (int k = 0; k < nstruct; ++k) {
+      eng[k] = out[8 * (size_t)k];
+      if (virial) for (int c = 0; c < 6; ++c) virial[6 * (size_t)k + c] = out[8 * (size_t)k + 1 + c];
+      m->cells_nghost_host[(size_t)k] = (long long)out[8 * (size_t)k + 7];
+    }
+  });
+}
+
+int ahip_last_cells_ghosts(ahip_model *m, int *nstruct, long long *nghost) {
+  return guarded([&] {
+    require_model(m);
+    if (!nstruct) throw ArgError("ahip_last_cells_ghosts: nstruct is NULL");
+    if (m->cells_nstruct < 0) throw StateError("ahip_last_cells_ghosts called before ahip_compute_cells (or after one that failed)");
+    *nstruct = m->cells_nstruct;
+    if (nghost) std::copy(m->cells_nghost_host.begin(), m->cells_nghost_host.end(), nghost);
   });
 }
 

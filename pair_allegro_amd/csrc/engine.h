@@ -180,6 +180,11 @@ struct Model {
   DevBuf c_x, c_mtype, c_f, c_eatom, c_src, c_shift, c_engvir;
   int cell_nghost_last = 0, cell_natoms = -1;
   std::vector<long long> cell_src_host;
+  // ahip_compute_cells (the rows above are then those of the whole batch): the packed upload (positions, structure table, model types, atom -> structure), the
+  // rows at their places in the cloud, the 8 sums per structure, and the last batch's ghost counts (ahip_last_cells_ghosts)
+  DevBuf c_in, c_xp, c_out;
+  int cells_nstruct = -1;
+  std::vector<long long> cells_nghost_host;
 
   // edge list + workspace
   DevBuf b_cnt, b_eoff, b_eii, b_ej, b_rvec, b_partial, b_ws, b_misc;
@@ -436,6 +441,22 @@ void wrap_cell(Model &m, int n, double *x, const double *cell, const int *pbc, h
 int borders_cell(Model &m, int nlocal, const double *x, const int *mtype, const double *cell, const int *pbc, double rc, int capacity,
                  double *xg, int *mtg, long long *src, double *shift, hipStream_t s);
 void cell_bounding_box(const double *cell, double margin, double *lo, double *hi);
+// A batch of cells as one non-periodic cloud (neigh.hip).  cells_plan is host-only and throws ArgError before any launch: per structure the geometry (a singular
+// or non-finite cell names its index), the 32-bit bound on atoms + images, the extent of its rows -- the Cartesian bounding box of its parallelepiped with the
+// fractional range [-m_d, 1 + m_d] on periodic axes and the range its atoms have on open ones -- and its origin: uniform slots of the largest extent plus
+// rc + 1e-6 on a near-cubic grid, so that no row of one structure is within rc + 1e-6 of a row of another.  `table` receives nstruct + 1 device-layout
+// entries (returns the size of one); lo / hi the bounding box of all slots, and more than 2^26 bins of neigh_build's grid over it is the "split the batch" error.
+// The others enqueue on `s`: wrap (k_cell_wrap per structure, out of place), count + ONE scan over the batch (returns the ghost total: the one
+// synchronisation), fill (the rows borders_cell gives for each structure alone, src + first[s]), place (own frame + origin), reduce (out[8 s]: energy, virial
+// xx yy zz xy xz yz from the row sum of x (x) f before the ghost forces go home, ghost count).
+size_t cells_plan(int nstruct, const int *first, const double *x, const double *cells, const int *pbc, double rc, std::vector<unsigned char> &table, double *lo,
+                  double *hi);
+void cells_wrap(int natoms, const double *xin, const int *mtin, const int *sidx, const void *table, double *x, int *mt, hipStream_t s);
+int cells_count(Model &m, int natoms, const double *x, const int *sidx, const void *table, hipStream_t s);
+void cells_fill(Model &m, int natoms, int nghost, const double *x, const int *mtype, const int *sidx, const void *table, double *xg, int *mtg, long long *src,
+                double *shift, hipStream_t s);
+void cells_place(int natoms, int nall, const double *x, const int *sidx, const long long *src, const void *table, double *xp, hipStream_t s);
+void cells_reduce(Model &m, int nstruct, int natoms, const void *table, const double *x, const double *f, const double *eatom, double *out, hipStream_t s);
 // one rank, ghost g (row nlocal + g) an image of local row src[g]: f[src[g]] += f[nlocal + g] (comm.hip: the reverse exchange of the local plan)
 void comm_scatter_local(int nghost, int nlocal, const long long *src, double *f, hipStream_t s);
 void nve_first_step(Model &m, int n, int nall, double *x, double *v, double *f, const int *mtype, const double *mass_host, int ntypes, double dt, double ftm2v,

@@ -4,6 +4,7 @@
 // test deck's `fix nve` (/root/reference/tests/test_python_repro_allegro.py:84-120).
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "engine.h"
 #include "prims.h"
@@ -12,6 +13,7 @@ namespace ahip {
 
 struct NbState {
   DevBuf bin_of, bin_cnt, bin_start, bin_fill, sorted, cnt, off, nlj, ilist, box, mapper;
+  DevBuf goff;                             // ahip_compute_cells: the scanned ghost counts of the batch's atoms (they outlive the list build, which scans into `off`)
   long long cap_j = 0;
   DevBuf inv_mass;                         // nve helpers, more than 16 model types: 1 / mass by model type on the device ...
   std::vector<double> inv_mass_host;       // ... and what it holds (uploaded when it changes)
@@ -359,27 +361,20 @@ __device__ __host__ inline long long cell_image_box(const CellGeom &g, const dou
   *zero = in ? ((long long)(-lo[0]) * c[1] + (-lo[1])) * c[2] + (-lo[2]) : -1;
   return in ? tot - 1 : tot;
 }
-__global__ void k_cell_count(int n, const double *x, CellGeom g, int *cnt) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// The three per-row bodies below serve the single-cell kernels (geometry in the kernel arguments) and the batch kernels (geometry looked up per atom) alike,
+// so the two paths cannot drift apart.
+// ghosts of one atom, saturated to 32 bits (the host has bounded the sum for wrapped input; a far-away atom saturates instead of wrapping)
+__device__ inline int cell_count_row(const CellGeom &g, const double *xi) {
   int lo[3], c[3];
   long long zero;
-  const long long k = cell_image_box(g, x + 3 * i, lo, c, &zero);
-  cnt[i] = k > 2147483647LL ? 2147483647 : (int)k;      // (the host has bounded the sum for wrapped input; a far-away atom saturates instead of wrapping)
+  const long long k = cell_image_box(g, xi, lo, c, &zero);
+  return k > 2147483647LL ? 2147483647 : (int)k;
 }
-__global__ void k_cell_fill(int n, const double *x, const int *mtype, CellGeom g, const int *off, int capacity, double *xg, int *mtg, long long *src, double *shift) {
-  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= capacity || k >= off[n]) return;
-  int a = 0, b = n;                                       // largest a with off[a] <= k (off[a] <= k < off[b] throughout)
-  while (b - a > 1) {
-    const int mid = a + (b - a) / 2;
-    if (off[mid] <= (int)k) a = mid; else b = mid;
-  }
-  const double *xi = x + 3 * (long long)a;
+// ghost number `r` of the atom at xi (its rank among the atom's ghosts, n3 fastest, the zero image skipped) -> output row k; false when the atom has none
+__device__ inline bool cell_fill_row(const CellGeom &g, const double *xi, long long r, long long k, double *xg, double *shift) {
   int lo[3], c[3];
   long long zero;
-  if (cell_image_box(g, xi, lo, c, &zero) <= 0) return;    // (cannot happen behind a consistent scan: no row belongs to an atom without images)
-  long long r = k - off[a];
+  if (cell_image_box(g, xi, lo, c, &zero) <= 0) return false;    // (cannot happen behind a consistent scan: no row belongs to an atom without images)
   if (zero >= 0 && r >= zero) ++r;
   const int n3 = lo[2] + (int)(r % c[2]);
   r /= c[2];
@@ -389,18 +384,41 @@ __global__ void k_cell_fill(int n, const double *x, const int *mtype, CellGeom g
     shift[3 * k + d] = sh;
     xg[3 * k + d] = xi[d] + sh;
   }
-  mtg[k] = mtype[a];
-  src[k] = a;
+  return true;
 }
-// x += (the integer lattice combination that brings s_d into [0, 1) on every periodic axis); an atom already inside is not touched
-__global__ void k_cell_wrap(int n, double *x, CellGeom g) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double *xi = x + 3 * i;
+// xi += (the integer lattice combination that brings s_d into [0, 1) on every periodic axis); an atom already inside is not touched
+__device__ __host__ inline void cell_wrap_row(const CellGeom &g, double *xi) {
   double k[3];
   for (int d = 0; d < 3; ++d) k[d] = g.pbc[d] ? -floor(cell_frac(g, xi, d)) : 0.0;
   if (k[0] == 0.0 && k[1] == 0.0 && k[2] == 0.0) return;
   for (int d = 0; d < 3; ++d) xi[d] += k[0] * g.h[d] + k[1] * g.h[3 + d] + k[2] * g.h[6 + d];
+}
+// largest a in [0, n) with off[a] <= k, for 0 <= k < off[n]: the source atom of output row k
+__device__ inline int cell_row_atom(const int *off, int n, long long k) {
+  int a = 0, b = n;                                       // (off[a] <= k < off[b] throughout)
+  while (b - a > 1) {
+    const int mid = a + (b - a) / 2;
+    if (off[mid] <= (int)k) a = mid; else b = mid;
+  }
+  return a;
+}
+__global__ void k_cell_count(int n, const double *x, CellGeom g, int *cnt) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  cnt[i] = cell_count_row(g, x + 3 * i);
+}
+__global__ void k_cell_fill(int n, const double *x, const int *mtype, CellGeom g, const int *off, int capacity, double *xg, int *mtg, long long *src, double *shift) {
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= capacity || k >= off[n]) return;
+  const int a = cell_row_atom(off, n, k);
+  if (!cell_fill_row(g, x + 3 * (long long)a, k - off[a], k, xg, shift)) return;
+  mtg[k] = mtype[a];
+  src[k] = a;
+}
+__global__ void k_cell_wrap(int n, double *x, CellGeom g) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  cell_wrap_row(g, x + 3 * i);
 }
 // cell (row-major, rows = lattice vectors), its inverse and rc / height; ArgError for a singular or non-finite cell
 static CellGeom cell_geometry(const char *who, const double *cell, const int *pbc, double rc) {
@@ -426,6 +444,12 @@ static CellGeom cell_geometry(const char *who, const double *cell, const int *pb
   }
   return g;
 }
+// images of n wrapped atoms: at most 2 ceil(m_d) + 1 each along a periodic axis
+static double cell_most_images(const CellGeom &g, int n) {
+  double most = (double)n;
+  for (int d = 0; d < 3; ++d) if (g.pbc[d]) most *= 2.0 * std::ceil(g.m[d]) + 1.0;
+  return most;
+}
 void wrap_cell(Model &m, int n, double *x, const double *cell, const int *pbc, hipStream_t s) {
   const CellGeom g = cell_geometry("ahip_wrap_cell_dev", cell, pbc, 0.0);
   if (n <= 0) return;
@@ -435,8 +459,7 @@ void wrap_cell(Model &m, int n, double *x, const double *cell, const int *pbc, h
 int borders_cell(Model &m, int nlocal, const double *x, const int *mtype, const double *cell, const int *pbc, double rc, int capacity,
                  double *xg, int *mtg, long long *src, double *shift, hipStream_t s) {
   const CellGeom g = cell_geometry("ahip_borders_cell_dev", cell, pbc, rc);
-  double most = (double)nlocal;                            // images of a wrapped atom: at most 2 ceil(m_d) + 1 along a periodic axis
-  for (int d = 0; d < 3; ++d) if (g.pbc[d]) most *= 2.0 * std::ceil(g.m[d]) + 1.0;
+  const double most = cell_most_images(g, nlocal);
   if (!(most <= 2147483647.0)) throw ArgError("ahip_borders_cell_dev: nlocal x images per atom exceeds 2^31 - 1 (the offsets are 32-bit); the cell is too thin for this cutoff");
   if (nlocal <= 0) return 0;
   if (!m.nb_state) m.nb_state = new NbState();
@@ -466,10 +489,213 @@ void cell_bounding_box(const double *cell, double margin, double *lo, double *hi
   }
 }
 
+// ---- a batch of cells as ONE non-periodic cloud (ahip_compute_cells) ----
+// Every structure keeps its own frame for the wrap and for its ghost images; only before the list build is every row (atom or ghost) translated by its
+// structure's origin, chosen on the host so that rows of different structures are farther apart than the list cutoff.  Behind that the batch is one list of
+// centres like any other.  The table has one entry per structure plus a closing one whose `first` is the number of atoms.
+struct CellEntry {
+  CellGeom g;
+  double origin[3];     // added to the structure's rows for the list build and the evaluation
+  int first;            // its first atom
+  int pad;
+};
+// the single-cell kernels' row bodies with the geometry looked up per atom.  The wrap is out of place (the upload stays as it came); the model types travel along
+__global__ void k_cells_wrap(int n, const double *xin, const int *mtin, const int *sidx, const CellEntry *tab, double *x, int *mt) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double *xi = x + 3 * i;
+  for (int d = 0; d < 3; ++d) xi[d] = xin[3 * i + d];
+  mt[i] = mtin[i];
+  cell_wrap_row(tab[sidx[i]].g, xi);
+}
+__global__ void k_cells_count(int n, const double *x, const int *sidx, const CellEntry *tab, int *cnt) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  cnt[i] = cell_count_row(tab[sidx[i]].g, x + 3 * i);
+}
+// over the scan of the WHOLE batch: ascending source atom groups the ghosts by structure; src is the atom's index in the batch
+__global__ void k_cells_fill(int n, const double *x, const int *mtype, const int *sidx, const CellEntry *tab, const int *off, int capacity, double *xg, int *mtg,
+                             long long *src, double *shift) {
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= capacity || k >= off[n]) return;
+  const int a = cell_row_atom(off, n, k);
+  if (!cell_fill_row(tab[sidx[a]].g, x + 3 * (long long)a, k - off[a], k, xg, shift)) return;
+  mtg[k] = mtype[a];
+  src[k] = a;
+}
+// rows (atoms, then ghosts) in the structures' own frames -> their places in the cloud
+__global__ void k_cells_place(int natoms, int nall, const double *x, const int *sidx, const long long *src, const CellEntry *tab, double *xp) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nall) return;
+  const long long a = r < natoms ? r : src[r - natoms];
+  const double *o = tab[sidx[a]].origin;
+  for (int d = 0; d < 3; ++d) xp[3 * r + d] = x[3 * r + d] + o[d];
+}
+// Energy, virial and ghost count of every structure: one workgroup per structure, float64, a fixed order (thread t takes the rows t, t + NT, ..., atoms before
+// ghosts; then a tree over the threads).  The virial is the row sum  W = sum_rows x_row (x) F_row  over the structure's atoms and ghosts with the forces BEFORE the
+// ghosts are folded home and positions in the structure's own frame: with F_i += g_e, F_j -= g_e per edge this is -sum_e r_e (x) g_e, whatever kernel wrote the forces.
+// out[8 s ..]: energy, xx, yy, zz, xy, xz, yz, ghosts.
+#ifdef AHIP_HOST_EMU
+constexpr int CELLS_REDUCE_THREADS = 1;      // the emulation launches threads one after the other: a single thread does the whole structure
+#else
+constexpr int CELLS_REDUCE_THREADS = 256;
+#endif
+__device__ inline void cells_row_virial(const double *x, const double *f, double *w) {
+  w[0] += x[0] * f[0]; w[1] += x[1] * f[1]; w[2] += x[2] * f[2];
+  w[3] += 0.5 * (x[0] * f[1] + x[1] * f[0]); w[4] += 0.5 * (x[0] * f[2] + x[2] * f[0]); w[5] += 0.5 * (x[1] * f[2] + x[2] * f[1]);
+}
+__global__ void __launch_bounds__(CELLS_REDUCE_THREADS) k_cells_reduce(int nstruct, int natoms, const CellEntry *tab, const int *off, const double *x,
+                                                                          const double *f, const double *eatom, double *out) {
+  const int s = blockIdx.x, t = threadIdx.x;
+  if (s >= nstruct) return;                                // (whole workgroups: the barriers below stay uniform)
+  const int a0 = tab[s].first, a1 = tab[s + 1].first;
+  const long long g0 = (long long)natoms + off[a0], g1 = (long long)natoms + off[a1];
+  double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (long long r = a0 + t; r < a1; r += CELLS_REDUCE_THREADS) { acc[0] += eatom[r]; cells_row_virial(x + 3 * r, f + 3 * r, acc + 1); }
+  for (long long r = g0 + t; r < g1; r += CELLS_REDUCE_THREADS) cells_row_virial(x + 3 * r, f + 3 * r, acc + 1);
+#ifndef AHIP_HOST_EMU
+  __shared__ double sh[7][CELLS_REDUCE_THREADS];
+  for (int k = 0; k < 7; ++k) sh[k][t] = acc[k];
+  __syncthreads();
+  for (int w = CELLS_REDUCE_THREADS / 2; w > 0; w >>= 1) {
+    if (t < w) for (int k = 0; k < 7; ++k) sh[k][t] += sh[k][t + w];
+    __syncthreads();
+  }
+  for (int k = 0; k < 7; ++k) acc[k] = sh[k][0];
+#endif
+  if (t == 0) {
+    for (int k = 0; k < 7; ++k) out[8 * (long long)s + k] = acc[k];
+    out[8 * (long long)s + 7] = (double)(off[a1] - off[a0]);
+  }
+}
+
+// bins of the grid neigh_build derives from a bounding box (its rule, restated)
+static long long neigh_grid_bins(const double *lo, const double *hi, double rc_list) {
+  long long nbins = 1;
+  for (int d = 0; d < 3; ++d) nbins *= std::min(1024, std::max(1, (int)std::floor((hi[d] - lo[d]) / rc_list)));
+  return nbins;
+}
+
+size_t cells_plan(int nstruct, const int *first, const double *x, const double *cells, const int *pbc, double rc, std::vector<unsigned char> &table, double *lo,
+                  double *hi) {
+  std::vector<CellEntry> tab((size_t)nstruct + 1);
+  std::vector<double> blo((size_t)nstruct * 3), ext((size_t)nstruct * 3);
+  const int natoms = nstruct > 0 ? first[nstruct] : 0;
+  double rows = (double)natoms, slot[3] = {0.0, 0.0, 0.0};
+  for (int s = 0; s < nstruct; ++s) {
+    const std::string who = "ahip_compute_cells: structure " + std::to_string(s);
+    CellEntry &e = tab[(size_t)s];
+    e.g = cell_geometry(who.c_str(), cells + 9 * (size_t)s, pbc + 3 * (size_t)s, rc);
+    e.first = first[s]; e.pad = 0;
+    const int n = first[s + 1] - first[s];
+    rows += cell_most_images(e.g, n);
+    if (!(rows <= 2147483647.0))
+      throw ArgError(who + ": atoms and images of the batch exceed 2^31 - 1 rows up to here (the offsets are 32-bit); split the batch, or the cell is too thin for this cutoff");
+    // the fractional range of its rows: [-m_d, 1 + m_d] on a periodic axis, what its atoms have on an open one (a molecule may lie outside its cell)
+    // (open axes: measured on the WRAPPED position, through the kernel's own row body -- far outside the cell along a periodic axis the open-axis
+    // component of the caller's position carries a rounding error that the wrapped row no longer has)
+    double a[3], b[3];
+    const bool open = !e.g.pbc[0] || !e.g.pbc[1] || !e.g.pbc[2];
+    for (int d = 0; d < 3; ++d) {
+      if (e.g.pbc[d]) { a[d] = -e.g.m[d]; b[d] = 1.0 + e.g.m[d]; }
+      else { a[d] = n > 0 ? HUGE_VAL : 0.0; b[d] = n > 0 ? -HUGE_VAL : 0.0; }
+    }
+    for (int i = first[s]; open && i < first[s + 1]; ++i) {
+      double xi[3] = {x[3 * (size_t)i], x[3 * (size_t)i + 1], x[3 * (size_t)i + 2]};
+      cell_wrap_row(e.g, xi);
+      for (int d = 0; d < 3; ++d) {
+        if (e.g.pbc[d]) continue;
+        const double v = cell_frac(e.g, xi, d);
+        a[d] = std::min(a[d], v); b[d] = std::max(b[d], v);
+      }
+    }
+    for (int d = 0; d < 3; ++d) if (!e.g.pbc[d]) { a[d] -= 1e-9; b[d] += 1e-9; }
+    // ... and the Cartesian bounding box of that parallelepiped
+    for (int k = 0; k < 3; ++k) {
+      double l = 0.0, h = 0.0;
+      for (int d = 0; d < 3; ++d) {
+        const double p = a[d] * e.g.h[3 * d + k], q = b[d] * e.g.h[3 * d + k];
+        l += std::min(p, q); h += std::max(p, q);
+      }
+      if (!std::isfinite(l) || !std::isfinite(h)) throw ArgError(who + ": a position is not finite");
+      blo[3 * (size_t)s + k] = l; ext[3 * (size_t)s + k] = h - l;
+      slot[k] = std::max(slot[k], h - l);
+    }
+  }
+  // uniform slots of the largest extent plus the gap, on a near-cubic grid (the most slots along the thinnest slot dimension)
+  int order[3] = {0, 1, 2}, cnt[3] = {1, 1, 1};
+  for (int k = 0; k < 3; ++k) slot[k] += rc + 1e-6;
+  std::sort(order, order + 3, [&](int p, int q) { return slot[p] < slot[q]; });
+  if (nstruct > 0) {
+    int n0 = (int)std::ceil(std::cbrt((double)nstruct));
+    while ((long long)n0 * n0 * n0 < nstruct) ++n0;
+    while (n0 > 1 && (long long)(n0 - 1) * (n0 - 1) * (n0 - 1) >= nstruct) --n0;
+    int n1 = (int)std::ceil(std::sqrt((double)nstruct / n0));
+    while ((long long)n0 * n1 * n1 < nstruct) ++n1;
+    const int n2 = (int)(((long long)nstruct + (long long)n0 * n1 - 1) / ((long long)n0 * n1));
+    cnt[order[0]] = n0; cnt[order[1]] = n1; cnt[order[2]] = n2;
+  }
+  for (int s = 0; s < nstruct; ++s) {
+    const int i0 = s % cnt[order[0]], i1 = (s / cnt[order[0]]) % cnt[order[1]], i2 = s / (cnt[order[0]] * cnt[order[1]]);
+    int idx[3];
+    idx[order[0]] = i0; idx[order[1]] = i1; idx[order[2]] = i2;
+    for (int k = 0; k < 3; ++k) tab[(size_t)s].origin[k] = idx[k] * slot[k] - blo[3 * (size_t)s + k];
+  }
+  CellEntry &end = tab[(size_t)nstruct];
+  std::memset(&end, 0, sizeof(CellEntry));
+  end.first = natoms;
+  for (int k = 0; k < 3; ++k) { lo[k] = 0.0; hi[k] = cnt[k] * slot[k]; }
+  if (neigh_grid_bins(lo, hi, rc) > (1LL << 26))
+    throw ArgError("ahip_compute_cells: the structures' common slot (" + std::to_string(slot[0]) + " x " + std::to_string(slot[1]) + " x " + std::to_string(slot[2]) +
+                   ", the largest extent of any) times " + std::to_string(nstruct) + " structures needs more than 2^26 neighbor bins: split the batch");
+  table.resize(tab.size() * sizeof(CellEntry));
+  std::memcpy(table.data(), tab.data(), table.size());
+  return sizeof(CellEntry);
+}
+void cells_wrap(int natoms, const double *xin, const int *mtin, const int *sidx, const void *table, double *x, int *mt, hipStream_t s) {
+  if (natoms <= 0) return;
+  hipLaunchKernelGGL(k_cells_wrap, dim3((unsigned)((natoms + 255) / 256)), dim3(256), 0, s, natoms, xin, mtin, sidx, (const CellEntry *)table, x, mt);
+  AHIP_CHECK(hipGetLastError());
+}
+int cells_count(Model &m, int natoms, const double *x, const int *sidx, const void *table, hipStream_t s) {
+  if (natoms <= 0) return 0;
+  if (!m.nb_state) m.nb_state = new NbState();
+  NbState &st = *(NbState *)m.nb_state;
+  st.cnt.reserve(((size_t)natoms + 1) * sizeof(int));
+  st.goff.reserve(((size_t)natoms + 2) * sizeof(int));
+  hipLaunchKernelGGL(k_cells_count, dim3((unsigned)((natoms + 255) / 256)), dim3(256), 0, s, natoms, x, sidx, (const CellEntry *)table, st.cnt.as<int>());
+  AHIP_CHECK(prim_exclusive_scan_i32(m.prim, st.cnt.as<int>(), st.goff.as<int>(), natoms, s));
+  int tot = 0;
+  AHIP_CHECK(hipMemcpyAsync(&tot, st.goff.as<int>() + natoms, sizeof(int), hipMemcpyDeviceToHost, s));
+  AHIP_CHECK(hipStreamSynchronize(s));
+  AHIP_CHECK(hipGetLastError());
+  if (tot < 0) throw ArgError("ahip_compute_cells: more than 2^31 - 1 images");
+  return tot;
+}
+void cells_fill(Model &m, int natoms, int nghost, const double *x, const int *mtype, const int *sidx, const void *table, double *xg, int *mtg, long long *src,
+                double *shift, hipStream_t s) {
+  if (natoms <= 0 || nghost <= 0) return;
+  NbState &st = *(NbState *)m.nb_state;
+  hipLaunchKernelGGL(k_cells_fill, dim3((unsigned)(((long long)nghost + 255) / 256)), dim3(256), 0, s, natoms, x, mtype, sidx, (const CellEntry *)table,
+                     st.goff.as<int>(), nghost, xg, mtg, src, shift);
+  AHIP_CHECK(hipGetLastError());
+}
+void cells_place(int natoms, int nall, const double *x, const int *sidx, const long long *src, const void *table, double *xp, hipStream_t s) {
+  if (nall <= 0) return;
+  hipLaunchKernelGGL(k_cells_place, dim3((unsigned)(((long long)nall + 255) / 256)), dim3(256), 0, s, natoms, nall, x, sidx, src, (const CellEntry *)table, xp);
+  AHIP_CHECK(hipGetLastError());
+}
+void cells_reduce(Model &m, int nstruct, int natoms, const void *table, const double *x, const double *f, const double *eatom, double *out, hipStream_t s) {
+  if (nstruct <= 0 || natoms <= 0) return;
+  NbState &st = *(NbState *)m.nb_state;
+  hipLaunchKernelGGL(k_cells_reduce, dim3((unsigned)nstruct), dim3(CELLS_REDUCE_THREADS), 0, s, nstruct, natoms, (const CellEntry *)table, st.goff.as<int>(), x, f, eatom, out);
+  AHIP_CHECK(hipGetLastError());
+}
+
 void neigh_free(Model &m) {
   if (!m.nb_state) return;
   NbState *st = (NbState *)m.nb_state;
-  for (DevBuf *b : {&st->bin_of, &st->bin_cnt, &st->bin_start, &st->bin_fill, &st->sorted, &st->cnt, &st->off, &st->nlj, &st->ilist, &st->box, &st->mapper, &st->inv_mass})
+  for (DevBuf *b : {&st->bin_of, &st->bin_cnt, &st->bin_start, &st->bin_fill, &st->sorted, &st->cnt, &st->off, &st->nlj, &st->ilist, &st->box, &st->mapper, &st->inv_mass, &st->goff})
     b->release();
   delete st;
   m.nb_state = nullptr;
