@@ -48,6 +48,9 @@ def main():
     path = os.path.join(model_dir, f"md_small_r{rank}.ahip")
     model_file.save_ahip(path, cfg, w)
     cell, pos, _ = lmp_like.diamond_si(3)
+    if world == 3 and cell[0, 0] / grid[0] < cfg["r_max"] + skin:
+        # 3x1x1 bricks of the 16.3 A box are 5.43 A wide, thinner than r_max + skin for a skin above 0.43 A: 4 cells (21.7 A, 7.24 A bricks) for this world only
+        cell, pos, _ = lmp_like.diamond_si(4)
     if len(sys.argv) > 7 and sys.argv[7] == "cluster":
         # a 64-atom cluster in a 40 A box, all of it inside the first brick of a 2x1x1 grid and within reach of the second: rank 0 owns every
         # atom, receives no ghost and still has a slab to send; rank 1 owns nothing and receives ghosts (the peer's receive must be met)

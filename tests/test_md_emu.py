@@ -58,11 +58,14 @@ def _run_workers(emu_lib, model_dir, tmp_path, world, port, extra=(), env_extra=
     return np.load(out)
 
 
-@pytest.mark.parametrize("world,port", [(2, 29731), (4, 29733), (8, 29735)])
+@pytest.mark.parametrize("world,port", [(2, 29731), (4, 29733), (8, 29735), (3, 29761)])
 def test_gloo_ranks_match_single_rank(emu_lib, model_dir, tmp_path, world, port):
     """2 / 4 / 8 processes (gloo) on 2x1x1 / 2x2x1 / 2x2x2 bricks -- the grids bench.py uses on 2 / 4 / 8 GPUs:
     forces after setup, positions and energy after 3 steps equal the single-rank run (borders, forward and
-    reverse communication across ranks and across periodic self-images)."""
+    reverse communication across ranks and across periodic self-images).  World 3 is 3x1x1: the lower and the upper
+    neighbour along x are different ranks (separate messages per swap; tests/test_comm_ranks.py holds that route at
+    kernel level).  A third of the worker's 16.3 A box is thinner than r_max + skin = 6 A, so the worker takes a
+    4-cell box (21.7 A) for that world only; the tolerances are those of the other worlds."""
     z = _run_workers(emu_lib, model_dir, tmp_path, world, port)
     np.testing.assert_allclose(z["f2"], z["f1"], atol=1e-10)
     np.testing.assert_allclose(z["x2"], z["x1"], atol=1e-12)
@@ -78,13 +81,14 @@ def test_gloo_rebuild_and_migration(emu_lib, model_dir, tmp_path):
     np.testing.assert_allclose(z["e2"], z["e1"], rtol=1e-9)
 
 
-@pytest.mark.parametrize("world,port", [(2, 29751), (4, 29753), (8, 29755)])
+@pytest.mark.parametrize("world,port", [(2, 29751), (4, 29753), (8, 29755), (3, 29763)])
 def test_gloo_library_borders_equal_the_swap_chain(emu_lib, model_dir, tmp_path, world, port):
     """at several ranks a re-neighboring is library kernels + the communicator's transport (ahip_comm_migrate, ahip_comm_borders: csrc/comm.hip),
     not six rounds of torch mask / nonzero / cat.  Hot system, small skin, 12 steps on 2 / 4 / 8 bricks (migrations included): after the last re-neighboring
     every rank holds the same owned atoms in the same order and the same ghost rows -- bit for bit, order included -- as the torch swap chain
     (AHIP_LIB_BORDERS=0, what LAMMPS' Comm::exchange / Comm::borders do for the reference, /root/reference/pair_nequip_allegro.cpp:366-368), and the
-    trajectory equals the single-rank run."""
+    trajectory equals the single-rank run.  World 3 is 3x1x1 (the lower and the upper neighbour are different ranks); with the skin of 0.3 A its 5.43 A
+    bricks hold r_max + skin, so the box is the one of the other worlds."""
     z = _run_workers(emu_lib, model_dir, tmp_path, world, port, extra=(4000.0, 12, 0.3), env_extra={"AHIP_TEST_COMPARE_BORDERS": "1"})
     assert int(z["nreb"]) >= 2
     np.testing.assert_allclose(z["x2"], z["x1"], atol=1e-8)
