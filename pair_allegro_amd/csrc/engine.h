@@ -19,19 +19,7 @@
 
 namespace ahip {
 
-struct HipError : std::runtime_error {
-  explicit HipError(const std::string &m) : std::runtime_error(m) {}
-};
-struct ArgError : std::runtime_error {
-  explicit ArgError(const std::string &m) : std::runtime_error(m) {}
-};
-struct StateError : std::runtime_error {
-  explicit StateError(const std::string &m) : std::runtime_error(m) {}
-};
-struct UnsupportedError : std::runtime_error {
-  explicit UnsupportedError(const std::string &m) : std::runtime_error(m) {}
-};
-
+// (HipError, ArgError, StateError, UnsupportedError: fused_shapes.h)
 #define AHIP_CHECK(expr)                                                                       \
   do {                                                                                         \
     hipError_t _e = (expr);                                                                    \

@@ -49,8 +49,8 @@
 #include "fused_rows.h"
 #include "prims.h"
 
-// This file is compiled in six parts (Makefile; same options, divides the build time): AHIP_FUSED_PART 0 = the host side + the f32-input MFMA
-// instances of k_fused, AHIP_FUSED_PART 1 = the bf16-split instances, 2 = the f16x2 instances, 3 = their read-out-depth-2 twins, 4 = their MLP-width-128 twins, 5 = their read-out-width-64 twins.  (Rounds 2-3 gave part 1 other compiler options because it computed wrong
+// This file is compiled in parts (Makefile; same options, divides the build time): AHIP_FUSED_PART 0 = the host side + the instances of part 0, n = the instances of
+// part n alone; which instances a part holds is fused_shapes.h: FUSED_INSTANCES.  (Rounds 2-3 gave part 1 other compiler options because it computed wrong
 // forces with part 0's: that was the store-data hazard described at fused_common.h: bstore, not the options.)
 #ifndef AHIP_FUSED_PART
 #define AHIP_FUSED_PART 0
@@ -1284,38 +1284,42 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
 }
 
 
-// ---------------------------------------------------------------------------- the bf16-split instances (fused_bf.o)
+// ---------------------------------------------------------------------------- the instances, one launch function per part
+// (the static_asserts: what a dispatch list names is in fused_shapes.h: FUSED_INSTANCES -- {family, arithmetic, two-body table, MD, RD, WF, RF, option, NW, NL, variant} -- and in this part)
 void fused_launch_bf16(int nw, bool prof, int arith, bool tbt, int grid, hipStream_t s, const FusedArgs &A);
 void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const FusedArgs &A);
 void fused_launch_f16_rd2(int nw, int md, int grid, hipStream_t s, const FusedArgs &A);
 void fused_launch_f16_w128(int nw, int md, int grid, hipStream_t s, const FusedArgs &A);
 void fused_launch_f16_r64(int nw, int md, int grid, hipStream_t s, const FusedArgs &A);
 #if AHIP_FUSED_PART == 5
-// the read-out-width-64 f16x2 instances (fused_hq.o; template parameter RT = 4): two-body table only, MLP width 64, latent MLP depth 1..3, read-out depth 1, plain and per-atom virial, not profiled
+// fused_hq.o: template parameter RT = 4
 void fused_launch_f16_r64(int nw, int md, int grid, hipStream_t s, const FusedArgs &A) {
   dispatch<Choices<4, 8>, Choices<1, 2, 3>, Choices<1, 3, 2>, Choices<VAR_VA, VAR_PLAIN>>([&](auto nw, auto nl, auto md, auto var) {
+    static_assert(fused_part_holds(AHIP_FUSED_PART, {FusedFamily::k_fused, 3, true, md, 1, 64, 64, false, nw, nl, var}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused<nw, false, 3, true, nl, md, var == VAR_VA, 1, 4, 4>), dim3(grid), dim3(nw * 64), 0, s, A);
   }, nw, A.NL, md, fused_variant(A.vatom, false));
 }
 #endif
 #if AHIP_FUSED_PART == 4
-// the MLP-width-128 f16x2 instances (fused_hm.o; template parameter WT = 8): two-body table only, latent MLP depth 1..3, read-out depth 1, plain and per-atom virial, not profiled
+// fused_hm.o: template parameter WT = 8
 void fused_launch_f16_w128(int nw, int md, int grid, hipStream_t s, const FusedArgs &A) {
   dispatch<Choices<4, 8>, Choices<1, 2, 3>, Choices<1, 3, 2>, Choices<VAR_VA, VAR_PLAIN>>([&](auto nw, auto nl, auto md, auto var) {
+    static_assert(fused_part_holds(AHIP_FUSED_PART, {FusedFamily::k_fused, 3, true, md, 1, 128, 32, false, nw, nl, var}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused<nw, false, 3, true, nl, md, var == VAR_VA, 1, 8>), dim3(grid), dim3(nw * 64), 0, s, A);
   }, nw, A.NL, md, fused_variant(A.vatom, false));
 }
 #endif
 #if AHIP_FUSED_PART == 3
-// the read-out-depth-2 f16x2 instances (fused_hr.o): two-body table only, latent MLP depth 1..3, plain and per-atom virial, not profiled
+// fused_hr.o: template parameter RD = 2
 void fused_launch_f16_rd2(int nw, int md, int grid, hipStream_t s, const FusedArgs &A) {
   dispatch<Choices<4, 8>, Choices<1, 2, 3>, Choices<1, 3, 2>, Choices<VAR_VA, VAR_PLAIN>>([&](auto nw, auto nl, auto md, auto var) {
+    static_assert(fused_part_holds(AHIP_FUSED_PART, {FusedFamily::k_fused, 3, true, md, 2, 64, 32, false, nw, nl, var}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused<nw, false, 3, true, nl, md, var == VAR_VA, 2>), dim3(grid), dim3(nw * 64), 0, s, A);
   }, nw, A.NL, md, fused_variant(A.vatom, false));
 }
 #endif
 #if AHIP_FUSED_PART == 2
-// the f16x2 instances (fused_h.o): two-body table only; latent MLP depth 1..3 (profiling build for depth 2 only)
+// fused_h.o
 void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const FusedArgs &A) {
 #ifdef AHIP_ASM_ONLY      // tools/asm_k_fused.sh: the headline instance alone, for a quick look at its code (static census, spills)
 #ifndef AHIP_ASM_NW
@@ -1339,14 +1343,18 @@ void fused_launch_f16(int nw, bool prof, int md, int grid, hipStream_t s, const 
   hipLaunchKernelGGL((k_fused<AHIP_ASM_NW, false, 3, true, AHIP_ASM_NL, AHIP_ASM_MD, AHIP_ASM_VA, 1, AHIP_ASM_WT, AHIP_ASM_RT>), dim3(grid), dim3(AHIP_ASM_NW * 64), 0, s, A);
 #else
   dispatch<Choices<4, 8>, Choices<1, 2, 3>, Choices<1, 3, 2>, Variants>([&](auto nw, auto nl, auto md, auto var) {
-    if constexpr (var != VAR_PROF || md == 2) hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, 3, true, nl, md, var == VAR_VA>), dim3(grid), dim3(nw * 64), 0, s, A);
-  }, nw, A.NL, md, fused_variant(A.vatom, prof && md == 2));
+    if constexpr (fused_part_holds(AHIP_FUSED_PART, {FusedFamily::k_fused, 3, true, md, 1, 64, 32, false, nw, nl, var}))      // (profiled: one MLP depth only)
+      hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, 3, true, nl, md, var == VAR_VA>), dim3(grid), dim3(nw * 64), 0, s, A);
+    else throw StateError("k_fused: not an instance of part 2");
+  }, nw, A.NL, md, fused_variant(A.vatom, prof && md == FUSED_PROF_MD));
 #endif
 }
 #endif
 #if AHIP_FUSED_PART == 1
+// fused_bf.o
 void fused_launch_bf16(int nw, bool prof, int arith, bool tbt, int grid, hipStream_t s, const FusedArgs &A) {
   dispatch<Choices<4, 8>, Choices<1, 2>, Choices<1, 0>, Choices<1, 2, 3>, Variants>([&](auto nw, auto b3, auto tb, auto nl, auto var) {
+    static_assert(fused_part_holds(AHIP_FUSED_PART, {FusedFamily::k_fused, b3, tb != 0, 2, 1, 64, 32, false, nw, nl, var}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, b3, tb != 0, nl, 2, var == VAR_VA>), dim3(grid), dim3(nw * 64), 0, s, A);
   }, nw, arith, tbt, A.NL, fused_variant(A.vatom, prof));
 }
@@ -1361,10 +1369,8 @@ struct FusedState {
   bool ready = false, prof_on = false, dbg_on = false, clk_on = false;
   bool tbt = true;             // two-body embedding from the spline table (default) or evaluated as an MLP (option fused_tb=mlp)
   int md = 2;                  // hidden layers of the latent MLP (template parameter MD of k_fused)
-  int rd = 1;                  // hidden layers of the read-out MLP (template parameter RD)
-  int rt = 2;                  // 16-feature tiles of the read-out MLP's hidden layer (template parameter RT: 2 = read-out width 32, 4 = 64)
-  int wt = 4;                  // 16-feature tiles of a hidden layer of the latent MLP (template parameter WT: 4 = MLP width 64, 8 = 128)
   Arith arith = AR_F32;        // arith_policy.h: resolve_arith (every arithmetic has its k_fused instances)
+  int part = 0;                // fused_shapes.h: FUSED_INSTANCES
   DevBuf prof, dbg;
   int ncu = 256;
   int force_nw = 0;            // AHIP_FUSED_NW=4|8 pins the workgroup shape (A/B measurements)
@@ -1419,7 +1425,6 @@ static void fused_prepare(Model &m) {
   std::memset(&A, 0, sizeof(A));
   // two-body: pair table (type-type rows of the first layer)
   const int W = h.mlp_width;                      // hidden width of the MLPs at the kernel's shape: 64 or 128 (fused_shapes.h: FUSED_WF, FUSED_WF2)
-  if (W != FUSED_WF && W != FUSED_WF2) throw UnsupportedError("fused kernels: MLP width " + std::to_string(W) + " is not a width of the kernel");      // (fused_host_model pads to one)
   const HostTensor &w0 = h.get("tb.w0");          // [2T+8][W]
   A.o_pair = w_mark(w);
   for (int ti = 0; ti < T; ++ti)
@@ -1431,12 +1436,10 @@ static void fused_prepare(Model &m) {
   st.tbt = fused_tb_is_table(m);
   st.arith = resolve_arith(m, false);
   st.md = h.mlp_depth;
-  st.rd = h.readout_depth;
-  st.wt = W / 16;
   const int RF = h.readout_width;                 // read-out width at the kernel's shape: 32 or 64 (fused_shapes.h: FUSED_RF, FUSED_RF2)
-  if (RF != FUSED_RF && RF != FUSED_RF2) throw UnsupportedError("fused kernels: read-out width " + std::to_string(RF) + " is not a width of the kernel");      // (fused_host_model pads to one)
-  st.rt = RF / 16;
-  const int MD = st.md, RD = st.rd;
+  const int MD = st.md, RD = h.readout_depth;
+  // the part of this file that holds the model's instances (fused_model_supported keeps a model without one away, fused_host_model pads to a width of the kernels)
+  st.part = fused_require_instance({FusedFamily::k_fused, st.arith, st.tbt, MD, RD, W, RF}).part;
   const bool b3 = st.arith == AR_BF16X3 || st.arith == AR_TF32EQ, h2 = st.arith == AR_F16X2, tbt = st.tbt;
   const int nterm = st.arith == AR_BF16X3 ? 3 : 2;
   int h_flags = 0;        // float16 range findings over the weight stream (engine.h: H_RANGE_*)
@@ -1458,11 +1461,6 @@ static void fused_prepare(Model &m) {
       for (int q = 0; q < 64; ++q)
         for (int n = 0; n < RF; ++n) w3r[(size_t)i * RF + n] += W3[(size_t)i * 64 + q] * Wr[(size_t)q * RF + n];
   }
-  if (!tbt && MD != 2) throw UnsupportedError("fused_tb=mlp needs MLP depth 2");
-  if (RD != 1 && !h2) throw UnsupportedError("fused kernels: read-out depth 2 has f16x2 instances only");      // (fused_model_supported keeps such a model away)
-  if (W != FUSED_WF && !(h2 && tbt && RD == 1)) throw UnsupportedError("fused kernels: MLP width 65..128 has f16x2 instances with the two-body table and read-out depth 1 only");      // (likewise)
-  if (RF != FUSED_RF && !(h2 && tbt && RD == 1 && W == FUSED_WF))
-    throw UnsupportedError("fused kernels: read-out width 33..64 has f16x2 instances with the two-body table, MLP width <= 64 and read-out depth 1 only");      // (likewise)
   if (!tbt) {
     fwd(wc, 8, 64);
     fwd(T_("tb.w1"), 64, 64);
@@ -1516,7 +1514,7 @@ static void fused_prepare(Model &m) {
   // two-body table (see k_fused), small tables, upload, scalar arguments, float16 range verdict: fused_common.h
   st.ncu = fused_prepare_tail(m, h, w, A, st.wbuf, tbt, 5, 32, nullptr, st.arith, h_flags);
   // Persistent workgroups, 8 waves per CU either way (two per SIMD, 256 registers each).
-  A.wave_scratch = (long long)R_TOTAL(NL, MD, st.wt) * ROW;       // (the read-out width does not enter: the RT = 4 instances are f16x2, which save no z (W3 Wr) rows -- and those would fit the layer's four u rows)
+  A.wave_scratch = (long long)R_TOTAL(NL, MD, W / 16) * ROW;       // (the read-out width does not enter: the RT = 4 instances are f16x2, which save no z (W3 Wr) rows -- and those would fit the layer's four u rows)
   st.scratch.reserve((size_t)st.ncu * 8 * A.wave_scratch * sizeof(float));
   A.scratch = st.scratch.as<float>();
   st.tiles.partial.reserve((size_t)st.ncu * 2 * 7 * sizeof(double));
@@ -1584,14 +1582,20 @@ bool fused_run(Model &m, const ComputeArgs &a, std::string *why) {
       // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
       A.tchunk = (nedges_est / (16 * shape) > (long long)g * 256) ? TCHUNK : 1;
       if (const char *tc = std::getenv("AHIP_TCHUNK")) A.tchunk = std::max(1, std::atoi(tc));       // experiments
-      if (st.arith == AR_F16X2 && st.rt == 4) { fused_launch_f16_r64(shape, st.md, g, s, A); continue; }                    // fused_hq.o (MLP width 64, read-out depth 1: fused_prepare)
-      if (st.arith == AR_F16X2 && st.wt == 8) { fused_launch_f16_w128(shape, st.md, g, s, A); continue; }                   // fused_hm.o (read-out depth 1: fused_prepare)
-      if (st.arith == AR_F16X2 && st.rd == 2) { fused_launch_f16_rd2(shape, st.md, g, s, A); continue; }                     // fused_hr.o
-      if (st.arith == AR_F16X2) { fused_launch_f16(shape, st.prof_on, st.md, g, s, A); continue; }                        // fused_h.o
-      if (st.arith != AR_F32) { fused_launch_bf16(shape, st.prof_on, st.arith, st.tbt, g, s, A); continue; }     // fused_bf.o
-      dispatch<Choices<4, 8>, Choices<1, 0>, Choices<1, 2, 3>, Variants>([&](auto nw, auto tb, auto nl, auto var) {
-        hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, 0, tb != 0, nl, 2, var == VAR_VA>), dim3(g), dim3(nw * 64), 0, s, A);
-      }, shape, st.tbt, A.NL, fused_variant(A.vatom, st.prof_on));
+      switch (st.part) {
+        case 5: fused_launch_f16_r64(shape, st.md, g, s, A); break;
+        case 4: fused_launch_f16_w128(shape, st.md, g, s, A); break;
+        case 3: fused_launch_f16_rd2(shape, st.md, g, s, A); break;
+        case 2: fused_launch_f16(shape, st.prof_on, st.md, g, s, A); break;
+        case 1: fused_launch_bf16(shape, st.prof_on, st.arith, st.tbt, g, s, A); break;
+        case 0:
+          dispatch<Choices<4, 8>, Choices<1, 0>, Choices<1, 2, 3>, Variants>([&](auto nw, auto tb, auto nl, auto var) {
+            static_assert(fused_part_holds(AHIP_FUSED_PART, {FusedFamily::k_fused, AR_F32, tb != 0, 2, 1, 64, 32, false, nw, nl, var}), "not in FUSED_INSTANCES");
+            hipLaunchKernelGGL((k_fused<nw, var == VAR_PROF, 0, tb != 0, nl, 2, var == VAR_VA>), dim3(g), dim3(nw * 64), 0, s, A);
+          }, shape, st.tbt, A.NL, fused_variant(A.vatom, st.prof_on));
+          break;
+        default: throw StateError("k_fused: no launch function for part " + std::to_string(st.part));
+      }
     }
   }
   AHIP_CHECK(hipGetLastError());

@@ -551,30 +551,7 @@ static void fused_tile_args(Model &m, TileBufs &tb, const ComputeArgs &a, Args &
   A.f = a.f; A.eatom = a.eatom; A.partial = tb.partial.as<double>(); A.vatom = a.vatom;
 }
 
-// ---- instance dispatch (host side) ----
-// dispatch<Choices<4, 8>, Choices<1, 2, 3>>(f, nw, nl) calls f(std::integral_constant<int, NW>{}, std::integral_constant<int, NL>{}): every run-time value
-// becomes the template argument equal to it (the LAST choice when none is), so a kernel instance exists exactly for what the choice lists name.
-template <int... Vs> struct Choices {};
-template <class... Sets> struct Dispatch;
-template <> struct Dispatch<> {
-  template <class F, class... C> static void run(F &f, const int *, C... c) { f(c...); }
-};
-template <int V, int... Vs, class... Rest> struct Dispatch<Choices<V, Vs...>, Rest...> {
-  template <class F, class... C> static void run(F &f, const int *v, C... c) {
-    if constexpr (sizeof...(Vs) == 0) Dispatch<Rest...>::run(f, v + 1, c..., std::integral_constant<int, V>{});
-    else if (*v == V) Dispatch<Rest...>::run(f, v + 1, c..., std::integral_constant<int, V>{});
-    else Dispatch<Choices<Vs...>, Rest...>::run(f, v, c...);
-  }
-};
-template <class... Sets, class F, class... I> static void dispatch(F &&f, I... v) {
-  static_assert(sizeof...(Sets) == sizeof...(I), "one run-time value per choice list");
-  const int vals[] = {(int)v...};
-  Dispatch<Sets...>::run(f, vals);
-}
-// instrumentation variant of a fused kernel instance: plain, phase-profiled, or with the per-atom virial (output "atomic_virial"; no profiled twin)
-enum { VAR_PLAIN = 0, VAR_PROF = 1, VAR_VA = 2 };
-using Variants = Choices<VAR_VA, VAR_PROF, VAR_PLAIN>;
-static inline int fused_variant(bool vatom, bool prof) { return vatom ? VAR_VA : prof ? VAR_PROF : VAR_PLAIN; }
+// (instance dispatch -- dispatch<Choices<...>>, Variants, fused_variant -- and the instance table: fused_shapes.h)
 
 // Fragment tiling of a [K][N] linear: KT input tiles x NT output tiles of 16 features; NT is padded to
 // even (tile pairs), and a single-input-tile linear is padded to KT = 2 so that it consumes 8 fragments.

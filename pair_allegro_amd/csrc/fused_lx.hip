@@ -840,31 +840,34 @@ __global__ void __launch_bounds__(NW * 64, 1) k_fused_lx(FusedLxArgs A) {
 }
 
 // ---------------------------------------------------------------------------- host side
-// This file is compiled five times (Makefile): AHIP_LX_PART 0 = the host side and the 4-wave read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone
-// (fused_lx_r.o), 2 = the 8-wave instances alone, with AHIP_NO_ACC_PARK (fused_lx_w.o), 3 = the MLP-width-128 instances alone (fused_lx_m.o), 4 = the read-out-width-64
-// instances alone (fused_lx_q.o)
+// This file is compiled in parts (Makefile): AHIP_LX_PART 0 = the host side and the instances of part 0, n = the instances of part n alone (2: with AHIP_NO_ACC_PARK);
+// which instances a part holds is fused_shapes.h: FUSED_INSTANCES
 #ifndef AHIP_LX_PART
 #define AHIP_LX_PART 0
 #endif
+// (the static_asserts: what a dispatch list names is in that table -- {family, arithmetic, -, MD, RD, WF, RF, option, NW, NL, variant} -- and in this part)
 void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
 void fusedlx_launch_w8(int nl, int ar, int var, int grid, hipStream_t s, const FusedLxArgs &A);
 void fusedlx_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
 void fusedlx_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
 #if AHIP_LX_PART == 4
-void fusedlx_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // RT = 4: f16x2 only, 4-wave tiles, MLP width 64, read-out depth 1, plain and per-atom virial, not profiled
+void fusedlx_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // fused_lx_q.o: RT = 4
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    static_assert(fused_part_holds(AHIP_LX_PART, {FusedFamily::lx32, 3, true, md, 1, 64, 64, false, 4, nl, v}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused_lx<4, nl, false, 3, v == VAR_VA, md, 1, 4, 4>), dim3(grid), dim3(4 * 64), 0, s, A);
   }, nl, var, md);
 }
 #elif AHIP_LX_PART == 3
-void fusedlx_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // HT = 8: f16x2 only, 4-wave tiles, read-out depth 1, plain and per-atom virial, not profiled
+void fusedlx_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // fused_lx_m.o: HT = 8
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    static_assert(fused_part_holds(AHIP_LX_PART, {FusedFamily::lx32, 3, true, md, 1, 128, 32, false, 4, nl, v}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused_lx<4, nl, false, 3, v == VAR_VA, md, 1, 8>), dim3(grid), dim3(4 * 64), 0, s, A);
   }, nl, var, md);
 }
 #elif AHIP_LX_PART == 1
-void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // f16x2 only, plain and per-atom virial, not profiled
+void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // fused_lx_r.o: RD = 2
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    static_assert(fused_part_holds(AHIP_LX_PART, {FusedFamily::lx32, 3, true, md, 2, 64, 32, false, 4, nl, v}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused_lx<4, nl, false, 3, v == VAR_VA, md, 2>), dim3(grid), dim3(4 * 64), 0, s, A);
   }, nl, var, md);
 }
@@ -872,8 +875,9 @@ void fusedlx_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const 
 #ifndef AHIP_NO_ACC_PARK
 #error "the 8-wave instances have 256 registers per wave: no AGPR park (build fused_lx_w.o with -DAHIP_NO_ACC_PARK)"
 #endif
-void fusedlx_launch_w8(int nl, int ar, int var, int grid, hipStream_t s, const FusedLxArgs &A) {      // f32 and f16x2, plain and per-atom virial, (MD, RD) = (2, 1), not profiled
+void fusedlx_launch_w8(int nl, int ar, int var, int grid, hipStream_t s, const FusedLxArgs &A) {      // fused_lx_w.o: NW = 8
   dispatch<Choices<1, 2, 3>, Choices<3, 0>, Choices<VAR_VA, VAR_PLAIN>>([&](auto nl, auto ar, auto v) {
+    static_assert(fused_part_holds(AHIP_LX_PART, {FusedFamily::lx32, ar, true, 2, 1, 64, 32, false, 8, nl, v}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused_lx<8, nl, false, ar, v == VAR_VA>), dim3(grid), dim3(8 * 64), 0, s, A);
   }, nl, ar, var);
 }
@@ -952,28 +956,29 @@ bool fusedlx_run(Model &m, const ComputeArgs &a, std::string *why) {
   FusedLxState &st = w128 ? lx_prepare<ShapeX<4, 8>>(m, m.fusedlx_state, nullptr, false, lx_stream, 4)
                           : lx_prepare<ShapeX<4>>(m, m.fusedlx_state, nullptr, false, lx_stream, max_slots > LX_TILE_SLOTS ? 8 : 4);
   static_assert(PX_N == LX_NPHASE, "profile phases");
-  if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
-  if (st.ht != 4 && !(st.ht == 8 && st.arith == AR_F16X2 && st.rd == 1 && max_slots == LX_TILE_SLOTS))
-    throw UnsupportedError("wide fused kernels: MLP width 65..128 has f16x2 instances on 64-slot tiles with read-out depth 1 only");      // (likewise; lx_max_tile_slots keeps wide_tile=auto at 64 slots)
-  if (st.rt != 2 && !(st.rt == 4 && st.arith == AR_F16X2 && st.rd == 1 && st.ht == 4 && max_slots == LX_TILE_SLOTS))
-    throw UnsupportedError("wide fused kernels: read-out width 33..64 has f16x2 instances on 64-slot tiles with MLP width <= 64 and read-out depth 1 only");      // (likewise)
+  const FusedInstanceKey key{FusedFamily::lx32, st.arith, true, st.md, st.rd, 16 * st.ht, 16 * st.rt};
   // Tile shape (4 waves / 64 slots or 8 waves / 128 slots, option wide_tile=auto) from the largest degree of THIS list, as k_fused does (fused.hip: fused_run): on the
   // host where it is known or bounded by the list's rows, else both shapes are launched and the device word decides (nw = 0)
   int nw = 4;
   if (max_slots > LX_TILE_SLOTS) {
-    if (!fused_has_wide_tile(FusedFamily::lx32, st.arith, st.md, st.rd)) throw StateError("wide_tile: the prepared instance has no 8-wave shape");      // (lx_max_tile_slots asked the same rule)
     if (!m.counts_pending) nw = m.last_max_deg <= LX_TILE_SLOTS ? 4 : 8;
     else nw = (m.max_list_row >= 0 && m.max_list_row <= LX_TILE_SLOTS) ? 4 : 0;
   }
-  lx_run<ShapeX<4>, ShapeX<8>>(m, a, st, "fused_lx", [&](const FusedLxArgs &A, int grid, int var, int shape) {
-    if (shape == 8) { fusedlx_launch_w8(A.NL, st.arith, var, grid, a.stream, A); return; }      // fused_lx_w.o
-    if (st.ht == 8) { fusedlx_launch_m(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_m.o
-    if (st.rt == 4) { fusedlx_launch_q(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_q.o
-    if (st.rd == 2) { fusedlx_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx_r.o
-    dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
-      if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)
-        hipLaunchKernelGGL((k_fused_lx<4, nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(4 * 64), 0, a.stream, A);
-    }, A.NL, st.arith, var, st.md);
+  lx_run<ShapeX<4>, ShapeX<8>>(m, a, st, "fused_lx", key, [&](const FusedLxArgs &A, int grid, int var, int part) {
+    switch (part) {
+      case 2: fusedlx_launch_w8(A.NL, st.arith, var, grid, a.stream, A); break;
+      case 3: fusedlx_launch_m(A.NL, var, st.md, grid, a.stream, A); break;
+      case 4: fusedlx_launch_q(A.NL, var, st.md, grid, a.stream, A); break;
+      case 1: fusedlx_launch_rd2(A.NL, var, st.md, grid, a.stream, A); break;
+      case 0:
+        dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
+          if constexpr (fused_part_holds(AHIP_LX_PART, {FusedFamily::lx32, ar, true, md, 1, 64, 32, false, 4, nl, v}))         // (the gate and lx_run never send anything else)
+            hipLaunchKernelGGL((k_fused_lx<4, nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(4 * 64), 0, a.stream, A);
+          else throw StateError("k_fused_lx: not an instance of part 0");
+        }, A.NL, st.arith, var, st.md);
+        break;
+      default: throw StateError("k_fused_lx: no launch function for part " + std::to_string(part));
+    }
   }, nw);
   return true;
 }

@@ -853,29 +853,33 @@ __global__ void __launch_bounds__(512, 1) k_fused_lx2(FusedLxArgs A) {
 }
 
 // ---------------------------------------------------------------------------- host side
-// This file is compiled four times (Makefile): AHIP_LX_PART 0 = the host side and the read-out-depth-1 instances, 1 = the read-out-depth-2 instances alone (fused_lx2_r.o),
-// 2 = the read-out-width-64 instances alone (fused_lx2_q.o), 3 = the MLP-width-128 instances alone (fused_lx2_m.o)
+// This file is compiled in parts (Makefile): AHIP_LX_PART 0 = the host side and the instances of part 0, n = the instances of part n alone; which instances a part holds
+// is fused_shapes.h: FUSED_INSTANCES
 #ifndef AHIP_LX_PART
 #define AHIP_LX_PART 0
 #endif
+// (the static_asserts: what a dispatch list names is in that table -- {family, arithmetic, -, MD, RD, WF, RF, option, tile, NL, variant} -- and in this part)
 void fusedlx2_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
 void fusedlx2_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
 void fusedlx2_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A);
 #if AHIP_LX_PART == 3
-void fusedlx2_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // WH = 4: f16x2 only, read-out depth 1, read-out width 32, plain and per-atom virial, not profiled
+void fusedlx2_launch_m(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // fused_lx2_m.o: WH = 4
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    static_assert(fused_part_holds(AHIP_LX_PART, {FusedFamily::lx64, 3, true, md, 1, 128, 32, true, 4, nl, v}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused_lx2<nl, false, 3, v == VAR_VA, md, 1, 2, 4>), dim3(grid), dim3(ShapeP::NW * 64), 0, s, A);
   }, nl, var, md);
 }
 #elif AHIP_LX_PART == 2
-void fusedlx2_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // RT = 4: f16x2 only, read-out depth 1, plain and per-atom virial, not profiled
+void fusedlx2_launch_q(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // fused_lx2_q.o: RT = 4
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    static_assert(fused_part_holds(AHIP_LX_PART, {FusedFamily::lx64, 3, true, md, 1, 64, 64, false, 4, nl, v}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused_lx2<nl, false, 3, v == VAR_VA, md, 1, 4>), dim3(grid), dim3(ShapeP::NW * 64), 0, s, A);
   }, nl, var, md);
 }
 #elif AHIP_LX_PART == 1
-void fusedlx2_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // f16x2 only, plain and per-atom virial, not profiled
+void fusedlx2_launch_rd2(int nl, int var, int md, int grid, hipStream_t s, const FusedLxArgs &A) {      // fused_lx2_r.o: RD = 2
   dispatch<Choices<1, 2, 3>, Choices<VAR_VA, VAR_PLAIN>, Choices<1, 3, 2>>([&](auto nl, auto v, auto md) {
+    static_assert(fused_part_holds(AHIP_LX_PART, {FusedFamily::lx64, 3, true, md, 2, 64, 32, false, 4, nl, v}), "not in FUSED_INSTANCES");
     hipLaunchKernelGGL((k_fused_lx2<nl, false, 3, v == VAR_VA, md, 2>), dim3(grid), dim3(ShapeP::NW * 64), 0, s, A);
   }, nl, var, md);
 }
@@ -967,19 +971,21 @@ bool fusedlx2_run(Model &m, const ComputeArgs &a, std::string *why) {
   FusedLxState &st = w128 ? lx_prepare<ShapePW<4>>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream)
                           : lx_prepare<ShapeP>(m, m.fusedlx2_state, ahip_cg_l2_cbase, true, lx2_stream);     // path weights x the path's base |c| (tp_g)
   static_assert(PP_N == LX_NPHASE, "profile phases");
-  if ((st.md != 2 || st.rd != 1) && st.arith != AR_F16X2) throw UnsupportedError("wide fused kernels: MLP depth 1 / 3 and read-out depth 2 have no float32 instance");      // (fusedlx_model_supported keeps such a model away)
-  if (st.rt != 2 && !(st.rt == 4 && st.arith == AR_F16X2 && st.rd == 1))
-    throw UnsupportedError("wide fused kernels: read-out width 33..64 has f16x2 instances with read-out depth 1 only");      // (likewise)
-  if (st.ht != 4 && !(st.ht == 8 && fused_lx64_w128(m) && st.arith == AR_F16X2 && st.rd == 1 && st.rt == 2))
-    throw UnsupportedError("wide fused kernels: MLP width 65..128 with 33..64 tensor features has f16x2 instances with read-out depth 1 and read-out width <= 32 only, behind option lx64_mlp_width=auto");      // (likewise)
-  lx_run<ShapeP>(m, a, st, "fused_lx2", [&](const FusedLxArgs &A, int grid, int var, int) {
-    if (st.ht == 8) { fusedlx2_launch_m(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_m.o
-    if (st.rt == 4) { fusedlx2_launch_q(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_q.o
-    if (st.rd == 2) { fusedlx2_launch_rd2(A.NL, var, st.md, grid, a.stream, A); return; }      // fused_lx2_r.o
-    dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
-      if constexpr ((v != VAR_PROF || (nl == 3 && md == 2)) && (md == 2 || ar == 3))         // profiled: 3 layers, depth 2 only; depth 1 / 3: f16x2 only (the gate never sends anything else)
-        hipLaunchKernelGGL((k_fused_lx2<nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(ShapeP::NW * 64), 0, a.stream, A);
-    }, A.NL, st.arith, var, st.md);
+  const FusedInstanceKey key{FusedFamily::lx64, st.arith, true, st.md, st.rd, 16 * st.ht, 16 * st.rt, fused_lx64_w128(m)};
+  lx_run<ShapeP>(m, a, st, "fused_lx2", key, [&](const FusedLxArgs &A, int grid, int var, int part) {
+    switch (part) {
+      case 3: fusedlx2_launch_m(A.NL, var, st.md, grid, a.stream, A); break;
+      case 2: fusedlx2_launch_q(A.NL, var, st.md, grid, a.stream, A); break;
+      case 1: fusedlx2_launch_rd2(A.NL, var, st.md, grid, a.stream, A); break;
+      case 0:
+        dispatch<Choices<1, 2, 3>, Choices<3, 0>, Variants, Choices<1, 3, 2>>([&](auto nl, auto ar, auto v, auto md) {
+          if constexpr (fused_part_holds(AHIP_LX_PART, {FusedFamily::lx64, ar, true, md, 1, 64, 32, false, 4, nl, v}))         // (the gate and lx_run never send anything else)
+            hipLaunchKernelGGL((k_fused_lx2<nl, v == VAR_PROF, ar, v == VAR_VA, md>), dim3(grid), dim3(ShapeP::NW * 64), 0, a.stream, A);
+          else throw StateError("k_fused_lx2: not an instance of part 0");
+        }, A.NL, st.arith, var, st.md);
+        break;
+      default: throw StateError("k_fused_lx2: no launch function for part " + std::to_string(part));
+    }
   });
   return true;
 }

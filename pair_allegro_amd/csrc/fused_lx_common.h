@@ -148,15 +148,15 @@ static __global__ void k_lx_shape_select(int *ntl, const int *maxdeg) {
   ntl[4] = wide ? n : 0; ntl[5] = 0;
 }
 
-// phases of the profiled instances (AHIP_FUSED_PROF=1, 3 layers, MLP depth 2, read-out depth 1): the kernels' PX_* / PP_* enums
+// phases of the profiled instances (AHIP_FUSED_PROF=1): the kernels' PX_* / PP_* enums
 static constexpr int LX_NPHASE = 13;
-// One evaluation on a prepared wide kernel (shape S): tile packing, arguments, `launch(A, grid, variant, waves)` (the file's instance dispatch; variant:
-// fused_common.h, VAR_*), the energy / virial sums, and the per-phase profile printed as "[ahip <name> prof]" (tools/abprof.sh reads it).
+// One evaluation on a prepared wide kernel (shape S): tile packing, arguments, `launch(A, grid, variant, part)` (the file's instance dispatch; variant: VAR_*, part: the
+// part of the file that holds the instance of `key` at this tile shape -- fused_shapes.h: FUSED_INSTANCES; the gates and lx_max_tile_slots keep a model without one away), the energy / virial sums, and the per-phase profile printed as "[ahip <name> prof]" (tools/abprof.sh reads it).
 // S8 / nw (k_fused_lx only): the kernel's second, 8-wave shape and which one runs -- 4: S, 8: S8, 0: both are launched, the stand-alone packing kernels widen the
 // tiles from the device word of the list's largest degree and k_lx_shape_select hands the tile count to the shape they were packed for and 0 to the other, which
 // returns at once.  Each shape has its own tile counter and its own rows of `partial`, so the kernels' device code knows nothing of the choice.
 template <class S, class S8 = S, class Launch>
-static void lx_run(Model &m, const ComputeArgs &a, FusedLxState &st, const char *name, Launch launch, int nw = 4) {
+static void lx_run(Model &m, const ComputeArgs &a, FusedLxState &st, const char *name, FusedInstanceKey key, Launch launch, int nw = 4) {
   static_assert(S::SLOTS == LX_TILE_SLOTS && S::MAXA == LX_TILE_MAXA, "allegro_hip.hip requests this tile shape from the edge build");
   static_assert(std::is_same<S, S8>::value || (S8::SLOTS == lx_tile_slots(true) && S8::MAXA == lx_tile_maxa(true)), "fused_shapes.h: the 8-wave tile shape");
   m.arith.last = st.arith;
@@ -169,7 +169,9 @@ static void lx_run(Model &m, const ComputeArgs &a, FusedLxState &st, const char 
   fused_tile_args(m, st.tiles, a, A, slots, maxa, maxdeg_sel, nw == 4, S8::MAXA);      // (the edge build packs 4-wave tiles only)
   int *const ntl = const_cast<int *>(A.ntiles);      // [0] tiles, [1] counter (fused_tile_args); nw == 0: [2], [3] the same for the 4-wave shape, [4], [5] for the 8-wave shape
   if (nw == 0) hipLaunchKernelGGL(k_lx_shape_select, dim3(1), dim3(1), 0, s, ntl, maxdeg_sel);
-  const bool prof = st.prof_on && A.NL == 3 && st.md == 2 && st.rd == 1 && nw == 4;
+  key.NL = A.NL; key.tile = 4; key.var = VAR_PROF;
+  const bool prof = st.prof_on && nw == 4 && fused_find_instance(key);
+  key.var = fused_variant(A.vatom, prof);
   {
     StageTimer tm(m, "model_fused", s);
     if (prof && !A.vatom) {
@@ -187,7 +189,8 @@ static void lx_run(Model &m, const ComputeArgs &a, FusedLxState &st, const char 
       // claims of TCHUNK tiles amortise the counter's round trip; with few tiles per workgroup the last claim decides the makespan
       // (10 648 Si atoms: 4 659 tiles on 512 workgroups = 12 instead of 10 tile times with claims of 4)
       A.tchunk = (fused_nedges_estimate(m) / (shape == 8 ? S8::SLOTS : S::SLOTS) > (long long)grid * 256) ? TCHUNK : 1;
-      launch(A, grid, fused_variant(A.vatom, prof), shape);
+      key.tile = shape;
+      launch(A, grid, key.var, fused_require_instance(key).part);
     }
   }
   AHIP_CHECK(hipGetLastError());
@@ -412,7 +415,6 @@ __device__ __forceinline__ f32x2 bload_half(__amdgpu_buffer_rsrc_t r, int voff, 
   const float q = __builtin_bit_cast(float, (voff + soff) | 0x3f000000);
   return f32x2{q, q};
 #else
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
   return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, AHIP_ROW_AUX));
 #endif
 }
