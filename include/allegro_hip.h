@@ -455,6 +455,35 @@ int ahip_comm_migrate(ahip_comm *c, int nlocal, double *x_dev, double *v_dev, lo
                       const int *grid, const int *coord, int *nlocal_new, void *stream);
 int ahip_comm_borders(ahip_comm *c, int nlocal, double *x_dev, int *mtype_dev, int capacity, const double *lo, const double *hi, const double *box,
                       double rc, const int *grid, const int *coord, int *nall, void *stream);
+/* The same two calls for ANY cell -- triclinic, with open axes -- decomposed into bricks of FRACTIONAL coordinates (LAMMPS' "lamda" decomposition of a triclinic
+ * box).  `cell`: host [9], rows = lattice vectors; `pbc`: host [3]; s = x . cell^-1 and m_d = rc / h_d (h_d the cell height along d) are those of
+ * ahip_borders_cell_dev (csrc/cell_geom.h), so one rank and many ranks decide alike.  Both calls are collective.
+ * Brick: the brick of `coord` is lo_d = (double)coord_d / grid_d <= s_d < hi_d = (double)(coord_d + 1) / grid_d; an atom's brick index along d is
+ *   clamp(floor(s_d * grid_d), 0, grid_d - 1), so an atom outside [0, 1) on an open axis belongs to the edge brick.
+ * ahip_comm_migrate_cell: wraps the owned rows with the rule of ahip_wrap_cell_dev (periodic axes only; an atom already inside comes back bit for bit), then, per
+ *   decomposed dimension, builds the keep / down / up lists with the delta rule of ahip_comm_migrate on the brick index above (at most one brick per
+ *   re-neighboring; with two bricks on a periodic axis "down" wins).  Across the face of an open axis nothing leaves and nothing arrives: there the difference of
+ *   brick indices is taken without the modulus, and no message is posted between the two edge bricks.  Row order (kept rows, then what the upper neighbour sent
+ *   down, then what the lower neighbour sent up), the 64-byte record, the single merged message with two bricks and the overflow answer -(rows needed), agreed on
+ *   by all ranks, are those of ahip_comm_migrate.
+ * ahip_comm_borders_cell: per dimension, over the rows known before that dimension, the lower list is s_d < lo_d + m_d and the upper list s_d >= hi_d - m_d, with
+ *   s taken from the row's current Cartesian position; ghosts are stored as Cartesian rows.  A step that wraps adds the lattice vector +a_d (downwards) or -a_d
+ *   (upwards) as three plain additions, a step that does not wrap copies the row bit for bit.  Nothing crosses the face of an open axis: the edge brick's swap towards
+ *   the face sends nothing, the brick at the other edge receives nothing through it, and no message is posted between them (with one brick along the axis that
+ *   swap has nsend = nrecv = 0).  Append order (first what came from above, then what came from below), the 28 bytes per row, the single merged message with two
+ *   bricks and the capacity protocol with its agreement are those of ahip_comm_borders.  The call INSTALLS the plan that ahip_comm_forward / ahip_comm_reverse run;
+ *   forward adds the same lattice vectors (a plan of ahip_comm_set_plan or ahip_comm_borders keeps its single-coordinate shift, bit for bit as before).
+ * An orthogonal cell (zero off-diagonal entries, positive diagonal) with all three axes periodic IS the box of ahip_comm_migrate / ahip_comm_borders and is decided
+ *   by them, in Cartesian coordinates (brick [box_d coord_d / grid_d, box_d (coord_d + 1) / grid_d), single-coordinate shifts), so that both spellings of one system
+ *   give the same rows bit for bit; fractional arithmetic cannot promise that (5 * (1 / 24) and 5 / 24 are different doubles).
+ * Refusals: AHIP_ERR_ARG before any launch or message, from the host arguments alone, hence on every rank alike (nobody is left waiting):
+ *   a singular or non-finite cell, a grid that does not match the communicator (both calls); and, in ahip_comm_borders_cell, where rc is known:
+ *   grid_d >= 2 with h_d / grid_d < rc (a brick thinner than the halo), and grid_d == 1 on a periodic axis with h_d < rc (several images per direction: one rank
+ *   builds that shell with ahip_borders_cell_dev).  Bricks thinner than the halo, which need several swaps per direction, are out of scope. */
+int ahip_comm_migrate_cell(ahip_comm *c, int nlocal, double *x_dev, double *v_dev, long long *tag_dev, int *mtype_dev, int capacity,
+                           const double *cell, const int *pbc, const int *grid, const int *coord, int *nlocal_new, void *stream);
+int ahip_comm_borders_cell(ahip_comm *c, int nlocal, double *x_dev, int *mtype_dev, int capacity, const double *cell, const int *pbc,
+                           double rc, const int *grid, const int *coord, int *nall, void *stream);
 /* x_dev [nall][3]: ghost rows refreshed from their owners (forward);  f_dev [nall][3]: ghost rows added to their owners (reverse). */
 int ahip_comm_forward(ahip_comm *c, double *x_dev, void *stream);
 int ahip_comm_reverse(ahip_comm *c, double *f_dev, void *stream);

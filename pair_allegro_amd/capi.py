@@ -40,6 +40,7 @@ SYMBOLS = [
     "ahip_set_active_types", "ahip_get_active_types",
     "ahip_wrap_cell_dev", "ahip_borders_cell_dev", "ahip_compute_cell", "ahip_last_cell_rows",
     "ahip_compute_cells", "ahip_last_cells_ghosts",
+    "ahip_comm_migrate_cell", "ahip_comm_borders_cell",
 ]
 
 
@@ -140,6 +141,10 @@ class Library:
         L.ahip_comm_borders.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
         L.ahip_comm_selftest.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.ahip_comm_migrate_cell.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
+        L.ahip_comm_borders_cell.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                             C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
         L.ahip_fill_zero_dev.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
 
     def debug_fused_linear(self, W: np.ndarray, x: np.ndarray) -> np.ndarray:
@@ -606,6 +611,24 @@ class Comm:
         out = C.c_int(0)
         self.L.check(self.L.lib.ahip_comm_borders(self.h, nlocal, C.c_void_p(x_ptr), C.c_void_p(mtype_ptr), capacity, _p(a[0], C.c_double), _p(a[1], C.c_double),
                                                   _p(a[2], C.c_double), float(rc), _p(g, C.c_int), _p(c, C.c_int), C.byref(out), stream or None))
+        return out.value
+
+    def migrate_cell(self, nlocal: int, x_ptr: int, v_ptr: int, tag_ptr: int, mtype_ptr: int, capacity: int, cell, pbc, grid, coord, stream: int = 0) -> int:
+        """Comm::exchange for any cell, bricks of fractional coordinates (ahip_comm_migrate_cell); returns the new owned count, negative = rows some brick would need."""
+        h = np.ascontiguousarray(cell, dtype=np.float64).reshape(9); p = np.ascontiguousarray([1 if b else 0 for b in pbc], dtype=np.int32)
+        g = np.ascontiguousarray(grid, dtype=np.int32); c = np.ascontiguousarray(coord, dtype=np.int32)
+        out = C.c_int(0)
+        self.L.check(self.L.lib.ahip_comm_migrate_cell(self.h, nlocal, C.c_void_p(x_ptr), C.c_void_p(v_ptr), C.c_void_p(tag_ptr), C.c_void_p(mtype_ptr), capacity,
+                                                       _p(h, C.c_double), _p(p, C.c_int), _p(g, C.c_int), _p(c, C.c_int), C.byref(out), stream or None))
+        return out.value
+
+    def borders_cell(self, nlocal: int, x_ptr: int, mtype_ptr: int, capacity: int, cell, pbc, rc: float, grid, coord, stream: int = 0) -> int:
+        """Comm::borders for any cell (ahip_comm_borders_cell): ghosts behind the owned rows, the exchange plan installed; returns owned + ghost rows (> capacity: retry)."""
+        h = np.ascontiguousarray(cell, dtype=np.float64).reshape(9); p = np.ascontiguousarray([1 if b else 0 for b in pbc], dtype=np.int32)
+        g = np.ascontiguousarray(grid, dtype=np.int32); c = np.ascontiguousarray(coord, dtype=np.int32)
+        out = C.c_int(0)
+        self.L.check(self.L.lib.ahip_comm_borders_cell(self.h, nlocal, C.c_void_p(x_ptr), C.c_void_p(mtype_ptr), capacity, _p(h, C.c_double), _p(p, C.c_int),
+                                                       float(rc), _p(g, C.c_int), _p(c, C.c_int), C.byref(out), stream or None))
         return out.value
 
     def allreduce(self, ptr: int, count: int, kind: int, stream: int = 0) -> None:

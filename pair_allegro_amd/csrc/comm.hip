@@ -30,6 +30,7 @@
 #include "../../include/allegro_hip.h"
 #include "engine.h"
 #include "prims.h"
+#include "cell_geom.h"
 
 extern "C" int ahip_comm_allreduce(ahip_comm *h, void *buf_dev, int count, int kind, void *stream);
 
@@ -45,6 +46,15 @@ static __global__ void k_comm_pack(int n, const long long *idx, const double *x,
   const long long i = idx[k];
   double v0 = x[3 * i], v1 = x[3 * i + 1], v2 = x[3 * i + 2];
   if (dim == 0) v0 += shift; else if (dim == 1) v1 += shift; else v2 += shift;
+  buf[3 * k] = v0; buf[3 * k + 1] = v1; buf[3 * k + 2] = v2;
+}
+// general cell: buf[k] = x[idx[k]] + (a lattice vector, three plain additions) where the step wraps, else the row bit for bit (adding 0.0 would turn -0.0 into +0.0)
+static __global__ void k_comm_pack_vec(int n, const long long *idx, const double *x, int add, double s0, double s1, double s2, double *buf) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const long long i = idx[k];
+  double v0 = x[3 * i], v1 = x[3 * i + 1], v2 = x[3 * i + 2];
+  if (add) { v0 += s0; v1 += s1; v2 += s2; }
   buf[3 * k] = v0; buf[3 * k + 1] = v1; buf[3 * k + 2] = v2;
 }
 // f[idx[k]] += buf[k]   (several k may name the same row: atomics)
@@ -115,6 +125,9 @@ struct Swap {
   int dim, sendrank, recvrank, nsend, nrecv, first_recv;
   double shift;
   const long long *send_idx;      // device, owned by the caller, valid until the next set_plan
+  // general cell (ahip_comm_borders_cell): vec 1 = the rows travel with the lattice vector shift3 added, 2 = bit for bit; 0 = the scalar shift on coordinate dim
+  int vec = 0;
+  double shift3[3] = {0.0, 0.0, 0.0};
 };
 
 struct Comm {
@@ -172,6 +185,13 @@ static bool pair_has_one_peer(const Comm &c, size_t k) {
          b.first_recv == a.first_recv + a.nrecv;
 }
 
+// the rows of one swap, shifted, into dst: the single-coordinate kernel for the plans of ahip_comm_set_plan / ahip_comm_borders, the vector one for a general cell
+static void pack_swap(const Swap &sw, const double *x, double *dst, hipStream_t s) {
+  if (sw.nsend <= 0) return;
+  if (sw.vec == 0) hipLaunchKernelGGL(k_comm_pack, dim3((sw.nsend + 255) / 256), dim3(256), 0, s, sw.nsend, sw.send_idx, x, sw.dim, sw.shift, dst);
+  else hipLaunchKernelGGL(k_comm_pack_vec, dim3((sw.nsend + 255) / 256), dim3(256), 0, s, sw.nsend, sw.send_idx, x, sw.vec == 1 ? 1 : 0, sw.shift3[0], sw.shift3[1], sw.shift3[2], dst);
+}
+
 static void comm_forward(Comm &c, double *x, hipStream_t s) {
   if (c.local_plan) {
     if (c.loc_nghost > 0)
@@ -188,8 +208,8 @@ static void comm_forward(Comm &c, double *x, hipStream_t s) {
       const Swap &a = c.swaps[k], &b = c.swaps[k + 1];
       c.sendbuf[0].reserve((size_t)std::max(a.nsend + b.nsend, 1) * 24);
       double *buf = c.sendbuf[0].as<double>();
-      if (a.nsend > 0) hipLaunchKernelGGL(k_comm_pack, dim3((a.nsend + 255) / 256), dim3(256), 0, s, a.nsend, a.send_idx, x, a.dim, a.shift, buf);
-      if (b.nsend > 0) hipLaunchKernelGGL(k_comm_pack, dim3((b.nsend + 255) / 256), dim3(256), 0, s, b.nsend, b.send_idx, x, b.dim, b.shift, buf + 3 * (size_t)a.nsend);
+      pack_swap(a, x, buf, s);
+      pack_swap(b, x, buf + 3 * (size_t)a.nsend, s);
       X.send(buf, (long long)(a.nsend + b.nsend) * 24, a.sendrank);
       X.recv(x + 3 * (size_t)a.first_recv, (long long)(a.nrecv + b.nrecv) * 24, a.sendrank);
       X.run();
@@ -201,8 +221,7 @@ static void comm_forward(Comm &c, double *x, hipStream_t s) {
       double *dst;
       if (self) dst = x + 3 * (size_t)sw.first_recv;                       // local image copy: straight into the ghost rows
       else { c.sendbuf[q - k].reserve((size_t)std::max(sw.nsend, 1) * 24); dst = c.sendbuf[q - k].as<double>(); }
-      if (sw.nsend > 0)
-        hipLaunchKernelGGL(k_comm_pack, dim3((sw.nsend + 255) / 256), dim3(256), 0, s, sw.nsend, sw.send_idx, x, sw.dim, sw.shift, dst);
+      pack_swap(sw, x, dst, s);
       if (!self) {
         X.send(dst, (long long)sw.nsend * 24, sw.sendrank);
         X.recv(x + 3 * (size_t)sw.first_recv, (long long)sw.nrecv * 24, sw.recvrank);
@@ -280,6 +299,28 @@ __device__ inline int row_class(const double *x, int i, const MigCut c) {
   cell = cell < 0 ? 0 : (cell > c.g - 1 ? c.g - 1 : cell);
   const int delta = ((cell - c.coord) % c.g + c.g) % c.g;
   return delta == c.g - 1 ? 1 : (delta == 1 ? 2 : 0);
+}
+// General cell (ahip_comm_borders_cell / ahip_comm_migrate_cell): the same two decisions on the fractional coordinate s_d = cell_frac (cell_geom.h: the very s
+// the one-rank builder of neigh.hip sees).  Slab: lo_cut = lo_d + m_d, hi_cut = hi_d - m_d with the brick [lo_d, hi_d) = [coord_d / grid_d, (coord_d + 1) / grid_d).
+struct FracSlabCut { CellGeom g; int dim; double lo_cut, hi_cut; };
+__device__ inline int row_class(const double *x, int i, const FracSlabCut &c) {
+  const double v = cell_frac(c.g, x + 3 * (size_t)i, c.dim);
+  return (v < c.lo_cut ? 1 : 0) | (v >= c.hi_cut ? 2 : 0);
+}
+// Migration: brick index clamp(floor(s_d * g), 0, g - 1), so an atom outside [0, 1) on an open axis belongs to the edge brick.  A periodic axis takes the delta
+// rule of MigCut; on an open axis nothing crosses the cell face, so the difference is taken without the modulus (with two bricks "up" then means up).
+struct FracMigCut { CellGeom g; int dim, gr, coord, periodic; };
+__device__ inline int row_class(const double *x, int i, const FracMigCut &c) {
+  const double b = floor(cell_frac(c.g, x + 3 * (size_t)i, c.dim) * c.gr);
+  const int cell = !(b > 0.0) ? 0 : (b > c.gr - 1 ? c.gr - 1 : (int)b);
+  if (!c.periodic) return cell - c.coord == -1 ? 1 : (cell - c.coord == 1 ? 2 : 0);
+  const int delta = ((cell - c.coord) % c.gr + c.gr) % c.gr;
+  return delta == c.gr - 1 ? 1 : (delta == 1 ? 2 : 0);
+}
+static __global__ void k_comm_wrap_cell(int n, double *x, CellGeom g) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  cell_wrap_row(g, x + 3 * (size_t)i);
 }
 template <class Cut, bool MIG> static __global__ void k_cls_count(int n, const double *x, Cut c, int nchunk, int *cnt) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -364,7 +405,9 @@ static int neighbour(const int *grid, const int *coord, const double *box, int d
   return rank_of(grid, c[0], c[1], c[2]);
 }
 // my two counts go to the two neighbours, theirs come back (8 bytes per peer; one message when both neighbours are the same rank)
-static void exchange_counts(Comm &c, hipStream_t s, const int nsend[2], const int to[2], const int from[2], int nrecv[2]) {
+// `open_face` (general cell, three or more bricks along an open axis): open_face[q] names the swap q whose SEND would cross the cell face, which makes the receive of
+// the other swap come across it too: neither count travels, and what would have been received counts as 0.
+static void exchange_counts(Comm &c, hipStream_t s, const int nsend[2], const int to[2], const int from[2], int nrecv[2], const bool *open_face = nullptr) {
   c.words.reserve(64);
   int *w = c.words.as<int>();                     // [0..1] mine, [4..5] received
   const bool self0 = to[0] == c.rank && from[0] == c.rank, self1 = to[1] == c.rank && from[1] == c.rank;
@@ -372,18 +415,22 @@ static void exchange_counts(Comm &c, hipStream_t s, const int nsend[2], const in
   if (self0 && self1) return;
   AHIP_CHECK(hipMemcpyAsync(w, nsend, 8, hipMemcpyHostToDevice, s));
   Xfer X{c, s, {}};
+  const bool dead_send[2] = {open_face && open_face[0], open_face && open_face[1]};
+  const bool dead_recv[2] = {dead_send[1], dead_send[0]};      // swap 0 receives from above, which is across the face exactly where sending upwards is
   if (!self0 && !self1 && to[0] == to[1] && from[0] == from[1] && to[0] == from[0]) {          // two bricks along the dimension: one peer
     X.send(w, 8, to[0]); X.recv(w + 4, 8, from[0]);
   } else {
-    if (!self0) { X.send(w, 4, to[0]); X.recv(w + 4, 4, from[0]); }
-    if (!self1) { X.send(w + 1, 4, to[1]); X.recv(w + 5, 4, from[1]); }
+    if (!self0 && !dead_send[0]) X.send(w, 4, to[0]);
+    if (!self0 && !dead_recv[0]) X.recv(w + 4, 4, from[0]);
+    if (!self1 && !dead_send[1]) X.send(w + 1, 4, to[1]);
+    if (!self1 && !dead_recv[1]) X.recv(w + 5, 4, from[1]);
   }
   X.run();
   int got[2] = {0, 0};
   AHIP_CHECK(hipMemcpyAsync(got, w + 4, 8, hipMemcpyDeviceToHost, s));
   AHIP_CHECK(hipStreamSynchronize(s));
-  if (!self0) nrecv[0] = got[0];
-  if (!self1) nrecv[1] = got[1];
+  if (!self0) nrecv[0] = dead_recv[0] ? 0 : got[0];
+  if (!self1) nrecv[1] = dead_recv[1] ? 0 : got[1];
 }
 // in-place max over the ranks of one host integer (the "does anybody overflow" agreement)
 static int agree_max(Comm &c, hipStream_t s, int v) {
@@ -397,36 +444,66 @@ static int agree_max(Comm &c, hipStream_t s, int v) {
   return v;
 }
 
+// the lower and the upper send list of dimension d over the rows [0, nprev), in ascending row order: count per chunk, scan, fill
+template <class Cut> static void slab_lists(Comm &c, hipStream_t s, int nprev, const double *x, const Cut &cut, int d, int nsend[2], long long *lst[2]) {
+  const int nchunk = (nprev + CH - 1) / CH;
+  c.cnt.reserve((size_t)2 * nchunk * sizeof(int)); c.off.reserve(((size_t)2 * nchunk + 1) * sizeof(int));
+  hipLaunchKernelGGL((k_cls_count<Cut, false>), dim3(gridfor(nchunk)), dim3(256), 0, s, nprev, x, cut, nchunk, c.cnt.as<int>());
+  AHIP_CHECK(prim_exclusive_scan_i32(c.prim, c.cnt.as<int>(), c.off.as<int>(), 2 * nchunk, s));
+  int tot[2] = {0, 0};
+  AHIP_CHECK(hipMemcpyAsync(&tot[0], c.off.as<int>() + nchunk, 4, hipMemcpyDeviceToHost, s));
+  AHIP_CHECK(hipMemcpyAsync(&tot[1], c.off.as<int>() + 2 * nchunk, 4, hipMemcpyDeviceToHost, s));
+  AHIP_CHECK(hipStreamSynchronize(s));
+  nsend[0] = tot[0]; nsend[1] = tot[1] - tot[0];
+  for (int q = 0; q < 2; ++q) { c.own_idx[2 * d + q].reserve((size_t)std::max(nsend[q], 1) * sizeof(long long)); lst[q] = c.own_idx[2 * d + q].as<long long>(); }
+  hipLaunchKernelGGL((k_cls_fill<Cut, false>), dim3(gridfor(nchunk)), dim3(256), 0, s, nprev, x, cut, nchunk, c.off.as<int>(), lst[0], lst[1], (long long *)nullptr);
+}
+// the neighbour of a general cell: which of the two swaps would send across the cell face (wraps[q] = +1: downwards, the rows gain +a_d; -1: upwards, -a_d)
+static void cell_neighbours(const int *grid, const int *coord, int d, int to[2], int from[2], int wraps[2]) {
+  const double unit[3] = {1.0, 1.0, 1.0};
+  double sh, dummy;
+  for (int q = 0; q < 2; ++q) {
+    const int step = q == 0 ? -1 : +1;
+    to[q] = neighbour(grid, coord, unit, d, step, &sh);
+    from[q] = neighbour(grid, coord, unit, d, -step, &dummy);
+    wraps[q] = sh > 0.0 ? +1 : (sh < 0.0 ? -1 : 0);
+  }
+}
 // Comm::borders.  x / mtype hold the nlocal owned atoms in rows [0, nlocal) and have room for `capacity` rows.  Returns the number of rows the brick
 // needs (owned + ghosts); > capacity means NOTHING may be used: every rank gets that answer together and the caller repeats the call with larger arrays.
+// With `cg` (ahip_comm_borders_cell) the cell is general: lo / hi are the FRACTIONAL bounds of the brick, the slab cuts lo_d + m_d and hi_d - m_d are compared with
+// s_d of the row's current Cartesian position, a swap that wraps adds the lattice vector, and nothing crosses the face of an open axis.
 static int comm_borders(Comm &c, int nlocal, double *x, int *mtype, int capacity, const double *lo, const double *hi, const double *box, double rc,
-                        const int *grid, const int *coord, hipStream_t s) {
+                        const int *grid, const int *coord, hipStream_t s, const CellGeom *cg = nullptr) {
   c.swaps.clear();
   c.local_plan = false;
   int ncur = nlocal, need = nlocal;
   bool overflow = nlocal > capacity;
   for (int d = 0; d < 3; ++d) {
     const int nprev = overflow ? 0 : ncur;                       // rows known before this dimension (after an overflow the lists no longer matter, only the message sizes do)
-    const int nchunk = (nprev + CH - 1) / CH;
     int nsend[2] = {0, 0};
     long long *lst[2] = {nullptr, nullptr};
     if (nprev > 0) {
-      c.cnt.reserve((size_t)2 * nchunk * sizeof(int)); c.off.reserve(((size_t)2 * nchunk + 1) * sizeof(int));
-      const SlabCut cut{d, lo[d] + rc, hi[d] - rc};
-      hipLaunchKernelGGL((k_cls_count<SlabCut, false>), dim3(gridfor(nchunk)), dim3(256), 0, s, nprev, x, cut, nchunk, c.cnt.as<int>());
-      AHIP_CHECK(prim_exclusive_scan_i32(c.prim, c.cnt.as<int>(), c.off.as<int>(), 2 * nchunk, s));
-      int tot[2] = {0, 0};
-      AHIP_CHECK(hipMemcpyAsync(&tot[0], c.off.as<int>() + nchunk, 4, hipMemcpyDeviceToHost, s));
-      AHIP_CHECK(hipMemcpyAsync(&tot[1], c.off.as<int>() + 2 * nchunk, 4, hipMemcpyDeviceToHost, s));
-      AHIP_CHECK(hipStreamSynchronize(s));
-      nsend[0] = tot[0]; nsend[1] = tot[1] - tot[0];
-      for (int q = 0; q < 2; ++q) { c.own_idx[2 * d + q].reserve((size_t)std::max(nsend[q], 1) * sizeof(long long)); lst[q] = c.own_idx[2 * d + q].as<long long>(); }
-      hipLaunchKernelGGL((k_cls_fill<SlabCut, false>), dim3(gridfor(nchunk)), dim3(256), 0, s, nprev, x, cut, nchunk, c.off.as<int>(), lst[0], lst[1], (long long *)nullptr);
+      if (cg) slab_lists(c, s, nprev, x, FracSlabCut{*cg, d, lo[d] + cg->m[d], hi[d] - cg->m[d]}, d, nsend, lst);
+      else slab_lists(c, s, nprev, x, SlabCut{d, lo[d] + rc, hi[d] - rc}, d, nsend, lst);
     }
     int to[2], from[2], nrecv[2];
-    double shift[2], dummy;
-    for (int q = 0; q < 2; ++q) { const int step = q == 0 ? -1 : +1; to[q] = neighbour(grid, coord, box, d, step, &shift[q]); from[q] = neighbour(grid, coord, box, d, -step, &dummy); }
-    exchange_counts(c, s, nsend, to, from, nrecv);
+    double shift[2] = {0.0, 0.0}, dummy;
+    Swap proto[2];                                                 // how the two swaps of this dimension shift their rows
+    bool open_face[2] = {false, false};
+    if (cg) {
+      int wraps[2];
+      cell_neighbours(grid, coord, d, to, from, wraps);
+      for (int q = 0; q < 2; ++q) {
+        proto[q].vec = wraps[q] ? 1 : 2;
+        for (int k = 0; k < 3; ++k) proto[q].shift3[k] = wraps[q] > 0 ? cg->h[3 * d + k] : (wraps[q] < 0 ? -cg->h[3 * d + k] : 0.0);
+        open_face[q] = wraps[q] != 0 && !cg->pbc[d];
+        if (open_face[q]) nsend[q] = 0;                            // an edge brick sends nothing across the face of an open axis
+      }
+    } else
+      for (int q = 0; q < 2; ++q) { const int step = q == 0 ? -1 : +1; to[q] = neighbour(grid, coord, box, d, step, &shift[q]); from[q] = neighbour(grid, coord, box, d, -step, &dummy); }
+    for (int q = 0; q < 2; ++q) { proto[q].dim = d; proto[q].shift = shift[q]; proto[q].nsend = nsend[q]; proto[q].send_idx = lst[q]; }
+    exchange_counts(c, s, nsend, to, from, nrecv, cg ? open_face : nullptr);
     need += nrecv[0] + nrecv[1];
     const bool fits = !overflow && (long long)ncur + nrecv[0] + nrecv[1] <= capacity;
     // messages: [x rows (24 B each) | model types (4 B each)] per swap; both swaps of a dimension in one message when they share the peer.  A rank that has
@@ -441,7 +518,7 @@ static int comm_borders(Comm &c, int nlocal, double *x, int *mtype, int capacity
       const bool self = q == 0 ? self0 : self1;
       if (self) {                                                  // one brick along this dimension: my own periodic images, straight into their rows
         if (fits && nsend[q] > 0) {
-          hipLaunchKernelGGL(k_comm_pack, dim3(gridfor(nsend[q])), dim3(256), 0, s, nsend[q], lst[q], x, d, shift[q], x + 3 * (size_t)first[q]);
+          pack_swap(proto[q], x, x + 3 * (size_t)first[q], s);
           hipLaunchKernelGGL(k_gather_i32, dim3(gridfor(nsend[q])), dim3(256), 0, s, nsend[q], lst[q], mtype, mtype + first[q]);
         }
         continue;
@@ -452,7 +529,7 @@ static int comm_borders(Comm &c, int nlocal, double *x, int *mtype, int capacity
       double *xs = (double *)sb + (q == 1 && one_peer ? 3 * (size_t)n0 : 0);
       int *ts = (int *)(sb + 24 * ((size_t)n0 + n1)) + (q == 1 && one_peer ? n0 : 0);
       if (nsend[q] > 0 && nprev > 0) {
-        hipLaunchKernelGGL(k_comm_pack, dim3(gridfor(nsend[q])), dim3(256), 0, s, nsend[q], lst[q], x, d, shift[q], xs);
+        pack_swap(proto[q], x, xs, s);
         hipLaunchKernelGGL(k_gather_i32, dim3(gridfor(nsend[q])), dim3(256), 0, s, nsend[q], lst[q], mtype, ts);
       }
       if (!one_peer) { X.send(sb, msg_bytes(nsend[q]), to[q]); X.recv(c.recvbuf[q].p, msg_bytes(nrecv[q]), from[q]); }
@@ -470,8 +547,11 @@ static int comm_borders(Comm &c, int nlocal, double *x, int *mtype, int capacity
         hipLaunchKernelGGL(k_copy_f64, dim3(gridfor(3LL * nrecv[q])), dim3(256), 0, s, 3LL * nrecv[q], xr, x + 3 * (size_t)first[q]);
         hipLaunchKernelGGL(k_copy_i32, dim3(gridfor(nrecv[q])), dim3(256), 0, s, (long long)nrecv[q], tr, mtype + first[q]);
       }
-      for (int q = 0; q < 2; ++q)
-        c.swaps.push_back(Swap{d, to[q], from[q], nsend[q], nrecv[q], first[q], shift[q], lst[q]});
+      for (int q = 0; q < 2; ++q) {
+        Swap sw = proto[q];
+        sw.sendrank = to[q]; sw.recvrank = from[q]; sw.nrecv = nrecv[q]; sw.first_recv = first[q];
+        c.swaps.push_back(sw);
+      }
       ncur += nrecv[0] + nrecv[1];
     } else overflow = true;
   }
@@ -482,36 +562,52 @@ static int comm_borders(Comm &c, int nlocal, double *x, int *mtype, int capacity
   return ncur;
 }
 
+// the down / up / keep lists of one dimension over the rows [0, n), in ascending row order
+template <class Cut> static void migrate_lists(Comm &c, hipStream_t s, int n, const double *x, const Cut &cut, int cntv[3], long long *lst[3]) {
+  const int nchunk = (n + CH - 1) / CH;
+  c.cnt.reserve((size_t)3 * nchunk * sizeof(int)); c.off.reserve(((size_t)3 * nchunk + 1) * sizeof(int));
+  hipLaunchKernelGGL((k_cls_count<Cut, true>), dim3(gridfor(nchunk)), dim3(256), 0, s, n, x, cut, nchunk, c.cnt.as<int>());
+  AHIP_CHECK(prim_exclusive_scan_i32(c.prim, c.cnt.as<int>(), c.off.as<int>(), 3 * nchunk, s));
+  int tot[3];
+  for (int q = 0; q < 3; ++q) AHIP_CHECK(hipMemcpyAsync(&tot[q], c.off.as<int>() + (q + 1) * nchunk, 4, hipMemcpyDeviceToHost, s));
+  AHIP_CHECK(hipStreamSynchronize(s));
+  cntv[0] = tot[0]; cntv[1] = tot[1] - tot[0]; cntv[2] = tot[2] - tot[1];
+  for (int q = 0; q < 3; ++q) { c.own_idx[q].reserve((size_t)std::max(cntv[q], 1) * sizeof(long long)); lst[q] = c.own_idx[q].as<long long>(); }
+  hipLaunchKernelGGL((k_cls_fill<Cut, true>), dim3(gridfor(nchunk)), dim3(256), 0, s, n, x, cut, nchunk, c.off.as<int>(), lst[0], lst[1], lst[2]);
+}
 // Comm::exchange.  Arrays x, v [capacity][3], tag, mtype [capacity] hold nlocal owned atoms; positions are wrapped into the periodic box and the atoms that
 // left this brick go to the neighbour brick, dimension by dimension (at most one brick per re-neighboring).  Returns the new number of owned atoms, or -need
 // (for every rank together) when a brick would exceed `capacity`.
+// With `cg` (ahip_comm_migrate_cell) the cell is general: the wrap is cell_wrap_row (periodic axes only), the brick index comes from the fractional coordinate and
+// nothing crosses the face of an open axis.
 static int comm_migrate(Comm &c, int nlocal, double *x, double *v, long long *tag, int *mtype, int capacity, const double *box, const int *grid,
-                        const int *coord, hipStream_t s) {
-  if (nlocal > 0) hipLaunchKernelGGL(k_wrap, dim3(gridfor(nlocal)), dim3(256), 0, s, nlocal, x, box[0], box[1], box[2]);
+                        const int *coord, hipStream_t s, const CellGeom *cg = nullptr) {
+  if (nlocal > 0) {
+    if (cg) hipLaunchKernelGGL(k_comm_wrap_cell, dim3(gridfor(nlocal)), dim3(256), 0, s, nlocal, x, *cg);
+    else hipLaunchKernelGGL(k_wrap, dim3(gridfor(nlocal)), dim3(256), 0, s, nlocal, x, box[0], box[1], box[2]);
+  }
   int n = nlocal, worst_need = 0;
   bool overflow = false;
   for (int d = 0; d < 3; ++d) {
     if (grid[d] == 1) continue;
-    const int nchunk = (n + CH - 1) / CH;
     int cntv[3] = {0, 0, n};
     long long *lst[3] = {nullptr, nullptr, nullptr};
-    const MigCut cut{d, grid[d], coord[d], box[d] / grid[d]};
     if (n > 0 && !overflow) {
-      c.cnt.reserve((size_t)3 * nchunk * sizeof(int)); c.off.reserve(((size_t)3 * nchunk + 1) * sizeof(int));
-      hipLaunchKernelGGL((k_cls_count<MigCut, true>), dim3(gridfor(nchunk)), dim3(256), 0, s, n, x, cut, nchunk, c.cnt.as<int>());
-      AHIP_CHECK(prim_exclusive_scan_i32(c.prim, c.cnt.as<int>(), c.off.as<int>(), 3 * nchunk, s));
-      int tot[3];
-      for (int q = 0; q < 3; ++q) AHIP_CHECK(hipMemcpyAsync(&tot[q], c.off.as<int>() + (q + 1) * nchunk, 4, hipMemcpyDeviceToHost, s));
-      AHIP_CHECK(hipStreamSynchronize(s));
-      cntv[0] = tot[0]; cntv[1] = tot[1] - tot[0]; cntv[2] = tot[2] - tot[1];
-      for (int q = 0; q < 3; ++q) { c.own_idx[q].reserve((size_t)std::max(cntv[q], 1) * sizeof(long long)); lst[q] = c.own_idx[q].as<long long>(); }
-      hipLaunchKernelGGL((k_cls_fill<MigCut, true>), dim3(gridfor(nchunk)), dim3(256), 0, s, n, x, cut, nchunk, c.off.as<int>(), lst[0], lst[1], lst[2]);
+      if (cg) migrate_lists(c, s, n, x, FracMigCut{*cg, d, grid[d], coord[d], cg->pbc[d]}, cntv, lst);
+      else migrate_lists(c, s, n, x, MigCut{d, grid[d], coord[d], box[d] / grid[d]}, cntv, lst);
     } else if (overflow) { cntv[0] = cntv[1] = 0; cntv[2] = 0; }
     int to[2], from[2], nrecv[2];
-    double dummy;
-    for (int q = 0; q < 2; ++q) { const int step = q == 0 ? -1 : +1; to[q] = neighbour(grid, coord, box, d, step, &dummy); from[q] = neighbour(grid, coord, box, d, -step, &dummy); }
+    bool open_face[2] = {false, false};                       // (their lists are empty by the rule of FracMigCut)
+    if (cg) {
+      int wraps[2];
+      cell_neighbours(grid, coord, d, to, from, wraps);
+      for (int q = 0; q < 2; ++q) open_face[q] = wraps[q] != 0 && !cg->pbc[d];
+    } else {
+      double dummy;
+      for (int q = 0; q < 2; ++q) { const int step = q == 0 ? -1 : +1; to[q] = neighbour(grid, coord, box, d, step, &dummy); from[q] = neighbour(grid, coord, box, d, -step, &dummy); }
+    }
     const int nsend[2] = {cntv[0], cntv[1]};
-    exchange_counts(c, s, nsend, to, from, nrecv);
+    exchange_counts(c, s, nsend, to, from, nrecv, cg ? open_face : nullptr);
     const bool one_peer = to[0] == to[1] && from[0] == from[1] && to[0] == from[0];
     for (int q = 0; q < 2; ++q) { c.mbuf[0].reserve((size_t)std::max(nsend[0] + nsend[1], 1) * 64); c.mbuf[1].reserve((size_t)std::max(nrecv[0] + nrecv[1], 1) * 64); }
     double *sb = c.mbuf[0].as<double>(), *rb = c.mbuf[1].as<double>();
@@ -727,6 +823,65 @@ extern "C" int ahip_comm_migrate(ahip_comm *h, int nlocal, double *x_dev, double
     throw ArgError("ahip_comm_migrate: bad argument");
   if (grid[0] * grid[1] * grid[2] != c->nranks) throw ArgError("ahip_comm_migrate: the rank grid does not match the communicator");
   *nlocal_new = comm_migrate(*c, nlocal, x_dev, v_dev, tag_dev, mtype_dev, capacity, box, grid, coord, (hipStream_t)stream);
+  COMM_CATCH
+}
+
+// what both general-cell calls check before any launch or message, from host arguments alone (so every rank decides alike): the geometry, and for borders
+// (rc > 0) that one swap per direction reaches every ghost
+static CellGeom brick_cell_geometry(const char *who, const Comm *c, const double *cell, const int *pbc, double rc, const int *grid, const int *coord) {
+  if (!cell || !pbc || !grid || !coord) throw ArgError(std::string(who) + ": null argument");
+  for (int d = 0; d < 3; ++d)
+    if (grid[d] < 1 || coord[d] < 0 || coord[d] >= grid[d]) throw ArgError(std::string(who) + ": bad grid / coordinate");
+  if ((long long)grid[0] * grid[1] * grid[2] != c->nranks) throw ArgError(std::string(who) + ": the rank grid does not match the communicator");
+  const CellGeom g = cell_geometry(who, cell, pbc, rc);
+  if (rc > 0.0)
+    for (int d = 0; d < 3; ++d) {
+      const std::string axis = std::string(who) + ": axis " + std::to_string(d);
+      if (grid[d] >= 2 && g.m[d] * grid[d] > 1.0)
+        throw ArgError(axis + ": a brick (cell height / " + std::to_string(grid[d]) + ") is thinner than rc; ghosts from beyond the nearest neighbour brick need several swaps per direction, which is out of scope: use fewer ranks along this axis");
+      if (grid[d] == 1 && g.pbc[d] && g.m[d] > 1.0)
+        throw ArgError(axis + ": the cell is thinner than rc along a periodic axis that is not decomposed (several images per direction); one rank builds such a shell with ahip_borders_cell_dev");
+    }
+  return g;
+}
+
+// An orthogonal, fully periodic cell IS the box of ahip_comm_borders / ahip_comm_migrate: it is decided in Cartesian coordinates by those very paths (brick
+// [box_d coord_d / grid_d, box_d (coord_d + 1) / grid_d), single-coordinate shifts), so that both spellings of one system give the same rows bit for bit.  Fractional
+// arithmetic cannot promise that: with box 24, 5 * (1 / 24) and 5 / 24 are different doubles, and an atom exactly rc from a brick face changes lists.
+static bool cell_is_box(const CellGeom &g, double box[3]) {
+  for (int r = 0; r < 3; ++r)
+    for (int k = 0; k < 3; ++k)
+      if (r == k ? !(g.h[3 * r + k] > 0.0) : g.h[3 * r + k] != 0.0) return false;
+  for (int d = 0; d < 3; ++d) { if (!g.pbc[d]) return false; box[d] = g.h[4 * d]; }
+  return true;
+}
+
+extern "C" int ahip_comm_borders_cell(ahip_comm *h, int nlocal, double *x_dev, int *mtype_dev, int capacity, const double *cell, const int *pbc, double rc,
+                                      const int *grid, const int *coord, int *nall, void *stream) {
+  COMM_TRY
+  Comm *c = (Comm *)h;
+  if (!c || nlocal < 0 || capacity < 0 || !nall || !(rc > 0.0) || !std::isfinite(rc) || (capacity > 0 && (!x_dev || !mtype_dev))) throw ArgError("ahip_comm_borders_cell: bad argument");
+  const CellGeom g = brick_cell_geometry("ahip_comm_borders_cell", c, cell, pbc, rc, grid, coord);
+  double lo[3], hi[3], box[3];
+  if (cell_is_box(g, box)) {
+    for (int d = 0; d < 3; ++d) { lo[d] = box[d] * coord[d] / grid[d]; hi[d] = box[d] * (coord[d] + 1) / grid[d]; }
+    *nall = comm_borders(*c, nlocal, x_dev, mtype_dev, capacity, lo, hi, box, rc, grid, coord, (hipStream_t)stream);
+    return AHIP_OK;
+  }
+  for (int d = 0; d < 3; ++d) { lo[d] = (double)coord[d] / grid[d]; hi[d] = (double)(coord[d] + 1) / grid[d]; }
+  *nall = comm_borders(*c, nlocal, x_dev, mtype_dev, capacity, lo, hi, nullptr, rc, grid, coord, (hipStream_t)stream, &g);
+  COMM_CATCH
+}
+
+extern "C" int ahip_comm_migrate_cell(ahip_comm *h, int nlocal, double *x_dev, double *v_dev, long long *tag_dev, int *mtype_dev, int capacity, const double *cell,
+                                      const int *pbc, const int *grid, const int *coord, int *nlocal_new, void *stream) {
+  COMM_TRY
+  Comm *c = (Comm *)h;
+  if (!c || nlocal < 0 || capacity < nlocal || !nlocal_new || (capacity > 0 && (!x_dev || !v_dev || !tag_dev || !mtype_dev))) throw ArgError("ahip_comm_migrate_cell: bad argument");
+  const CellGeom g = brick_cell_geometry("ahip_comm_migrate_cell", c, cell, pbc, 0.0, grid, coord);
+  double box[3];
+  if (cell_is_box(g, box)) *nlocal_new = comm_migrate(*c, nlocal, x_dev, v_dev, tag_dev, mtype_dev, capacity, box, grid, coord, (hipStream_t)stream);
+  else *nlocal_new = comm_migrate(*c, nlocal, x_dev, v_dev, tag_dev, mtype_dev, capacity, nullptr, grid, coord, (hipStream_t)stream, &g);
   COMM_CATCH
 }
 

@@ -8,6 +8,7 @@
 
 #include "engine.h"
 #include "prims.h"
+#include "cell_geom.h"
 
 namespace ahip {
 
@@ -333,16 +334,7 @@ int borders_local(Model &m, int nlocal, const double *x, const int *mtype, const
 // The admissible n_d are an integer interval [lo_d, hi_d], so the count is closed-form per atom; the fill runs one thread per OUTPUT row (a thread per atom would
 // serialise 856 images on four lanes): binary search of the scanned offsets for the source atom, n decoded from the rank inside the atom's image box, n3 fastest,
 // the zero image skipped.  Order: ascending source atom, then (n1, n2, n3) lexicographic.
-struct CellGeom {
-  double h[9];        // lattice vectors (rows)
-  double inv[9];      // cell^-1: s_d = sum_k x_k inv[3 k + d]
-  double m[3];        // rc / height (borders only)
-  int pbc[3];
-};
-// explicit fma chain: the count and the fill kernel must see the very same s
-__device__ __host__ inline double cell_frac(const CellGeom &g, const double *x, int d) {
-  return fma(x[2], g.inv[6 + d], fma(x[1], g.inv[3 + d], x[0] * g.inv[d]));
-}
+// CellGeom, cell_frac, cell_wrap_row and cell_geometry live in cell_geom.h: the brick decomposition (comm.hip) decides with the same s and the same m_d.
 __device__ __host__ inline int cell_clamp_int(double v) { return v < -1073741824.0 ? -1073741824 : (v > 1073741824.0 ? 1073741824 : (int)v); }
 // images admitted along d: lo <= n_d <= hi (an open axis: 0 only); returns their number
 __device__ __host__ inline int cell_image_range(const CellGeom &g, const double *x, int d, int *lo) {
@@ -386,13 +378,6 @@ __device__ inline bool cell_fill_row(const CellGeom &g, const double *xi, long l
   }
   return true;
 }
-// xi += (the integer lattice combination that brings s_d into [0, 1) on every periodic axis); an atom already inside is not touched
-__device__ __host__ inline void cell_wrap_row(const CellGeom &g, double *xi) {
-  double k[3];
-  for (int d = 0; d < 3; ++d) k[d] = g.pbc[d] ? -floor(cell_frac(g, xi, d)) : 0.0;
-  if (k[0] == 0.0 && k[1] == 0.0 && k[2] == 0.0) return;
-  for (int d = 0; d < 3; ++d) xi[d] += k[0] * g.h[d] + k[1] * g.h[3 + d] + k[2] * g.h[6 + d];
-}
 // largest a in [0, n) with off[a] <= k, for 0 <= k < off[n]: the source atom of output row k
 __device__ inline int cell_row_atom(const int *off, int n, long long k) {
   int a = 0, b = n;                                       // (off[a] <= k < off[b] throughout)
@@ -419,30 +404,6 @@ __global__ void k_cell_wrap(int n, double *x, CellGeom g) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   cell_wrap_row(g, x + 3 * i);
-}
-// cell (row-major, rows = lattice vectors), its inverse and rc / height; ArgError for a singular or non-finite cell
-static CellGeom cell_geometry(const char *who, const double *cell, const int *pbc, double rc) {
-  CellGeom g;
-  double scale = 0.0;
-  for (int k = 0; k < 9; ++k) {
-    if (!std::isfinite(cell[k])) throw ArgError(std::string(who) + ": the cell has a non-finite entry");
-    g.h[k] = cell[k];
-    scale = std::max(scale, std::fabs(cell[k]));
-  }
-  const double *a = g.h, *b = g.h + 3, *c = g.h + 6;
-  const double bc[3] = {b[1] * c[2] - b[2] * c[1], b[2] * c[0] - b[0] * c[2], b[0] * c[1] - b[1] * c[0]};
-  const double ca[3] = {c[1] * a[2] - c[2] * a[1], c[2] * a[0] - c[0] * a[2], c[0] * a[1] - c[1] * a[0]};
-  const double ab[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-  const double det = a[0] * bc[0] + a[1] * bc[1] + a[2] * bc[2];
-  if (!std::isfinite(det) || !(std::fabs(det) > 1e-12 * scale * scale * scale)) throw ArgError(std::string(who) + ": the cell is singular");
-  const double *cr[3] = {bc, ca, ab};                      // column d of cell^-1 = (cross product of the other two rows) / det
-  for (int d = 0; d < 3; ++d) {
-    double nrm = 0.0;
-    for (int k = 0; k < 3; ++k) { g.inv[3 * k + d] = cr[d][k] / det; nrm += cr[d][k] * cr[d][k]; }
-    g.m[d] = rc * std::sqrt(nrm) / std::fabs(det);         // rc / h_d,  h_d = volume / |cross product|
-    g.pbc[d] = pbc[d] != 0;
-  }
-  return g;
 }
 // images of n wrapped atoms: at most 2 ceil(m_d) + 1 each along a periodic axis
 static double cell_most_images(const CellGeom &g, int n) {

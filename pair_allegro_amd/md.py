@@ -132,7 +132,8 @@ class Simulation:
                  grid: Tuple[int, int, int] = (1, 1, 1), rank: int = 0, dist=None, dt: float = 0.001, overlap: Optional[bool] = None,
                  neigh_every: int = 1, neigh_delay: int = 0, neigh_check: bool = True, pbc: Sequence[bool] = (True, True, True)):
         """`box`: the three edge lengths of an orthogonal periodic box (brick decomposition over `grid`, every brick at least r_max + skin thick), or a 3x3
-        matrix whose rows are the lattice vectors of ANY cell -- triclinic, thinner than the cutoff, with open axes (`pbc`) -- on one rank."""
+        matrix whose rows are the lattice vectors of ANY cell -- triclinic, with open axes (`pbc`) -- decomposed over `grid` into bricks of fractional
+        coordinates (every brick at least r_max + skin high along its axis); on one rank the cell may also be thinner than the cutoff."""
         self.backend = backend
         # Overlapped schedule (SURVEY 8e): local atoms are ordered interior-first at every re-neighboring; the first half of
         # the interior centres is evaluated while ghost positions travel (forward comm), then the boundary centres, and the
@@ -141,15 +142,18 @@ class Simulation:
         # Default: overlapped when there is an exchange between ranks to hide; one rank evaluates all centres in one call (three
         # launches instead of one cost 2.5 % at 1 M atoms on one GPU: profiles/r02_a_overlap_1gpu.md).
         nranks = int(grid[0]) * int(grid[1]) * int(grid[2])
-        # General-cell mode (a 3x3 `box`): one rank owns every atom; wrap and ghosts come from the library (ahip_wrap_cell_dev, ahip_borders_cell_dev), the
-        # per-step exchange is the local plan.  A 3-vector `box` takes none of these branches.
+        # General-cell mode (a 3x3 `box`).  One rank owns every atom: wrap and ghosts come from the library (ahip_wrap_cell_dev, ahip_borders_cell_dev), the
+        # per-step exchange is the local plan.  Several ranks own bricks of fractional coordinates: migration, ghosts and the plan of the per-step exchange
+        # come from ahip_comm_migrate_cell / ahip_comm_borders_cell.  A 3-vector `box` takes none of these branches.
         self.cell = None
         self.pbc = tuple(bool(p) for p in pbc)
         if len(self.pbc) != 3:
             raise ValueError("pbc must have three entries")
         if np.asarray(box).shape == (3, 3):
-            if nranks != 1 or overlap:
-                raise ValueError("a 3x3 box (general cell) runs on one rank only, grid (1, 1, 1), with overlap off")
+            if nranks != 1 and dist is None:
+                raise ValueError(f"grid {tuple(grid)} needs a process group (dist); without one a 3x3 box (general cell) runs on one rank, grid (1, 1, 1)")
+            if nranks == 1 and overlap:
+                raise ValueError("a 3x3 box (general cell) on one rank, grid (1, 1, 1), runs with overlap off")
             if not (hasattr(backend, "wrap_cell") and hasattr(backend, "borders_cell")):
                 raise ValueError("a 3x3 box (general cell) needs a backend with wrap_cell and borders_cell")
             self.cell = np.ascontiguousarray(box, dtype=np.float64)
@@ -186,11 +190,32 @@ class Simulation:
         self.nranks = self.grid[0] * self.grid[1] * self.grid[2]
         self.coord = (rank // (self.grid[1] * self.grid[2]), (rank // self.grid[2]) % self.grid[1], rank % self.grid[2])
         xg = np.asarray(x_global, dtype=np.float64)
-        if self.cell is not None:
+        if self.cell is not None and self.nranks == 1:
             # lo / hi: the bounding box of the cell's eight corners (the list build bins over it, widened by rc); every atom is owned, wrapped or not
             self.lo = np.minimum(self.cell, 0.0).sum(axis=0)
             self.hi = np.maximum(self.cell, 0.0).sum(axis=0)
             own = np.ones(len(xg), dtype=bool)
+        elif self.cell is not None:
+            # Bricks of fractional coordinates (include/allegro_hip.h: ahip_comm_borders_cell): [coord_d / grid_d, (coord_d + 1) / grid_d) of s = x . cell^-1, an atom
+            # beyond an open face with the edge brick.  lo / hi: the bounding box of the brick's eight corners, for the list build as above.
+            inv = np.linalg.inv(self.cell)
+            self._cell_inv = inv
+            self._cell_margin = self.rc * np.linalg.norm(inv, axis=0)        # m_d = rc / height per axis
+            g = np.array(self.grid, dtype=np.float64)
+            for d in range(3):
+                if self.grid[d] >= 2 and self._cell_margin[d] * self.grid[d] > 1.0:
+                    raise ValueError(f"axis {d}: a brick (cell height {self.rc / self._cell_margin[d]:.4g} / {self.grid[d]}) is thinner than r_max+skin = {self.rc:.4g}: "
+                                     "use fewer ranks along that axis")
+                if self.grid[d] == 1 and self.pbc[d] and self._cell_margin[d] > 1.0:
+                    raise ValueError(f"axis {d}: the cell (height {self.rc / self._cell_margin[d]:.4g}) is thinner than r_max+skin = {self.rc:.4g} along a periodic axis: "
+                                     "such a cell runs on one rank, grid (1, 1, 1)")
+            self._brick_lo = np.array(self.coord, dtype=np.float64) / g
+            self._brick_hi = (np.array(self.coord, dtype=np.float64) + 1.0) / g
+            corners = np.array([[(self._brick_lo, self._brick_hi)[k][d] for d, k in enumerate(c)] for c in np.ndindex(2, 2, 2)]) @ self.cell
+            self.lo, self.hi = corners.min(axis=0), corners.max(axis=0)
+            sf = xg @ inv
+            sf = np.where(np.array(self.pbc), sf - np.floor(sf), sf)          # ownership only: the positions stay as given, the first migration wraps them
+            own = np.all(np.clip(np.floor(sf * g), 0, g - 1) == np.array(self.coord), axis=1)
         else:
             self.lo = np.array([self.box[d] * self.coord[d] / self.grid[d] for d in range(3)])
             self.hi = np.array([self.box[d] * (self.coord[d] + 1) / self.grid[d] for d in range(3)])
@@ -438,6 +463,48 @@ class Simulation:
         self.nall = nall
         self._ghost_src = self._ghost_shift = None
 
+    def _need_cell_comm(self) -> None:
+        if self.comm is None or not hasattr(self.comm.L.lib, "ahip_comm_borders_cell"):
+            raise RuntimeError("a 3x3 box on several ranks needs the library's communicator (ahip_comm_migrate_cell / ahip_comm_borders_cell)")
+
+    def _migrate_cell_lib(self) -> None:
+        """General cell, several ranks: wrap and hand-over inside the library, bricks of fractional coordinates (ahip_comm_migrate_cell)."""
+        self._need_cell_comm()
+        n = self.nlocal
+        cap = n + max(4096, n // 4)
+        x = torch.empty((cap, 3), dtype=torch.float64, device=self.dev); x[:n] = self.x[:n]
+        v = torch.empty((cap, 3), dtype=torch.float64, device=self.dev); v[:n] = self.v[:n]
+        tag = torch.empty(cap, dtype=torch.int64, device=self.dev); tag[:n] = self.tag[:n]
+        mt = torch.empty(cap, dtype=torch.int32, device=self.dev); mt[:n] = self.mtype[:n]
+        nn = self.comm.migrate_cell(n, x.data_ptr(), v.data_ptr(), tag.data_ptr(), mt.data_ptr(), cap, self.cell, self.pbc, self.grid, self.coord, self._stream())
+        if nn < 0:
+            raise RuntimeError(f"migration: a brick would hold {-nn} atoms, more than the {cap} rows provided (rank {self.rank})")
+        self.nlocal = nn
+        self.x, self.v, self.tag, self.mtype = x[:nn], v[:nn], tag[:nn], mt[:nn]
+
+    def _borders_cell_lib(self) -> None:
+        """General cell, several ranks: the ghost shell and the plan of the per-step exchange from ahip_comm_borders_cell, with the capacity protocol of _borders_lib."""
+        self._need_cell_comm()
+        nl = self.nlocal
+        width = (self._brick_hi - self._brick_lo) / self._cell_margin                 # brick height in units of rc
+        est = int(nl * (np.prod(1.0 + 2.0 / width) - 1.0) * 1.3) + 2048
+        cap = nl + max(est, int(1.25 * getattr(self, "_nghost_last", 0)))
+        if os.environ.get("AHIP_TEST_SMALL_BORDERS_CAP") == "1":      # tests only, as in _borders_lib
+            cap = nl + 8
+        while True:
+            xa = torch.empty((cap, 3), dtype=torch.float64, device=self.dev); xa[:nl] = self.x[:nl]
+            mta = torch.empty(cap, dtype=torch.int32, device=self.dev); mta[:nl] = self.mtype[:nl]
+            nall = self.comm.borders_cell(nl, xa.data_ptr(), mta.data_ptr(), cap, self.cell, self.pbc, self.rc, self.grid, self.coord, self._stream())
+            if nall <= cap:
+                break
+            cap = int(1.1 * nall) + 1024
+        self._nghost_last = nall - nl
+        self.swaps = []
+        self._lib_plan = True
+        self.x, self.mtype = xa[:nall], mta[:nall]
+        self.nall = nall
+        self._ghost_src = self._ghost_shift = None
+
     def _migrate_cell(self) -> None:
         """General cell, one rank: nobody changes owner, the atoms only go back into the cell along its periodic axes (one launch, nothing read back)."""
         n = self.nlocal
@@ -472,7 +539,7 @@ class Simulation:
 
     def _migrate(self) -> None:
         if self.cell is not None:
-            return self._migrate_cell()
+            return self._migrate_cell() if self.nranks == 1 else self._migrate_cell_lib()
         if self._lib_reneighbor():
             return self._migrate_lib()
         n = self.nlocal
@@ -536,7 +603,7 @@ class Simulation:
     def _borders(self) -> None:
         self._lib_plan = False
         if self.cell is not None:
-            return self._borders_cell()
+            return self._borders_cell() if self.nranks == 1 else self._borders_cell_lib()
         if self._borders_local():
             return
         if self._lib_reneighbor():
@@ -595,9 +662,14 @@ class Simulation:
         """Local atoms farther than r_max+skin from every brick face come first: every list neighbour of such an atom is a
         local atom, so its edges need no ghost position and produce no ghost force."""
         n = self.nlocal
-        lo = torch.tensor(self.lo + self.rc, dtype=torch.float64, device=self.dev)
-        hi = torch.tensor(self.hi - self.rc, dtype=torch.float64, device=self.dev)
-        x = self.x[:n]
+        if self.cell is not None:                       # general cell: the same rule in fractional coordinates, lo_d + m_d <= s_d < hi_d - m_d
+            lo = torch.tensor(self._brick_lo + self._cell_margin, dtype=torch.float64, device=self.dev)
+            hi = torch.tensor(self._brick_hi - self._cell_margin, dtype=torch.float64, device=self.dev)
+            x = self.x[:n] @ torch.tensor(self._cell_inv, dtype=torch.float64, device=self.dev)
+        else:
+            lo = torch.tensor(self.lo + self.rc, dtype=torch.float64, device=self.dev)
+            hi = torch.tensor(self.hi - self.rc, dtype=torch.float64, device=self.dev)
+            x = self.x[:n]
         interior = ((x >= lo) & (x < hi)).all(dim=1)
         order = torch.argsort((~interior).to(torch.int8), stable=True)
         self.x, self.v = self.x[order].contiguous(), self.v[order].contiguous()
