@@ -281,7 +281,9 @@ int ahip_last_max_degree(ahip_model *m);
 int ahip_last_heavy_centres(ahip_model *m, int *ncentres, long long *nedges);
 
 /* Diagnostic: single-wave self-test of the fused path's register-chain MFMA primitive,
- * out[32][N] = in[32][K] @ W[K][N] (W row-major f64, in/out f32 host buffers). */
+ * out[32][N] = in[32][K] @ W[K][N] (W row-major f64, in/out f32 host buffers).
+ * With AHIP_DEBUG_SPLIT=mix|ref in the environment and N == K: the f16x2 operand split alone, in its mixed-fma or its reference form; out receives
+ * 32 K words: the 16 K packed hi terms of the pairs (in[2 i], in[2 i + 1]), then their 16 K packed lo' terms.  W is not read. */
 int ahip_debug_fused_linear(int K, int N, const double *W, const float *in, float *out);
 
 /* Diagnostics of the device-wide primitives (csrc/prims.hip) and of the layer-at-a-time path's float32 GEMM (csrc/gemm.hip): host buffers in, host

@@ -282,15 +282,16 @@ enum { PH_GEOM = 0, PH_TB, PH_EMB, PH_ENV, PH_TP, PH_MIX, PH_LAT, PH_OUT, PH_BLA
 // the f32-input MFMA form or to the bf16x3 form (inputs are split into their three bf16 terms right here).
 // AR: arithmetic of the tile's linears: 0 = f32-input MFMA, 1 = bf16x3 (three-term split, float32-equivalent), 2 = tf32eq (two-term bf16 split),
 // 3 = f16x2 (two float16 terms, float32-equivalent inside float16's exponent range: fused_h.h)
-template <int AR> struct RingT {
+// MX: the f16x2 operand split in its mixed-precision-fma form (fused_h.h: split2_h), chosen per instance by k_fused.
+template <int AR, bool MX = false> struct RingT {
   int act = 1;                 // wave-uniform: 0 while the wave's 16 slots of the current tile hold no edge (its linears are skipped, see the tile loop)
   f32x4 f[AR != 0 ? 1 : RING];
   u32x4 b[AR == 0 ? 1 : (AR == 1 ? RINGB : AR == 2 ? RINGB2 : RINGH)];
 };
 // BR = false: the caller has tested ring.act itself, around a PAIR of one-step linears (see lin_mix).
 // jump: f16x2 only, see linear_h (the stream jump over a linear this wave will skip).
-template <int AR, int KT, int NT, bool ACC, int RPI, bool BR = true, class Epi>
-__device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in)[KT], f32x4 (&out)[NT], int v16, RingT<AR> &ring, Epi epi, int jump = 0) {
+template <int AR, int KT, int NT, bool ACC, int RPI, bool BR = true, class Epi, bool MX>
+__device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in)[KT], f32x4 (&out)[NT], int v16, RingT<AR, MX> &ring, Epi epi, int jump = 0) {
   if (BR && !ring.act) {             // (uniform) a wave without edges in this tile: no fragments, no MFMAs, no epilogue; finite outputs for the arithmetic around the linears
     if constexpr (!ACC) {
 #pragma unroll
@@ -302,7 +303,7 @@ __device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32
     static_assert(KT % 2 == 0, "K-steps are pairs of 16-feature tiles");
     Hop b[1][KT / 2], unused[1][NT / 2];
 #pragma unroll
-    for (int ks = 0; ks < KT / 2; ++ks) b[0][ks] = split_pair_h(in[2 * ks], in[2 * ks + 1]);
+    for (int ks = 0; ks < KT / 2; ++ks) b[0][ks] = split_pair_h<MX>(in[2 * ks], in[2 * ks + 1]);
     Epi ep[1] = {epi};
     linear_h<1, KT / 2, NT, ACC, false, (4 * RPI) % RINGH, Epi, true>(W, wp, b, reinterpret_cast<f32x4 (&)[1][NT]>(out), unused, v16, ring.b, ep, jump);
   } else if constexpr (AR != 0) {
@@ -321,25 +322,25 @@ __device__ __forceinline__ void lin(__amdgpu_buffer_rsrc_t W, int &wp, const f32
 // The three m components of an l = 1 row share ONE channel-mixing matrix: on the f16x2 arithmetic they go through the linear as three GROUPS that share every weight
 // fragment (linear_h<3, ...>: one fragment load, three B operands, three accumulator sets) instead of three passes over three copies of the matrix in the stream:
 // 8 KiB of fragments fewer per mixing block and direction and wave-tile.
-template <int RPI, bool BR = true, class Epi>
+template <int RPI, bool BR = true, class Epi, bool MX>
 __device__ __forceinline__ void lin_m3(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in0)[2], const f32x4 (&in1)[2], const f32x4 (&in2)[2], f32x4 (&out)[3][2], int v16,
-                                       RingT<3> &ring, Epi (&epi)[3], int jump = 0) {
+                                       RingT<3, MX> &ring, Epi (&epi)[3], int jump = 0) {
   if (BR && !ring.act) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) { out[q][0] = f32x4{0.f, 0.f, 0.f, 0.f}; out[q][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     return;
   }
   Hop b[3][1], unused[3][1];
-  b[0][0] = split_pair_h(in0[0], in0[1]); b[1][0] = split_pair_h(in1[0], in1[1]); b[2][0] = split_pair_h(in2[0], in2[1]);
+  b[0][0] = split_pair_h<MX>(in0[0], in0[1]); b[1][0] = split_pair_h<MX>(in1[0], in1[1]); b[2][0] = split_pair_h<MX>(in2[0], in2[1]);
   linear_h<3, 1, 2, false, false, (4 * RPI) % RINGH, Epi, true>(W, wp, b, out, unused, v16, ring.b, epi, jump);
 }
 // A channel mixing on the f16x2 arithmetic is two ONE-step linears (the l = 0 block, then lin_m3).  They share one `ring.act` branch: a region that consumes a whole
 // ring (two steps) leaves every slot at the age it had on entry, whichever way the branch went.  With a branch each, the path "first skipped, second taken" -- which
 // never runs, a wave is idle for a whole tile, but which the wait-count insertion has to merge -- presents the second linear's fragments as the youngest loads of the
 // queue, and its first products wait behind s_waitcnt vmcnt(3..2) for everything older.
-template <class Epi0, class Epi3>
+template <class Epi0, class Epi3, bool MX>
 __device__ __forceinline__ void lin_mix(__amdgpu_buffer_rsrc_t W, int &wp, const f32x4 (&in0)[2], const f32x4 (&in1)[2], const f32x4 (&in2)[2], const f32x4 (&in3)[2], f32x4 (&out0)[2],
-                                        f32x4 (&out)[3][2], int v16, RingT<3> &ring, Epi0 epi0, Epi3 (&epi)[3], int jump = 0) {
+                                        f32x4 (&out)[3][2], int v16, RingT<3, MX> &ring, Epi0 epi0, Epi3 (&epi)[3], int jump = 0) {
   if (!ring.act) {
     out0[0] = f32x4{0.f, 0.f, 0.f, 0.f}; out0[1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -453,7 +454,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_fused(FusedArgs A) {
     tprev = clock64();
   }
   float *const pk0 = lds.park[wave];
-  RingT<AR> ring;                              // the weight-fragment stream (see linear_s / linear_b)
+  // (the mixed-fma operand split, fused_h.h, where it leaves every instance's registers and scratch as they were: the 4-wave tiles of MLP width <= 64)
+  RingT<AR, AR == 3 && NW == 4 && WT == 4> ring;      // the weight-fragment stream (see linear_s / linear_b)
   int wp = A.o_stream;
   if constexpr (AR != 0) ring_prime_b(WB, wp, v16, ring.b);
   else ring_prime(WB, wp, v16, ring.f);
@@ -1732,6 +1734,16 @@ __global__ void __launch_bounds__(128) k_selftest_linear_h(const float *Wf, int 
     }
 }
 
+// The f16x2 operand split alone (fused_h.h: split2_h), pair i = (in[2 i], in[2 i + 1]): out[i] = the packed hi terms, out[npairs + i] = the packed lo' terms.
+template <bool MIX> __global__ void __launch_bounds__(256) k_split_probe(const float *in, unsigned *out, int npairs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= npairs) return;
+  unsigned h, l;
+  split2_h<MIX>(in[2 * i], in[2 * i + 1], h, l);
+  out[i] = h;
+  out[npairs + i] = l;
+}
+
 #endif   // AHIP_FUSED_PART == 0
 }  // namespace ahip
 
@@ -1751,6 +1763,23 @@ extern "C" int ahip_debug_fused_edges(ahip_model *mh, float *out, long long nedg
 
 extern "C" int ahip_debug_fused_linear(int K, int N, const double *W, const float *in, float *out) {
   try {
+    if (const char *sp = std::getenv("AHIP_DEBUG_SPLIT")) {
+      // the operand split alone: in[32 K] floats -> out[32 K] words, the 16 K packed hi terms, then the 16 K packed lo' terms; "mix" or "ref" (W is not read)
+      const std::string form(sp);
+      if (N != K || K < 1 || (form != "mix" && form != "ref")) return AHIP_ERR_UNSUPPORTED;
+      const int npairs = 16 * K;
+      float *din = nullptr;
+      unsigned *dout = nullptr;
+      AHIP_CHECK(hipMalloc((void **)&din, (size_t)2 * npairs * sizeof(float)));
+      AHIP_CHECK(hipMalloc((void **)&dout, (size_t)2 * npairs * sizeof(unsigned)));
+      AHIP_CHECK(hipMemcpy(din, in, (size_t)2 * npairs * sizeof(float), hipMemcpyHostToDevice));
+      if (form == "mix") hipLaunchKernelGGL((k_split_probe<true>), dim3((npairs + 255) / 256), dim3(256), 0, 0, din, dout, npairs);
+      else hipLaunchKernelGGL((k_split_probe<false>), dim3((npairs + 255) / 256), dim3(256), 0, 0, din, dout, npairs);
+      AHIP_CHECK(hipDeviceSynchronize());
+      AHIP_CHECK(hipMemcpy(out, dout, (size_t)2 * npairs * sizeof(unsigned), hipMemcpyDeviceToHost));
+      (void)hipFree(din); (void)hipFree(dout);
+      return 0;
+    }
     const char *ar = std::getenv("AHIP_FUSED_ARITH");
     const int nterm = (ar && std::string(ar) == "tf32eq") ? 2 : 3;
     const bool h2 = ar && std::string(ar) == "f16x2";

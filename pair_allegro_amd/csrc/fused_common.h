@@ -27,7 +27,7 @@ static constexpr int TCHUNK = 4;         // tiles per claim of the dynamic tile 
 
 // Switches that exist for timing experiments only and compute WRONG results (or drop a hazard pad) are refused outside an experiment build.
 #if (defined(ABL_NOROWS) || defined(ABL_NOW) || defined(AHIP_NO_STORE_PAD) || defined(ABL_NO_ENVSTAGE) || defined(ABL_NO_FTP) || defined(ABL_NO_LAT) || defined(ABL_NO_MIX) || \
-     defined(ABL_NOSYNC) || defined(ABL_NOREDUCE) || defined(ABL_NOROWST) || defined(ABL_NOROWLD) || defined(ABL_NOATOM) || defined(ABL_NOTBGATHER)) && !defined(AHIP_EXPERIMENT_SWITCHES)
+     defined(ABL_NOSYNC) || defined(ABL_NOREDUCE) || defined(ABL_NOROWST) || defined(ABL_NOROWLD) || defined(ABL_NOATOM) || defined(ABL_NOTBGATHER) || defined(ABL_NOSPLIT)) &&!defined(AHIP_EXPERIMENT_SWITCHES)
 #error "ABL_* / AHIP_NO_STORE_PAD are timing-experiment switches (wrong results): add -DAHIP_EXPERIMENT_SWITCHES, never in the product build"
 #endif
 

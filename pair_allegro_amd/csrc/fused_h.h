@@ -36,8 +36,16 @@ constexpr int lin_frags_h(int KT, int NT) { return 4 * (NT / 2) * (KT / 2); }
 __device__ __forceinline__ f32x4 mfma_h(u32x4 a, u32x4 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
-// two f32 -> packed f16 terms (low half = first value)
-__device__ __forceinline__ void split2_h(float v0, float v1, unsigned &hi, unsigned &lo) {
+// two f32 -> packed f16 terms (low half = first value).  split2_h_ref is the round-5 expression: convert, convert back, subtract, scale, convert
+// (v_cvt_pk_f16_f32, v_cvt_f32_f16 twice -- one of them an SDWA form --, v_pk_add_f32, v_pk_mul_f32, v_cvt_pk_f16_f32).  split2_h<true> (round 9)
+// forms the remainder v - hi with the mixed-precision fma, which reads hi as a float16 half: exact, as the float32 subtraction of the converted-back value
+// was, so the same bits without the two conversions back and without the packed subtraction; the scale is two plain v_mul_f32.  Six instructions per pair
+// either way -- the time is in WHICH ones: on the 1 M-atom Si box 34.02 ms per step with the reference form, 33.58 with this one, 33.74 with v_pk_mul_f32
+// for the scale (form 2), 34.09 with v_fma_mixlo_f16 / v_fma_mixhi_f16 producing lo' directly (form 1: five instructions, the slowest), 34.09 with plain
+// conversions, subtractions and multiplies (form 4: eight).  Same hi and lo' bits as split2_h_ref for every finite input in every form
+// (tests/test_gpu_fused_valu_diet.py sweeps forms 3 and ref through k_split_probe).  Inline assembly: the compiler folds fma(x, -1, v) back into the
+// subtraction it has no mixed form for.  The "s" operand of form 1 is the 2^11 (no literal in a VOP3P encoding).
+__device__ __forceinline__ void split2_h_ref(float v0, float v1, unsigned &hi, unsigned &lo) {
   const f32x2 v = {v0, v1};
   const f16x2 h = __builtin_convertvector(v, f16x2);
   const f32x2 r = (v - __builtin_convertvector(h, f32x2)) * H_LO_SCALE;
@@ -45,13 +53,50 @@ __device__ __forceinline__ void split2_h(float v0, float v1, unsigned &hi, unsig
   hi = __builtin_bit_cast(unsigned, h);
   lo = __builtin_bit_cast(unsigned, l);
 }
-__device__ __forceinline__ Hop split_pair_h(const f32x4 &t0, const f32x4 &t1) {
+template <bool MIX> __device__ __forceinline__ void split2_h(float v0, float v1, unsigned &hi, unsigned &lo) {
+#if defined(ABL_NOSPLIT)      // timing experiment only (results are wrong): what the split's VALU instructions are worth on the wave's chain
+  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0, v1}, f16x2));
+  lo = 0u;
+#else
+  if constexpr (!MIX) {
+    split2_h_ref(v0, v1, hi, lo);
+  } else {
+    const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0, v1}, f16x2));
+    unsigned l;
+#ifndef AHIP_SPLIT_FORM
+#define AHIP_SPLIT_FORM 3                          // experiments: 1, 2, 4 = the forms measured against it (above)
+#endif
+#if AHIP_SPLIT_FORM == 4
+    const f16x2 hh = __builtin_bit_cast(f16x2, h);
+    const float r0 = (v0 - (float)hh[0]) * H_LO_SCALE, r1 = (v1 - (float)hh[1]) * H_LO_SCALE;
+    l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, f16x2));
+#else
+    float r0, r1;
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h), "v"(v0));
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h), "v"(v1));
+#if AHIP_SPLIT_FORM == 1
+    const float sc = H_LO_SCALE;
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(l) : "v"(r0), "s"(sc));
+    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l) : "v"(r1), "s"(sc));
+#elif AHIP_SPLIT_FORM == 2
+    l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1} * H_LO_SCALE, f16x2));
+#else
+    const float q0 = r0 * H_LO_SCALE, q1 = r1 * H_LO_SCALE;
+    l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{q0, q1}, f16x2));
+#endif
+#endif
+    hi = h;
+    lo = l;
+  }
+#endif
+}
+template <bool MIX = false> __device__ __forceinline__ Hop split_pair_h(const f32x4 &t0, const f32x4 &t1) {
   Hop b;
   unsigned h, l;
-  split2_h(t0[0], t0[1], h, l); b.hi[0] = h; b.lo[0] = l;
-  split2_h(t0[2], t0[3], h, l); b.hi[1] = h; b.lo[1] = l;
-  split2_h(t1[0], t1[1], h, l); b.hi[2] = h; b.lo[2] = l;
-  split2_h(t1[2], t1[3], h, l); b.hi[3] = h; b.lo[3] = l;
+  split2_h<MIX>(t0[0], t0[1], h, l); b.hi[0] = h; b.lo[0] = l;
+  split2_h<MIX>(t0[2], t0[3], h, l); b.hi[1] = h; b.lo[1] = l;
+  split2_h<MIX>(t1[0], t1[1], h, l); b.hi[2] = h; b.lo[2] = l;
+  split2_h<MIX>(t1[2], t1[3], h, l); b.hi[3] = h; b.lo[3] = l;
   return b;
 }
 

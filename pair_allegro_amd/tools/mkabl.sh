@@ -15,7 +15,7 @@ case $obj in
   *) echo "unknown object $obj"; exit 1 ;;
 esac
 [ -n "$ABL_SPEC" ] && SPEC="$ABL_SPEC"      # ABL_SPEC=... replaces the per-object options of the Makefile (e.g. to drop an -mllvm flag)
-ALL="allegro_hip.o prims.o neigh.o edges.o gemm.o fused.o fused_bf.o fused_h.o fused_lx.o fused_lx2.o comm.o model_io.o"
+ALL="allegro_hip.o prims.o neigh.o edges.o gemm.o fused.o fused_bf.o fused_h.o fused_hr.o fused_hm.o fused_hq.o fused_lx.o fused_lx_r.o fused_lx_w.o fused_lx_m.o fused_lx_q.o fused_lx2.o fused_lx2_r.o fused_lx2_q.o fused_lx2_m.o comm.o model_io.o"      # (the Makefile's OBJS)
 for v in "$@"; do
   name=${v%%:*}; flags=${v#*:}
   (
