@@ -359,13 +359,49 @@ int ahip_borders_cell_dev(ahip_model *m, int nlocal, const double *x_dev, const 
  *   f      [natoms][3] and eatom [natoms] (or NULL) are WRITTEN, not accumulated, in the caller's atom order (ghost forces already added to their sources)
  *   eng    energy;  virial [6] or NULL: xx,yy,zz,xy,xz,yz in LAMMPS order and sign, as ahip_compute
  * Steps: upload, ahip_wrap_cell_dev, ahip_borders_cell_dev (retried with a larger capacity when needed), ahip_build_neighbors_dev over the bounding box of the
- * cell's eight corners +- rc, the evaluation of ahip_compute_dev, ghost forces added to their sources, download.  Nothing is reused between calls.  A model of more
+ * cell's eight corners +- rc, the evaluation of ahip_compute_dev, ghost forces added to their sources, download.  Nothing is reused between calls (ahip_compute_cell_reuse below does that).  A model of more
  * than 16 types takes its active set from the types present.  ahip_last_path, ahip_get_edges and the other accessors keep working afterwards; their rows are the
  * atoms followed by the ghosts, and ahip_last_cell_rows maps every row to its atom (nrows = natoms + ghosts; row_atom: room for nrows entries, or NULL for the
  * count alone). */
 int ahip_compute_cell(ahip_model *m, int natoms, const double *x, const int *mtype, const double *cell, const int *pbc, double skin, double *f,
                       double *eatom, double *eng, double *virial);
 int ahip_last_cell_rows(ahip_model *m, int *nrows, long long *row_atom);
+
+/* ahip_compute_cell for a caller that hands over nearly the same structure again and again (MD in Python, a relaxation, NEB images, a variable-cell optimiser):
+ * the model keeps the ghosts and the neighbor list of one call and the next call runs on them when that is provably safe.  Arguments, output contract, argument
+ * errors and the handling of the float16-range alarm are those of ahip_compute_cell; *rebuilt (may be NULL) receives 1 when the call built ghosts and list
+ * (exactly the steps of ahip_compute_cell), 0 when it ran on the held ones.  Opt-in: ahip_compute_cell itself keeps nothing.
+ * Held after a rebuild: the cell A0, the wrapped atom positions xhold, per ghost its source atom and its integer image n (recovered on the device from the
+ * shifts as round(shift . A0^-1)), the installed list, and host copies of mtype, pbc, skin and natoms.
+ * A call tries the held list when one exists and is still the installed list, natoms, every mtype[i], pbc and skin equal the held ones, and skin > 0 (with
+ * skin = 0 every call rebuilds).  It uploads x and rewrites every row on the device (one kernel, one thread per row): with A the cell of THIS call,
+ *     t = (x_a - xhold_a) . A^-1,   k_d = floor(t_d + 0.5) on periodic axes, 0 on open ones      (the caller may have wrapped the atom in between, or not)
+ *     atom row a = x_a - k . A,     ghost row (a, n) = x_a - k . A + n . A
+ * so every ghost is an exact periodic image in the new cell.  The largest |x_a - k . A - xhold_a| = U comes back in one 4-byte read-back (squared, in float32,
+ * rounded up).  Then the evaluation of ahip_compute_dev runs on the refreshed rows with the held list; the edge build filters the list at the model's own
+ * cutoffs in every call, as it does for LAMMPS' skin-inflated list.  One synchronisation for U and the final one, where a rebuild has three.
+ * CRITERION.  rc = largest model cutoff + skin; h0_d the heights of the HELD cell; M_d = ceil(rc / h0_d) + 1; g_d = |a_d - a0_d| the Euclidean length of the
+ * change of lattice vector d; sums and the minimum over the periodic axes only.  The held list is used iff
+ *     2 U + sum_d M_d g_d <= skin      and      sum_d g_d <= min_d h0_d
+ * (an unchanged cell: the classic U <= skin / 2; no periodic axis: 2 U <= skin), else the call rebuilds inside itself.
+ * Why that is enough: take atom i and image n' of atom j at held distance D0.  Its distance has changed by at most 2 U + sum_d |n'_d| g_d.  The held positions
+ * are wrapped, so D0 >= (|n'_d| - 1) h0_d for every d.  If |n'_d| <= M_d on every axis, the change is <= skin < D0 - r_max whenever D0 > rc.  Otherwise let
+ * k = max_d (|n'_d| - M_d) >= 1: then D0 >= rc + k h0 on that axis, while the change is <= skin + k sum_d g_d <= skin + k min_d h0_d.  Either way a pair that
+ * was outside the held list (D0 > rc) is still outside r_max.
+ * The hold ends with ahip_cell_reuse_reset; with anything that installs another list or other rows (ahip_neigh_update*, ahip_build_neighbors_dev,
+ * ahip_borders_*_dev, ahip_compute_cell, an ahip_compute_cells with atoms); with any successful ahip_set_option; and with an ahip_compute_cell_reuse that fails
+ * behind a launch.  A call refused for its arguments (a singular or non-finite cell included: AHIP_ERR_ARG before any launch) leaves it as it was.
+ * ahip_last_cell_rows, ahip_get_edges, ahip_last_path and the other accessors keep working after a call on the held list: the rows are the held rows, the edges
+ * those of this evaluation.
+ * ahip_cell_reuse_stats: successful ahip_compute_cell_reuse calls, and how many of them rebuilt, since the model was loaded or ahip_cell_reuse_reset was called
+ * (either pointer may be NULL).
+ * Measured on one MI355X (tools/cell_reuse_cost.py, profiles/cell_reuse_cost.txt): a 200-call random walk of 0.02 A per call at skin 1.0 A, float32 model S,
+ * host clock per call: 64-atom Si cell 198.7 us against 393.0 us through ahip_compute_cell (5 calls rebuilt), 10 648-atom Si box 733.7 us against 1019.5 us (7 rebuilt).
+ * A variant that enqueues the evaluation before U is known and reads both back in one synchronisation is left as a follow-up. */
+int ahip_compute_cell_reuse(ahip_model *m, int natoms, const double *x, const int *mtype, const double *cell, const int *pbc, double skin, double *f,
+                            double *eatom, double *eng, double *virial, int *rebuilt);
+int ahip_cell_reuse_reset(ahip_model *m);
+int ahip_cell_reuse_stats(ahip_model *m, long long *calls, long long *rebuilds);
 
 /* A BATCH of structures in one call: what ahip_compute_cell computes for each of `nstruct` structures alone, with one upload, one ghost build, one neighbor
  * list and one evaluation for all of them (a data set of small cells is launch- and synchronisation-bound one structure at a time).  HOST pointers.

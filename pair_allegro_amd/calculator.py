@@ -5,6 +5,7 @@
     calc = Calculator("model.nequip.pth")
     out = calc.compute(cell, positions, symbols)          # out["energy"], out["forces"], out["stress"]
     outs = calc.compute_many([(cell, positions, symbols), ...])      # a data set: one library call for many structures (ahip_compute_cells)
+    calc = Calculator("model.nequip.pth", skin=1.0, reuse=True)      # a trajectory: ghosts and neighbor list are kept from call to call (ahip_compute_cell_reuse)
 
 Any cell works: triclinic, thinner than the cutoff (several images per direction), open axes.  No ASE import: an ASE calculator is three lines
 around `compute(atoms.cell.array, atoms.positions, atoms.get_chemical_symbols(), atoms.pbc)`.
@@ -19,19 +20,28 @@ from . import capi
 
 
 class Calculator:
-    def __init__(self, model_path: str, device: int = 0, lib: Optional[capi.Library] = None, options: Optional[dict] = None, skin: float = 0.0):
+    def __init__(self, model_path: str, device: int = 0, lib: Optional[capi.Library] = None, options: Optional[dict] = None, skin: float = 0.0,
+                 reuse: bool = False):
         """`options`: library options by name (include/allegro_hip.h: ahip_set_option), e.g. {"precision": "float64"}.  `skin` >= 0 only inflates the ghost
-        shell and the neighbor list; the results do not depend on it."""
+        shell and the neighbor list; the results do not depend on it.  `reuse`: `compute` keeps ghosts and list between calls and rebuilds them only when
+        atoms or cell have moved too far for the skin (needs skin > 0; MD, relaxations, variable-cell optimisers)."""
         if skin < 0:
             raise ValueError("skin must be >= 0")
+        if reuse and not skin > 0:
+            raise ValueError("reuse=True needs skin > 0: the skin is what the atoms may move through before the list is rebuilt")
         self.model = capi.Model(model_path, device, lib)
         for k, v in (options or {}).items():
             self.model.set_option(k, v)
         self.skin = float(skin)
+        self.reuse = bool(reuse)
         self.type_names = list(self.model.type_names)
 
     def close(self) -> None:
         self.model.close()
+
+    def reset(self) -> None:
+        """drop the list held by reuse=True: the next `compute` rebuilds it"""
+        self.model.cell_reuse_reset()
 
     def model_types(self, symbols: Sequence[str]) -> np.ndarray:
         """chemical symbols -> model types through the model's type_names; an unknown symbol is a ValueError that names it"""
@@ -46,23 +56,33 @@ class Calculator:
 
         Returns a dict: energy; forces [n][3]; atomic_energy [n]; virial [6] (xx, yy, zz, xy, xz, yz in LAMMPS order and sign); stress [3][3] =
         -virial matrix / volume = (1 / V) dE / d(strain), None unless all three axes are periodic; info: path (kernel family and arithmetic), nghost,
-        nedges, row_atom (the atom index of every row -- atoms, then ghost images -- the edge accessors of the model refer to).
+        nedges, row_atom (the atom index of every row -- atoms, then ghost images -- the edge accessors of the model refer to), and with reuse=True
+        rebuilt (whether this call built ghosts and list).
 
-        Nothing is kept between calls: every call wraps, builds the ghost images and the neighbor list again, even for positions that barely moved.
-        Reusing lists across calls (a skin with a displacement check, as the MD driver does) is left to a later change."""
+        By default nothing is kept between calls: every call wraps, builds the ghost images and the neighbor list again, even for positions that barely moved.
+        With reuse=True the model holds them (ahip_compute_cell_reuse): a call refreshes the rows on the device and rebuilds only when the largest
+        displacement U since the hold and the change of the lattice vectors fail 2 U + sum_d M_d |a_d - a0_d| <= skin (include/allegro_hip.h states the
+        criterion and why it is sufficient).  The cell may change between calls; a change of the species, the atom count, pbc, or any other call on the
+        model that installs a list (compute_many among them) makes the next call rebuild.  The results are those of the default path."""
         cell = np.asarray(cell, dtype=np.float64)
         pos = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
         if len(symbols) != len(pos):
             raise ValueError("positions and symbols differ in length")
         pbc = tuple(bool(p) for p in pbc)
         mt = self.model_types(symbols)
-        energy, forces, eatom, vir = self.model.compute_cell(pos, mt, cell, pbc, self.skin)
+        rebuilt = None
+        if self.reuse:
+            energy, forces, eatom, vir, rebuilt = self.model.compute_cell_reuse(pos, mt, cell, pbc, self.skin)
+        else:
+            energy, forces, eatom, vir = self.model.compute_cell(pos, mt, cell, pbc, self.skin)
         rows = self.model.last_cell_rows()
         stress = None
         if all(pbc):
             vm = np.array([[vir[0], vir[3], vir[4]], [vir[3], vir[1], vir[5]], [vir[4], vir[5], vir[2]]])
             stress = -vm / abs(np.linalg.det(cell))
         info = dict(path=self.model.last_path, nghost=int(len(rows) - len(pos)), nedges=self.model.nedges(), row_atom=rows)
+        if self.reuse:
+            info["rebuilt"] = rebuilt
         return dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, info=info)
 
     def compute_many(self, structures: Sequence, max_atoms: int = 1 << 20) -> list:

@@ -41,6 +41,7 @@ SYMBOLS = [
     "ahip_wrap_cell_dev", "ahip_borders_cell_dev", "ahip_compute_cell", "ahip_last_cell_rows",
     "ahip_compute_cells", "ahip_last_cells_ghosts",
     "ahip_comm_migrate_cell", "ahip_comm_borders_cell",
+    "ahip_compute_cell_reuse", "ahip_cell_reuse_reset", "ahip_cell_reuse_stats",
 ]
 
 
@@ -386,6 +387,38 @@ class Model:
         self.L.check(self.L.lib.ahip_compute_cell(self.h, n, _p(x, C.c_double), _p(mt, C.c_int), _p(c, C.c_double), _p(p, C.c_int), float(skin),
                                                    _p(f, C.c_double), _p(ea, C.c_double), C.byref(eng), _p(vir, C.c_double)))
         return eng.value, f, ea, vir
+
+    def compute_cell_reuse(self, x: np.ndarray, mtype: np.ndarray, cell, pbc=(True, True, True), skin: float = 1.0, want_eatom: bool = True):
+        """compute_cell that keeps ghosts and neighbor list from call to call (ahip_compute_cell_reuse) and rebuilds them only when the criterion of
+        include/allegro_hip.h says the held list may miss a pair.  Returns (energy, forces, atomic energies or None, virial [6], rebuilt)."""
+        c, p = self._cell_args(cell, pbc)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        mt = np.ascontiguousarray(mtype, dtype=np.int32).reshape(-1)
+        if len(mt) != len(x):
+            raise ValueError("positions and types differ in length")
+        n = len(x)
+        f = np.zeros((n, 3))
+        ea = np.zeros(n) if want_eatom else None
+        eng = C.c_double(0)
+        vir = np.zeros(6)
+        rebuilt = C.c_int(-1)
+        self.L.lib.ahip_compute_cell_reuse.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_double,
+                                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]
+        self.L.check(self.L.lib.ahip_compute_cell_reuse(self.h, n, _p(x, C.c_double), _p(mt, C.c_int), _p(c, C.c_double), _p(p, C.c_int), float(skin),
+                                                         _p(f, C.c_double), _p(ea, C.c_double), C.byref(eng), _p(vir, C.c_double), C.byref(rebuilt)))
+        return eng.value, f, ea, vir, bool(rebuilt.value)
+
+    def cell_reuse_reset(self) -> None:
+        """drop the held list (and the counters): the next compute_cell_reuse rebuilds"""
+        self.L.lib.ahip_cell_reuse_reset.argtypes = [C.c_void_p]
+        self.L.check(self.L.lib.ahip_cell_reuse_reset(self.h))
+
+    def cell_reuse_stats(self):
+        """(successful compute_cell_reuse calls, how many of them rebuilt) since the model was loaded or cell_reuse_reset was called"""
+        a = C.c_longlong(0); b = C.c_longlong(0)
+        self.L.lib.ahip_cell_reuse_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        self.L.check(self.L.lib.ahip_cell_reuse_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def last_cell_rows(self) -> np.ndarray:
         """atom index of every row (atoms, then ghosts) of the last compute_cell (ahip_last_cell_rows)"""

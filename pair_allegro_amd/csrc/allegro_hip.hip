@@ -27,6 +27,7 @@
 
 #include "engine.h"
 #include "generic_engine.h"
+#include "cell_geom.h"
 
 using namespace ahip;
 
@@ -253,7 +254,7 @@ void ahip_model_free(ahip_model *m) {
   for (DevBuf *b : {&m->b_flagwork, &m->b_ilist, &m->b_nloff, &m->b_nlj, &m->b_x, &m->b_ftype, &m->b_mtype, &m->b_f, &m->b_eatom,
                     &m->b_engvir, &m->b_cutsq, &m->b_cnt, &m->b_eoff, &m->b_eii, &m->b_ej, &m->b_rvec, &m->b_ett, &m->b_partial,
                     &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom,
-                    &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist, &m->c_x, &m->c_mtype, &m->c_f, &m->c_eatom, &m->c_src, &m->c_shift, &m->c_engvir, &m->c_in, &m->c_xp, &m->c_out})
+                    &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist, &m->c_x, &m->c_mtype, &m->c_f, &m->c_eatom, &m->c_src, &m->c_shift, &m->c_engvir, &m->c_in, &m->c_xp, &m->c_out, &m->r_xin, &m->r_xhold, &m->r_img, &m->r_disp})
     b->release();
   for (auto &t : m->slots) for (auto &e : t.ring) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (hipEvent_t e : m->f_events) (void)hipEventDestroy(e);
@@ -337,6 +338,7 @@ int ahip_set_option(ahip_model *m, const char *key, const char *value) {
     } else if (k == "timing") {
       m->timing = (v == "1" || v == "on" || v == "true");
     } else throw ArgError("unknown option '" + k + "'");
+    ++m->list_serial;                        // an option may change what an evaluation runs on: a list held by ahip_compute_cell_reuse is built again
   });
 }
 
@@ -498,6 +500,7 @@ static void install_list_host(ahip_model *m, int inum, int nall) {
   m->d_nloff = m->b_nloff.as<int>();
   m->d_nlj = m->b_nlj.as<int>();
   m->inum = inum; m->nall = nall; m->nneigh = (long long)nn; m->have_list = true;
+  ++m->list_serial;
   m->max_list_row = 0;
   for (int ii = 0; ii < inum; ++ii) m->max_list_row = std::max(m->max_list_row, m->h_off32[ii + 1] - m->h_off32[ii]);
 }
@@ -574,6 +577,7 @@ int ahip_neigh_update_dev(ahip_model *m, int inum, int nall, const int *ilist_de
     if (inum > 0 && (!ilist_dev || !offsets_dev)) throw ArgError("ahip_neigh_update_dev: NULL list pointer");
     m->d_ilist = ilist_dev; m->d_nloff = offsets_dev; m->d_nlj = neigh_dev;
     m->inum = inum; m->nall = nall; m->nneigh = nneigh_total; m->have_list = true;
+    ++m->list_serial;
     // longest row: bounds the degree of every centre until the next hand-over, which is what lets the per-step calls run without a read-back
     AHIP_CHECK(hipSetDevice(m->device));
     m->max_list_row = edges_max_row(*m, inum, offsets_dev);
@@ -1391,86 +1395,164 @@ static void rethrow_code(int rc) {
   throw HipError(err);
 }
 
+// what ahip_compute_cell and ahip_compute_cell_reuse refuse alike, before anything is written or launched; returns the model types present
+static std::vector<int> cell_check_args(const ahip_model *m, const std::string &who, int natoms, const double *x, const int *mtype, const double *cell, const int *pbc,
+                                        double skin, const double *f, const double *eng) {
+  if (natoms < 0 || !cell || !pbc || !eng || (natoms > 0 && (!x || !mtype || !f))) throw ArgError(who + ": bad argument");
+  if (!(skin >= 0.0) || !std::isfinite(skin)) throw ArgError(who + ": skin must be a finite number >= 0");
+  const int T = m->hm.num_types;
+  std::vector<int> present;
+  for (int i = 0; i < natoms; ++i) {
+    if (mtype[i] < 0 || mtype[i] >= T)
+      throw ArgError(who + ": atom " + std::to_string(i) + " has model type " + std::to_string(mtype[i]) + ", outside the model's " + std::to_string(T) + " types");
+    present.push_back(mtype[i]);
+  }
+  std::sort(present.begin(), present.end());
+  present.erase(std::unique(present.begin(), present.end()), present.end());
+  return present;
+}
+
+// The evaluation on the rows of c_x / c_mtype with the installed list, ghost forces folded home, one synchronisation, the downloads.
+// (twice at most: an evaluation whose f16x2 kernels raise the float16-range alarm under fused_arith=auto is repeated on the float32 instance, as in ahip_compute)
+static void cell_evaluate(ahip_model *m, const std::string &who, int natoms, int ng, double *f, double *eatom, double *eng, double *virial, hipStream_t s) {
+  const int nall = natoms + ng;
+  for (int attempt = 0;; ++attempt) {
+    AHIP_CHECK(hipMemsetAsync(m->c_f.p, 0, (size_t)std::max(nall, 1) * 3 * sizeof(double), s));
+    AHIP_CHECK(hipMemsetAsync(m->c_eatom.p, 0, (size_t)std::max(nall, 1) * sizeof(double), s));
+    rethrow_code(ahip_compute_dev(m, natoms, ng, m->c_x.as<double>(), m->c_mtype.as<int>(), nullptr, m->c_f.as<double>(), m->c_eatom.as<double>(),
+                                  m->c_engvir.as<double>(), s));
+    comm_scatter_local(ng, natoms, m->c_src.as<long long>(), m->c_f.as<double>(), s);      // ghost forces go home (newton on)
+    AHIP_CHECK(hipGetLastError());
+    AHIP_CHECK(hipStreamSynchronize(s));
+    if (const int bad = inactive_take(*m)) throw ArgError(who + ": " + inactive_message(*m, bad, "this evaluation") + " (nothing was written to f)");
+    if (alarm_take(*m)) {
+      if (arith_may_degrade(*m) && attempt == 0) {
+        arith_degrade(*m, "an activation left float16's range (non-finite edge gradient on the f16x2 arithmetic); the evaluation was repeated");
+        continue;
+      }
+      throw StateError("fused_arith=f16x2: an edge gradient was not finite (an activation left float16's range, or the input was not finite): the forces of this "
+                       "evaluation are invalid and were not written to f; set option fused_arith=f32 (or auto) for this model");
+    }
+    break;
+  }
+  double ev[7];
+  copy_d2h(ev, m->c_engvir.p, 7 * sizeof(double));
+  if (natoms > 0) {
+    copy_d2h(f, m->c_f.p, (size_t)natoms * 3 * sizeof(double));
+    if (eatom) copy_d2h(eatom, m->c_eatom.p, (size_t)natoms * sizeof(double));
+  }
+  *eng = ev[0];
+  if (virial) for (int k = 0; k < 6; ++k) virial[k] = ev[1 + k];
+}
+
+// ahip_compute_cell, and the rebuild path of ahip_compute_cell_reuse: upload, wrap, ghosts, list, evaluation, download.  Returns the number of ghosts.
+static int cell_rebuild(ahip_model *m, const std::string &who, const std::vector<int> &present, int natoms, const double *x, const int *mtype, const double *cell,
+                        const int *pbc, double skin, double *f, double *eatom, double *eng, double *virial) {
+  const double rc = *std::max_element(m->rcut_model_host.begin(), m->rcut_model_host.end()) + skin;
+  AHIP_CHECK(hipSetDevice(m->device));
+  hipStream_t s = nullptr;
+  *eng = 0;
+  if (virial) for (int k = 0; k < 6; ++k) virial[k] = 0;
+  m->hold.serial = 0;                         // the rows of a held list are overwritten from here on
+  // upload, wrap, ghosts: rows [0, natoms) of c_x / c_mtype are the atoms, the images go behind them.  The first capacity is the last call's count when the
+  // system has the same size, else none (the call then only counts); a grown buffer loses its content, so the one retry uploads again
+  int cap = natoms == m->cell_natoms ? m->cell_nghost_last + m->cell_nghost_last / 8 : 0, ng = 0;
+  m->cell_src_host.clear(); m->cell_natoms = natoms;
+  double lo[3], hi[3];
+  cell_bounding_box(cell, rc + 1e-6, lo, hi);
+  for (;;) {
+    const size_t rows = (size_t)natoms + (size_t)cap;
+    m->c_x.reserve(std::max<size_t>(rows, 1) * 3 * sizeof(double));
+    m->c_mtype.reserve(std::max<size_t>(rows, 1) * sizeof(int));
+    m->c_src.reserve(std::max<size_t>((size_t)cap, 1) * sizeof(long long));
+    m->c_shift.reserve(std::max<size_t>((size_t)cap, 1) * 3 * sizeof(double));
+    if (natoms > 0) {
+      copy_h2d(m->c_x.p, x, (size_t)natoms * 3 * sizeof(double));
+      copy_h2d(m->c_mtype.p, mtype, (size_t)natoms * sizeof(int));
+    }
+    wrap_cell(*m, natoms, m->c_x.as<double>(), cell, pbc, s);
+    ng = borders_cell(*m, natoms, m->c_x.as<double>(), m->c_mtype.as<int>(), cell, pbc, rc, cap, m->c_x.as<double>() + 3 * (size_t)natoms,
+                      m->c_mtype.as<int>() + natoms, m->c_src.as<long long>(), m->c_shift.as<double>(), s);
+    if (ng <= cap) break;
+    cap = ng;
+  }
+  m->cell_nghost_last = ng;
+  if ((long long)natoms + ng > 2147483647LL) throw ArgError(who + ": atoms + ghosts exceed 2^31 - 1 rows");
+  const int nall = natoms + ng;
+  m->cell_src_host.resize((size_t)ng);
+  if (ng > 0) copy_d2h(m->cell_src_host.data(), m->c_src.p, (size_t)ng * sizeof(long long));
+  m->active_mapped = present;               // a model of more than 16 types runs on the types present (run_model: resolve_active)
+  neigh_build(*m, natoms, nall, m->c_x.as<double>(), lo, hi, rc, s);
+  m->c_f.reserve((size_t)std::max(nall, 1) * 3 * sizeof(double));
+  m->c_eatom.reserve((size_t)std::max(nall, 1) * sizeof(double));
+  m->c_engvir.reserve(8 * sizeof(double));
+  cell_evaluate(m, who, natoms, ng, f, eatom, eng, virial, s);
+  return ng;
+}
+
 int ahip_compute_cell(ahip_model *m, int natoms, const double *x, const int *mtype, const double *cell, const int *pbc, double skin, double *f,
                       double *eatom, double *eng, double *virial) {
   return guarded([&] {
     require_model(m);
-    if (natoms < 0 || !cell || !pbc || !eng || (natoms > 0 && (!x || !mtype || !f))) throw ArgError("ahip_compute_cell: bad argument");
-    if (!(skin >= 0.0) || !std::isfinite(skin)) throw ArgError("ahip_compute_cell: skin must be a finite number >= 0");
-    const int T = m->hm.num_types;
-    std::vector<int> present;
-    for (int i = 0; i < natoms; ++i) {
-      if (mtype[i] < 0 || mtype[i] >= T)
-        throw ArgError("ahip_compute_cell: atom " + std::to_string(i) + " has model type " + std::to_string(mtype[i]) + ", outside the model's " + std::to_string(T) + " types");
-      present.push_back(mtype[i]);
-    }
-    std::sort(present.begin(), present.end());
-    present.erase(std::unique(present.begin(), present.end()), present.end());
-    const double rc = *std::max_element(m->rcut_model_host.begin(), m->rcut_model_host.end()) + skin;
+    const std::vector<int> present = cell_check_args(m, "ahip_compute_cell", natoms, x, mtype, cell, pbc, skin, f, eng);
+    cell_rebuild(m, "ahip_compute_cell", present, natoms, x, mtype, cell, pbc, skin, f, eatom, eng, virial);
+  });
+}
+
+int ahip_compute_cell_reuse(ahip_model *m, int natoms, const double *x, const int *mtype, const double *cell, const int *pbc, double skin, double *f,
+                            double *eatom, double *eng, double *virial, int *rebuilt) {
+  return guarded([&] {
+    require_model(m);
+    const std::string who = "ahip_compute_cell_reuse";
+    const std::vector<int> present = cell_check_args(m, who, natoms, x, mtype, cell, pbc, skin, f, eng);
+    (void)cell_geometry(who.c_str(), cell, pbc, 1.0);      // a singular or non-finite cell is refused here, with the hold as it was
+    const Model::CellHold &h = m->hold;
+    bool held = skin > 0.0 && h.serial != 0 && h.serial == m->list_serial && natoms == h.natoms && skin == h.skin;
+    for (int d = 0; held && d < 3; ++d) held = (pbc[d] != 0) == (h.pbc[d] != 0);
+    held = held && std::equal(mtype, mtype + natoms, h.mtype.begin());
+    // Whatever fails from here on fails behind a launch and leaves nothing held; a success restores the hold or replaces it.
+    const unsigned long long serial = h.serial;
+    m->hold.serial = 0;
     AHIP_CHECK(hipSetDevice(m->device));
     hipStream_t s = nullptr;
-    *eng = 0;
-    if (virial) for (int k = 0; k < 6; ++k) virial[k] = 0;
-    // upload, wrap, ghosts: rows [0, natoms) of c_x / c_mtype are the atoms, the images go behind them.  The first capacity is the last call's count when the
-    // system has the same size, else none (the call then only counts); a grown buffer loses its content, so the one retry uploads again
-    int cap = natoms == m->cell_natoms ? m->cell_nghost_last + m->cell_nghost_last / 8 : 0, ng = 0;
-    m->cell_src_host.clear(); m->cell_natoms = natoms;
-    double lo[3], hi[3];
-    cell_bounding_box(cell, rc + 1e-6, lo, hi);
-    for (;;) {
-      const size_t rows = (size_t)natoms + (size_t)cap;
-      m->c_x.reserve(std::max<size_t>(rows, 1) * 3 * sizeof(double));
-      m->c_mtype.reserve(std::max<size_t>(rows, 1) * sizeof(int));
-      m->c_src.reserve(std::max<size_t>((size_t)cap, 1) * sizeof(long long));
-      m->c_shift.reserve(std::max<size_t>((size_t)cap, 1) * 3 * sizeof(double));
-      if (natoms > 0) {
-        copy_h2d(m->c_x.p, x, (size_t)natoms * 3 * sizeof(double));
-        copy_h2d(m->c_mtype.p, mtype, (size_t)natoms * sizeof(int));
+    if (held && cell_hold_refresh(*m, x, cell, s)) {
+      *eng = 0;
+      if (virial) for (int k = 0; k < 6; ++k) virial[k] = 0;
+      if (m->cell_natoms != natoms || (int)m->cell_src_host.size() != h.nghost) {      // (a batch without atoms in between has reset what ahip_last_cell_rows reports)
+        m->cell_natoms = natoms; m->cell_nghost_last = h.nghost;
+        m->cell_src_host.resize((size_t)h.nghost);
+        if (h.nghost > 0) copy_d2h(m->cell_src_host.data(), m->c_src.p, (size_t)h.nghost * sizeof(long long));
       }
-      wrap_cell(*m, natoms, m->c_x.as<double>(), cell, pbc, s);
-      ng = borders_cell(*m, natoms, m->c_x.as<double>(), m->c_mtype.as<int>(), cell, pbc, rc, cap, m->c_x.as<double>() + 3 * (size_t)natoms,
-                        m->c_mtype.as<int>() + natoms, m->c_src.as<long long>(), m->c_shift.as<double>(), s);
-      if (ng <= cap) break;
-      cap = ng;
+      m->active_mapped = present;
+      cell_evaluate(m, who, natoms, h.nghost, f, eatom, eng, virial, s);
+      m->hold.serial = serial;
+      if (rebuilt) *rebuilt = 0;
+    } else {
+      const int ng = cell_rebuild(m, who, present, natoms, x, mtype, cell, pbc, skin, f, eatom, eng, virial);
+      const double rc = *std::max_element(m->rcut_model_host.begin(), m->rcut_model_host.end()) + skin;
+      cell_hold_take(*m, natoms, ng, cell, pbc, skin, rc, s);
+      m->hold.mtype.assign(mtype, mtype + natoms);
+      m->hold.serial = m->list_serial;
+      ++m->reuse_rebuilds;
+      if (rebuilt) *rebuilt = 1;
     }
-    m->cell_nghost_last = ng;
-    if ((long long)natoms + ng > 2147483647LL) throw ArgError("ahip_compute_cell: atoms + ghosts exceed 2^31 - 1 rows");
-    const int nall = natoms + ng;
-    m->cell_src_host.resize((size_t)ng);
-    if (ng > 0) copy_d2h(m->cell_src_host.data(), m->c_src.p, (size_t)ng * sizeof(long long));
-    m->active_mapped = present;               // a model of more than 16 types runs on the types present (run_model: resolve_active)
-    neigh_build(*m, natoms, nall, m->c_x.as<double>(), lo, hi, rc, s);
-    m->c_f.reserve((size_t)std::max(nall, 1) * 3 * sizeof(double));
-    m->c_eatom.reserve((size_t)std::max(nall, 1) * sizeof(double));
-    m->c_engvir.reserve(8 * sizeof(double));
-    // (twice at most: an evaluation whose f16x2 kernels raise the float16-range alarm under fused_arith=auto is repeated on the float32 instance, as in ahip_compute)
-    for (int attempt = 0;; ++attempt) {
-      AHIP_CHECK(hipMemsetAsync(m->c_f.p, 0, (size_t)std::max(nall, 1) * 3 * sizeof(double), s));
-      AHIP_CHECK(hipMemsetAsync(m->c_eatom.p, 0, (size_t)std::max(nall, 1) * sizeof(double), s));
-      rethrow_code(ahip_compute_dev(m, natoms, ng, m->c_x.as<double>(), m->c_mtype.as<int>(), nullptr, m->c_f.as<double>(), m->c_eatom.as<double>(),
-                                    m->c_engvir.as<double>(), s));
-      comm_scatter_local(ng, natoms, m->c_src.as<long long>(), m->c_f.as<double>(), s);      // ghost forces go home (newton on)
-      AHIP_CHECK(hipGetLastError());
-      AHIP_CHECK(hipStreamSynchronize(s));
-      if (const int bad = inactive_take(*m)) throw ArgError("ahip_compute_cell: " + inactive_message(*m, bad, "this evaluation") + " (nothing was written to f)");
-      if (alarm_take(*m)) {
-        if (arith_may_degrade(*m) && attempt == 0) {
-          arith_degrade(*m, "an activation left float16's range (non-finite edge gradient on the f16x2 arithmetic); the evaluation was repeated");
-          continue;
-        }
-        throw StateError("fused_arith=f16x2: an edge gradient was not finite (an activation left float16's range, or the input was not finite): the forces of this "
-                         "evaluation are invalid and were not written to f; set option fused_arith=f32 (or auto) for this model");
-      }
-      break;
-    }
-    double ev[7];
-    copy_d2h(ev, m->c_engvir.p, 7 * sizeof(double));
-    if (natoms > 0) {
-      copy_d2h(f, m->c_f.p, (size_t)natoms * 3 * sizeof(double));
-      if (eatom) copy_d2h(eatom, m->c_eatom.p, (size_t)natoms * sizeof(double));
-    }
-    *eng = ev[0];
-    if (virial) for (int k = 0; k < 6; ++k) virial[k] = ev[1 + k];
+    ++m->reuse_calls;
+  });
+}
+
+int ahip_cell_reuse_reset(ahip_model *m) {
+  return guarded([&] {
+    require_model(m);
+    m->hold.serial = 0;
+    m->reuse_calls = m->reuse_rebuilds = 0;
+  });
+}
+
+int ahip_cell_reuse_stats(ahip_model *m, long long *calls, long long *rebuilds) {
+  return guarded([&] {
+    require_model(m);
+    if (calls) *calls = m->reuse_calls;
+    if (rebuilds) *rebuilds = m->reuse_rebuilds;
   });
 }
 
@@ -1530,6 +1612,7 @@ int ahip_compute_cells(ahip_model *m, int nstruct, const int *first, const doubl
       m->cells_nstruct = nstruct; m->cells_nghost_host.assign((size_t)nstruct, 0);
       return;
     }
+    m->hold.serial = 0;                       // the rows of a list held by ahip_compute_cell_reuse are overwritten from here on
     AHIP_CHECK(hipSetDevice(m->device));
     hipStream_t s = nullptr;
     // ONE upload: positions | structure table | model types | atom -> structure (packed on the host first: a second pass over the input, O(atoms), instead of

@@ -173,6 +173,20 @@ struct Model {
   DevBuf c_in, c_xp, c_out;
   int cells_nstruct = -1;
   std::vector<long long> cells_nghost_host;
+  // ahip_compute_cell_reuse: what a model holds from one call to the next.  list_serial counts every installation of a neighbor list (allegro_hip.hip:
+  // install_list_host, ahip_neigh_update_dev; neigh.hip: neigh_build, neigh_from_table) and every successful ahip_set_option; the hold is valid while its own
+  // serial is the model's, so nothing else has to know about it.  On the device: the staged positions of the call, the wrapped atom positions at the hold, the
+  // integer image of every ghost, the squared displacements (float32 bit patterns) with their maximum behind them.  The rows, the ghosts' sources and the list
+  // are those of ahip_compute_cell above.
+  unsigned long long list_serial = 0;
+  struct CellHold {
+    unsigned long long serial = 0;           // list_serial when the hold was taken; 0: nothing is held
+    int natoms = 0, nghost = 0, pbc[3] = {0, 0, 0};
+    double skin = 0.0, cell[9] = {0}, images[3] = {0, 0, 0}, min_height = 0.0;      // images: M_d = ceil(rc / h0_d) + 1; min_height: over the periodic axes
+    std::vector<int> mtype;
+  } hold;
+  DevBuf r_xin, r_xhold, r_img, r_disp;
+  long long reuse_calls = 0, reuse_rebuilds = 0;
 
   // edge list + workspace
   DevBuf b_cnt, b_eoff, b_eii, b_ej, b_rvec, b_partial, b_ws, b_misc;
@@ -429,6 +443,13 @@ void wrap_cell(Model &m, int n, double *x, const double *cell, const int *pbc, h
 int borders_cell(Model &m, int nlocal, const double *x, const int *mtype, const double *cell, const int *pbc, double rc, int capacity,
                  double *xg, int *mtg, long long *src, double *shift, hipStream_t s);
 void cell_bounding_box(const double *cell, double margin, double *lo, double *hi);
+// The held list of ahip_compute_cell_reuse (neigh.hip; criterion and proof: include/allegro_hip.h).  cell_hold_take, behind a rebuild whose rows are in m.c_x /
+// m.c_src / m.c_shift: copies the wrapped atom rows, recovers every ghost's integer image n = round(shift . cell^-1) and fills m.hold (enqueues on `s`, no
+// synchronisation; the caller sets the serial).  cell_hold_refresh: ArgError for a singular or non-finite `cell` before any launch; false, without a launch,
+// when the change of the cell alone fails the criterion; else uploads x, rewrites every row of m.c_x as the exact image in `cell` of the new position
+// (k_cell_refresh), reads the largest displacement back (one synchronisation) and says whether the held list still holds every pair within the cutoffs.
+void cell_hold_take(Model &m, int natoms, int nghost, const double *cell, const int *pbc, double skin, double rc, hipStream_t s);
+bool cell_hold_refresh(Model &m, const double *x_host, const double *cell, hipStream_t s);
 // A batch of cells as one non-periodic cloud (neigh.hip).  cells_plan is host-only and throws ArgError before any launch: per structure the geometry (a singular
 // or non-finite cell names its index), the 32-bit bound on atoms + images, the extent of its rows -- the Cartesian bounding box of its parallelepiped with the
 // fractional range [-m_d, 1 + m_d] on periodic axes and the range its atoms have on open ones -- and its origin: uniform slots of the largest extent plus

@@ -166,6 +166,7 @@ void neigh_build(Model &m, int nlocal, int nall, const double *x_dev, const doub
   m.d_nloff = st.off.as<int>();
   m.d_nlj = st.nlj.as<int>();
   m.inum = nlocal; m.nall = nall; m.nneigh = tot; m.have_list = true;
+  ++m.list_serial;
   m.max_list_row = maxrow;
   m.h_ilist.clear();
 }
@@ -234,6 +235,7 @@ void neigh_from_table(Model &m, int inum, int nall, const int *ilist_dev, const 
   m.d_nloff = st.off.as<int>();
   m.d_nlj = st.nlj.as<int>();
   m.inum = inum; m.nall = nall; m.nneigh = tot; m.have_list = true;
+  ++m.list_serial;
   m.max_list_row = hb[0];
   m.h_ilist.clear();
 }
@@ -315,6 +317,7 @@ int borders_local(Model &m, int nlocal, const double *x, const int *mtype, const
   bb.rc = rc;
   st.cnt.reserve(((size_t)nlocal + 1) * sizeof(int));
   st.off.reserve(((size_t)nlocal + 2) * sizeof(int));
+  ++m.list_serial;        // (st.off also carries the row offsets of a list built by neigh_build: a hold on that list ends here)
   const unsigned B = 256, G = (unsigned)((nlocal + B - 1) / B);
   hipLaunchKernelGGL(k_border_count, dim3(G), dim3(B), 0, s, nlocal, x, bb, st.cnt.as<int>());
   AHIP_CHECK(prim_exclusive_scan_i32(m.prim, st.cnt.as<int>(), st.off.as<int>(), nlocal, s));
@@ -427,6 +430,7 @@ int borders_cell(Model &m, int nlocal, const double *x, const int *mtype, const 
   NbState &st = *(NbState *)m.nb_state;
   st.cnt.reserve(((size_t)nlocal + 1) * sizeof(int));
   st.off.reserve(((size_t)nlocal + 2) * sizeof(int));
+  ++m.list_serial;        // (as in borders_local: the scan below overwrites the offsets of a list built by neigh_build)
   const unsigned B = 256;
   hipLaunchKernelGGL(k_cell_count, dim3((unsigned)((nlocal + B - 1) / B)), dim3(B), 0, s, nlocal, x, g, st.cnt.as<int>());
   AHIP_CHECK(prim_exclusive_scan_i32(m.prim, st.cnt.as<int>(), st.off.as<int>(), nlocal, s));
@@ -448,6 +452,91 @@ void cell_bounding_box(const double *cell, double margin, double *lo, double *hi
     for (int k = 0; k < 3; ++k) { l += std::min(cell[3 * k + d], 0.0); h += std::max(cell[3 * k + d], 0.0); }
     lo[d] = l - margin; hi[d] = h + margin;
   }
+}
+
+// ---- the held list of ahip_compute_cell_reuse ----
+// At a rebuild the model keeps, beside the rows and the list: the cell A0, the wrapped atom positions xhold and, per ghost, its integer image n.  A later call
+// with positions x and cell A rewrites EVERY row as an exact periodic image in A of the new position: atom a moves by the lattice combination k that brings it
+// nearest to where it was held (the caller may have wrapped it in between), ghost (a, n) follows as x_a - k A + n A.  Whether the held list still serves is
+// decided on the host from the largest displacement (criterion and proof: include/allegro_hip.h).
+__device__ __host__ inline int float_bits(float v) {
+  int b;
+  __builtin_memcpy(&b, &v, sizeof(b));
+  return b;
+}
+// n = round(shift . A0^-1): the shifts are n . A0 to rounding and n is a small integer, so the nearest integer is n itself
+__global__ void k_cell_images(int nghost, const double *shift, CellGeom g, int *img) {
+  const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nghost) return;
+  for (int d = 0; d < 3; ++d) img[3 * k + d] = (int)rint(cell_frac(g, shift + 3 * k, d));
+}
+// one thread per row (atoms, then ghosts); g is the cell of THIS call.  disp[a]: float32 bit pattern of |x_a - k A - xhold_a|^2 rounded up (as k_disp_max
+// rounds), 0x7fffffff when it is not finite -- non-negative floats order like their bit patterns, so prim_max_i32 finds the largest
+__global__ void k_cell_refresh(int natoms, int nrows, const double *xin, const double *xhold, const long long *src, const int *img, CellGeom g, double *x, int *disp) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nrows) return;
+  const long long a = r < natoms ? r : src[r - natoms];
+  const double dx[3] = {xin[3 * a] - xhold[3 * a], xin[3 * a + 1] - xhold[3 * a + 1], xin[3 * a + 2] - xhold[3 * a + 2]};
+  double c[3];                               // the row is x_a + c . A
+  for (int d = 0; d < 3; ++d) c[d] = g.pbc[d] ? -floor(cell_frac(g, dx, d) + 0.5) : 0.0;
+  if (r < natoms) {
+    double u2 = 0.0;
+    for (int d = 0; d < 3; ++d) {
+      const double u = dx[d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+      u2 += u * u;
+    }
+    const float v = (float)u2 * 1.000001f;   // rounded up: the criterion must not miss
+    disp[r] = v >= 0.f && v <= 3.0e38f ? float_bits(v) : 0x7fffffff;
+  } else {
+    for (int d = 0; d < 3; ++d) c[d] += (double)img[3 * (r - natoms) + d];
+  }
+  for (int d = 0; d < 3; ++d) x[3 * r + d] = xin[3 * a + d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+}
+void cell_hold_take(Model &m, int natoms, int nghost, const double *cell, const int *pbc, double skin, double rc, hipStream_t s) {
+  const CellGeom g = cell_geometry("ahip_compute_cell_reuse", cell, pbc, rc);
+  Model::CellHold &h = m.hold;
+  h.natoms = natoms; h.nghost = nghost; h.skin = skin;
+  h.min_height = INFINITY;
+  for (int d = 0; d < 3; ++d) {
+    h.pbc[d] = g.pbc[d];
+    h.images[d] = std::ceil(g.m[d]) + 1.0;                 // M_d = ceil(rc / h0_d) + 1
+    if (g.pbc[d]) h.min_height = std::min(h.min_height, rc / g.m[d]);
+  }
+  std::copy(cell, cell + 9, h.cell);
+  m.r_xhold.reserve((size_t)std::max(natoms, 1) * 3 * sizeof(double));
+  m.r_img.reserve((size_t)std::max(nghost, 1) * 3 * sizeof(int));
+  if (natoms > 0) AHIP_CHECK(hipMemcpyAsync(m.r_xhold.p, m.c_x.p, (size_t)natoms * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+  if (nghost > 0) hipLaunchKernelGGL(k_cell_images, dim3((unsigned)((nghost + 255) / 256)), dim3(256), 0, s, nghost, m.c_shift.as<double>(), g, m.r_img.as<int>());
+  AHIP_CHECK(hipGetLastError());
+}
+bool cell_hold_refresh(Model &m, const double *x_host, const double *cell, hipStream_t s) {
+  const Model::CellHold &h = m.hold;
+  const CellGeom g = cell_geometry("ahip_compute_cell_reuse", cell, h.pbc, 0.0);
+  double sum_g = 0.0, sum_mg = 0.0;          // over the periodic axes: g_d = |a_d - a0_d|
+  for (int d = 0; d < 3; ++d) {
+    if (!h.pbc[d]) continue;
+    double q = 0.0;
+    for (int k = 0; k < 3; ++k) { const double e = cell[3 * d + k] - h.cell[3 * d + k]; q += e * e; }
+    sum_g += std::sqrt(q);
+    sum_mg += h.images[d] * std::sqrt(q);
+  }
+  if (!(sum_g <= h.min_height) || !(sum_mg <= h.skin)) return false;
+  const int natoms = h.natoms, nrows = h.natoms + h.nghost;
+  if (natoms == 0) return true;
+  m.r_xin.reserve((size_t)natoms * 3 * sizeof(double));
+  m.r_disp.reserve(((size_t)natoms + 1) * sizeof(int));
+  copy_h2d(m.r_xin.p, x_host, (size_t)natoms * 3 * sizeof(double));
+  int *disp = m.r_disp.as<int>(), umax = 0;
+  hipLaunchKernelGGL(k_cell_refresh, dim3((unsigned)(((long long)nrows + 255) / 256)), dim3(256), 0, s, natoms, nrows, m.r_xin.as<double>(), m.r_xhold.as<double>(),
+                     m.c_src.as<long long>(), m.r_img.as<int>(), g, m.c_x.as<double>(), disp);
+  AHIP_CHECK(prim_max_i32(disp, natoms, disp + natoms, s));
+  AHIP_CHECK(hipMemcpyAsync(&umax, disp + natoms, sizeof(int), hipMemcpyDeviceToHost, s));
+  AHIP_CHECK(hipStreamSynchronize(s));
+  AHIP_CHECK(hipGetLastError());
+  if (umax == 0x7fffffff) return false;      // a position that is not finite: the rebuild path treats it as ahip_compute_cell does
+  float u2;
+  std::memcpy(&u2, &umax, sizeof(u2));
+  return 2.0 * std::sqrt((double)u2) + sum_mg <= h.skin;
 }
 
 // ---- a batch of cells as ONE non-periodic cloud (ahip_compute_cells) ----
