@@ -403,6 +403,64 @@ int ahip_compute_cell_reuse(ahip_model *m, int natoms, const double *x, const in
 int ahip_cell_reuse_reset(ahip_model *m);
 int ahip_cell_reuse_stats(ahip_model *m, long long *calls, long long *rebuilds);
 
+/* A RELAXATION of the atomic positions at fixed cell in one call: FIRE (Bitzek et al. 2006 as ASE implements it, unit masses) with the optimiser's state on the
+ * device.  The host enqueues check_every moves -- each with its evaluation -- without a wait and then reads one small state block back, where a loop over
+ * ahip_compute_cell_reuse pays an upload, three downloads and two synchronisations per move.  HOST pointers; arguments and argument errors are those of
+ * ahip_compute_cell_reuse, and besides: skin <= 0, p == NULL or a parameter outside the range given below.  All of them are AHIP_ERR_ARG before any launch, with x
+ * untouched and a held list as it was.
+ *   x      [natoms][3]  in: the start; out: the relaxed positions, NEVER wrapped (an atom that leaves the cell keeps its continuous coordinate)
+ *   fixed  [natoms] or NULL: non-zero = the atom does not move.  Its force is reported as the model gives it, not zeroed.
+ *   f, eatom (or NULL), eng, virial (or NULL): those of the returned x, with the contract of ahip_compute_cell
+ *   steps: moves made;  converged: max_i |F_i| <= fmax over the free atoms, from the forces handed out;  fmax_out: that maximum;  evaluations: every
+ *   ahip_compute_dev issued, those whose forces were discarded included;  rebuilds: ghost shells and lists built, the first included.  Each may be NULL.
+ * Parameters: fmax >= 0; max_steps >= 0; check_every >= 1; 0 < dt_start <= dt_max; max_step > 0; n_min >= 0; f_inc >= 1; 0 < f_dec <= 1; 0 <= alpha_start <= 1;
+ *   0 < f_alpha <= 1; all finite.
+ * ALGORITHM.  F: the forces with the ghost forces folded home, rows of fixed atoms set to 0.  v = 0, dt = dt_start, alpha = alpha_start, npos = 0 at the start.
+ * vf = sum v.F, ff = sum F.F, vv = sum v.v over all atoms.  U: the largest displacement of an atom from where it was when the held list was built (as in
+ * ahip_compute_cell_reuse: squared, in float32, rounded up); max_i |F_i|^2 is taken in float32 as well.  Before every move, in this order:
+ *   1. U is not finite                          -> NONFINITE
+ *   2. 2 U > skin                               -> NEED_REBUILD (the forces just computed are discarded; the cell does not change, so this is the reuse criterion)
+ *   3. vf, ff, vv or max |F_i|^2 is not finite  -> NONFINITE
+ *   4. max_i |F_i| <= fmax                      -> CONVERGED
+ * Otherwise the atoms move:
+ *   vf > 0:  c1 = 1 - alpha;  c2 = alpha sqrt(vv / ff);  if npos > n_min: dt = min(dt f_inc, dt_max), alpha *= f_alpha;  then npos += 1
+ *   else:    c1 = c2 = 0;  alpha = alpha_start;  dt *= f_dec;  npos = 0
+ *   and with the new dt:   v' = c1 v + (c2 + dt) F;   s = min(1, max_step / |dr|);   x' = x + s dt v';   v' is kept unscaled.
+ * |dr| is ASE's |dt v'|, the length of the whole 3 natoms vector.  Since v' is linear in v and F,
+ *     |dr|^2 = dt^2 (c1^2 vv + 2 c1 (c2 + dt) vf + (c2 + dt)^2 ff),
+ * so the three sums decide the move and one reduction pass per move suffices.  (v starts at 0, so the first move takes the else branch: dt_start f_dec.)
+ * DEVICE.  k_relax_gather writes [v.F, F.F, v.v] and the float32 bits of |F_i|^2 per atom; the deterministic column sum and the integer maximum of csrc/prims.hip
+ * reduce them; k_relax_decide, one thread, applies the above to the state block; k_relax_move, one thread per row (atoms, then ghosts), recomputes x' of the row's
+ * source atom and writes the row as the exact periodic image ahip_compute_cell_reuse would write, so the held list serves as it does there.  x and v alternate
+ * between two buffers: no thread reads what another thread of the same launch writes.  Once the status is not RUNNING every one of these kernels returns at once:
+ * positions, rows and state stay those whose forces the last evaluation of the chunk computes again.
+ * HOST.  Rebuild (rows, list, hold as in ahip_compute_cell_reuse), evaluate; then min(check_every, moves left) times {gather, reduce, decide, move, zero f,
+ * ahip_compute_dev, ghost forces home} without a wait, and one read-back of the state block.  RUNNING: the next chunk.  NEED_REBUILD: the rows, the list and
+ * the hold are built again from the positions on the device, which are evaluated, and the moves go on with v, dt, alpha and npos as they were.  CONVERGED: done.
+ * NONFINITE, or the float16-range alarm of any evaluation of the chunk: under fused_arith=auto on the f16x2 arithmetic, once per call, the model degrades to the float32 instance and the
+ * positions of the last valid move are evaluated again; otherwise the call returns AHIP_ERR_STATE and nothing is written to x or f (two coincident atoms end
+ * so).  An explicit active set that leaves out a type in use is AHIP_ERR_ARG behind the first read-back, nothing written.  A larger check_every wastes up to
+ * check_every - 1 evaluations at a rebuild or at convergence and saves a synchronisation per move; the result does not depend on it beyond the rounding of the
+ * forces' accumulation order.
+ * On success the model holds the list of the last rebuild as ahip_compute_cell_reuse would, with the same skin: a trajectory may go on from the returned x.
+ * ahip_last_cell_rows, ahip_get_edges and ahip_last_path describe the last evaluation.  A failure behind a launch ends the hold.
+ * Measured on one MI355X (tools/relax_cost.py, profiles/relax_cost.txt): a 200-move run from a 0.05 A jitter at skin 1.0 A, fmax 0, float32 model S, host
+ * clock per move, against the same FIRE written in numpy over Calculator(reuse=True).compute: 64-atom Si cell 148.4 / 131.4 / 137.4 us at check_every 1 / 4 / 16
+ * against 230.4 us (6 rebuilds; 211 / 220 / 244 evaluations), 10 648-atom Si box 517.9 / 457.2 / 452.3 us against 1632.0 us (2 rebuilds; 203 / 204 / 204
+ * evaluations).  Not slower than the Python loop at either size; the end points of the two routes agree to 1e-14 A. */
+typedef struct ahip_relax_params {
+  double fmax;        /* converged when max_i |F_i| <= fmax (eV/A); >= 0 */
+  int    max_steps;   /* moves at most; >= 0 */
+  int    check_every; /* moves enqueued between two looks of the host at the state; >= 1 */
+  double dt_start, dt_max, max_step;            /* 0.1, 1.0, 0.2 */
+  int    n_min;                                 /* 5 */
+  double f_inc, f_dec, alpha_start, f_alpha;    /* 1.1, 0.5, 0.1, 0.99 */
+} ahip_relax_params;
+int ahip_relax_params_default(ahip_relax_params *p);   /* the values above; fmax 0.05, max_steps 500, check_every 4 */
+int ahip_relax_cell(ahip_model *m, int natoms, double *x, const int *mtype, const double *cell, const int *pbc, double skin, const int *fixed,
+                    const ahip_relax_params *p, double *f, double *eatom, double *eng, double *virial, int *steps, int *converged, double *fmax_out,
+                    int *evaluations, int *rebuilds);
+
 /* A BATCH of structures in one call: what ahip_compute_cell computes for each of `nstruct` structures alone, with one upload, one ghost build, one neighbor
  * list and one evaluation for all of them (a data set of small cells is launch- and synchronisation-bound one structure at a time).  HOST pointers.
  *   first  [nstruct + 1], first[0] = 0, non-decreasing: structure s owns the atoms first[s] .. first[s+1] - 1 (an empty structure is allowed; nstruct == 0 too)

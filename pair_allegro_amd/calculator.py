@@ -6,6 +6,7 @@
     out = calc.compute(cell, positions, symbols)          # out["energy"], out["forces"], out["stress"]
     outs = calc.compute_many([(cell, positions, symbols), ...])      # a data set: one library call for many structures (ahip_compute_cells)
     calc = Calculator("model.nequip.pth", skin=1.0, reuse=True)      # a trajectory: ghosts and neighbor list are kept from call to call (ahip_compute_cell_reuse)
+    out = calc.relax(cell, positions, symbols, fmax=0.05)            # a FIRE relaxation at fixed cell in one library call (ahip_relax_cell): out["positions"]
 
 Any cell works: triclinic, thinner than the cutoff (several images per direction), open axes.  No ASE import: an ASE calculator is three lines
 around `compute(atoms.cell.array, atoms.positions, atoms.get_chemical_symbols(), atoms.pbc)`.
@@ -84,6 +85,34 @@ class Calculator:
         if self.reuse:
             info["rebuilt"] = rebuilt
         return dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, info=info)
+
+    def relax(self, cell, positions, symbols: Sequence[str], pbc: Sequence[bool] = (True, True, True), fmax: float = 0.05, max_steps: int = 500, fixed=None,
+              check_every: int = 4, **fire) -> dict:
+        """Relaxes the positions at fixed cell: FIRE with the optimiser's state on the device, one library call (ahip_relax_cell; include/allegro_hip.h states
+        the algorithm).  Converged when the largest force on a free atom is <= `fmax` (eV/A), or stopped after `max_steps` moves.  `fixed`: a boolean mask of
+        atoms that do not move.  `check_every`: moves the host enqueues between two looks at the state.  `fire`: the other fields of ahip_relax_params
+        (dt_start, dt_max, max_step, n_min, f_inc, f_dec, alpha_start, f_alpha).
+
+        Returns the dict of `compute` at the relaxed positions plus positions [n][3] (never wrapped: an atom that left the cell keeps its continuous
+        coordinate); info gains steps, converged, fmax (the largest force on a free atom), evaluations and rebuilds.  Needs a calculator with skin > 0: the
+        ghosts and the neighbor list are held while the atoms move, as with reuse=True.  A later `compute` of a reuse=True calculator goes on from that hold."""
+        if not self.skin > 0:
+            raise ValueError("relax needs a calculator with skin > 0: the skin is what the atoms may move through before the neighbor list is rebuilt")
+        cell = np.asarray(cell, dtype=np.float64)
+        pos = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
+        if len(symbols) != len(pos):
+            raise ValueError("positions and symbols differ in length")
+        pbc = tuple(bool(p) for p in pbc)
+        mt = self.model_types(symbols)
+        x, energy, forces, eatom, vir, rinfo = self.model.relax_cell(pos, mt, cell, pbc, self.skin, fixed=fixed, fmax=fmax, max_steps=max_steps,
+                                                                     check_every=check_every, **fire)
+        rows = self.model.last_cell_rows()
+        stress = None
+        if all(pbc):
+            vm = np.array([[vir[0], vir[3], vir[4]], [vir[3], vir[1], vir[5]], [vir[4], vir[5], vir[2]]])
+            stress = -vm / abs(np.linalg.det(cell))
+        info = dict(path=self.model.last_path, nghost=int(len(rows) - len(pos)), nedges=self.model.nedges(), row_atom=rows, **rinfo)
+        return dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, positions=x, info=info)
 
     def compute_many(self, structures: Sequence, max_atoms: int = 1 << 20) -> list:
         """A data set in as few library calls as possible (ahip_compute_cells: one upload, one ghost build, one neighbor list and one evaluation per call,

@@ -42,7 +42,14 @@ SYMBOLS = [
     "ahip_compute_cells", "ahip_last_cells_ghosts",
     "ahip_comm_migrate_cell", "ahip_comm_borders_cell",
     "ahip_compute_cell_reuse", "ahip_cell_reuse_reset", "ahip_cell_reuse_stats",
+    "ahip_relax_params_default", "ahip_relax_cell",
 ]
+
+
+class RelaxParams(C.Structure):
+    """ahip_relax_params (include/allegro_hip.h)"""
+    _fields_ = [("fmax", C.c_double), ("max_steps", C.c_int), ("check_every", C.c_int), ("dt_start", C.c_double), ("dt_max", C.c_double), ("max_step", C.c_double),
+                ("n_min", C.c_int), ("f_inc", C.c_double), ("f_dec", C.c_double), ("alpha_start", C.c_double), ("f_alpha", C.c_double)]
 
 
 class XferOp(C.Structure):
@@ -407,6 +414,52 @@ class Model:
         self.L.check(self.L.lib.ahip_compute_cell_reuse(self.h, n, _p(x, C.c_double), _p(mt, C.c_int), _p(c, C.c_double), _p(p, C.c_int), float(skin),
                                                          _p(f, C.c_double), _p(ea, C.c_double), C.byref(eng), _p(vir, C.c_double), C.byref(rebuilt)))
         return eng.value, f, ea, vir, bool(rebuilt.value)
+
+    def relax_params(self, **fire) -> RelaxParams:
+        """the library's defaults (ahip_relax_params_default) with the named fields replaced; an unknown name is a TypeError"""
+        p = RelaxParams()
+        self.L.lib.ahip_relax_params_default.argtypes = [C.POINTER(RelaxParams)]
+        self.L.check(self.L.lib.ahip_relax_params_default(C.byref(p)))
+        names = {n for n, _ in RelaxParams._fields_}
+        for k, v in fire.items():
+            if k not in names:
+                raise TypeError(f"unknown FIRE parameter {k!r} (known: {', '.join(n for n, _ in RelaxParams._fields_)})")
+            setattr(p, k, v)
+        return p
+
+    def relax_cell(self, x: np.ndarray, mtype: np.ndarray, cell, pbc=(True, True, True), skin: float = 1.0, fixed=None, want_eatom: bool = True,
+                   x_inout: Optional[np.ndarray] = None, f: Optional[np.ndarray] = None, **fire):
+        """FIRE relaxation at fixed cell on the device (ahip_relax_cell).  `fire`: fields of ahip_relax_params (fmax, max_steps, check_every, dt_start, ...).
+        Returns (positions, energy, forces, atomic energies or None, virial [6], info) with info = dict(steps, converged, fmax, evaluations, rebuilds).  The
+        positions are never wrapped.  `x_inout` / `f` (C-contiguous float64 [n][3]): the arrays the library itself reads and writes, instead of copies of `x`."""
+        c, p = self._cell_args(cell, pbc)
+        xr = np.array(x, dtype=np.float64).reshape(-1, 3) if x_inout is None else x_inout
+        mt = np.ascontiguousarray(mtype, dtype=np.int32).reshape(-1)
+        n = len(xr)
+        if len(mt) != n:
+            raise ValueError("positions and types differ in length")
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.int32).reshape(-1)
+            if len(fx) != n:
+                raise ValueError("positions and the fixed mask differ in length")
+        f = np.zeros((n, 3)) if f is None else f
+        for a in (xr, f):
+            if a.dtype != np.float64 or not a.flags.c_contiguous or a.shape != (n, 3):
+                raise ValueError("x_inout and f must be C-contiguous float64 arrays of shape [n][3]")
+        par = self.relax_params(**fire)
+        ea = np.zeros(n) if want_eatom else None
+        eng, fmax = C.c_double(0), C.c_double(0)
+        vir = np.zeros(6)
+        steps, conv, nev, nreb = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self.L.lib.ahip_relax_cell.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_double,
+                                               C.POINTER(C.c_int), C.POINTER(RelaxParams), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        self.L.check(self.L.lib.ahip_relax_cell(self.h, n, _p(xr, C.c_double), _p(mt, C.c_int), _p(c, C.c_double), _p(p, C.c_int), float(skin), _p(fx, C.c_int),
+                                                 C.byref(par), _p(f, C.c_double), _p(ea, C.c_double), C.byref(eng), _p(vir, C.c_double), C.byref(steps),
+                                                 C.byref(conv), C.byref(fmax), C.byref(nev), C.byref(nreb)))
+        info = dict(steps=steps.value, converged=bool(conv.value), fmax=fmax.value, evaluations=nev.value, rebuilds=nreb.value)
+        return xr, eng.value, f, ea, vir, info
 
     def cell_reuse_reset(self) -> None:
         """drop the held list (and the counters): the next compute_cell_reuse rebuilds"""

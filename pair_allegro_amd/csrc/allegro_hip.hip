@@ -254,7 +254,8 @@ void ahip_model_free(ahip_model *m) {
   for (DevBuf *b : {&m->b_flagwork, &m->b_ilist, &m->b_nloff, &m->b_nlj, &m->b_x, &m->b_ftype, &m->b_mtype, &m->b_f, &m->b_eatom,
                     &m->b_engvir, &m->b_cutsq, &m->b_cnt, &m->b_eoff, &m->b_eii, &m->b_ej, &m->b_rvec, &m->b_ett, &m->b_partial,
                     &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom,
-                    &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist, &m->c_x, &m->c_mtype, &m->c_f, &m->c_eatom, &m->c_src, &m->c_shift, &m->c_engvir, &m->c_in, &m->c_xp, &m->c_out, &m->r_xin, &m->r_xhold, &m->r_img, &m->r_disp})
+                    &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist, &m->c_x, &m->c_mtype, &m->c_f, &m->c_eatom, &m->c_src, &m->c_shift, &m->c_engvir, &m->c_in, &m->c_xp, &m->c_out, &m->r_xin, &m->r_xhold, &m->r_img, &m->r_disp,
+                    &m->q_x[0], &m->q_x[1], &m->q_v[0], &m->q_v[1], &m->q_fixed, &m->q_part, &m->q_fbits, &m->q_state})
     b->release();
   for (auto &t : m->slots) for (auto &e : t.ring) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (hipEvent_t e : m->f_events) (void)hipEventDestroy(e);
@@ -1412,17 +1413,21 @@ static std::vector<int> cell_check_args(const ahip_model *m, const std::string &
   return present;
 }
 
-// The evaluation on the rows of c_x / c_mtype with the installed list, ghost forces folded home, one synchronisation, the downloads.
-// (twice at most: an evaluation whose f16x2 kernels raise the float16-range alarm under fused_arith=auto is repeated on the float32 instance, as in ahip_compute)
-static void cell_evaluate(ahip_model *m, const std::string &who, int natoms, int ng, double *f, double *eatom, double *eng, double *virial, hipStream_t s) {
+// One evaluation on the rows of c_x / c_mtype with the installed list, enqueued: zeroed f and eatom, ahip_compute_dev, ghost forces folded home (newton on)
+static void cell_evaluate_enqueue(ahip_model *m, int natoms, int ng, hipStream_t s) {
   const int nall = natoms + ng;
+  AHIP_CHECK(hipMemsetAsync(m->c_f.p, 0, (size_t)std::max(nall, 1) * 3 * sizeof(double), s));
+  AHIP_CHECK(hipMemsetAsync(m->c_eatom.p, 0, (size_t)std::max(nall, 1) * sizeof(double), s));
+  rethrow_code(ahip_compute_dev(m, natoms, ng, m->c_x.as<double>(), m->c_mtype.as<int>(), nullptr, m->c_f.as<double>(), m->c_eatom.as<double>(),
+                                m->c_engvir.as<double>(), s));
+  comm_scatter_local(ng, natoms, m->c_src.as<long long>(), m->c_f.as<double>(), s);
+  AHIP_CHECK(hipGetLastError());
+}
+// The evaluation with its one synchronisation; the results stay on the device.  Returns how many evaluations it took
+// (twice at most: an evaluation whose f16x2 kernels raise the float16-range alarm under fused_arith=auto is repeated on the float32 instance, as in ahip_compute)
+static int cell_evaluate_dev(ahip_model *m, const std::string &who, int natoms, int ng, hipStream_t s) {
   for (int attempt = 0;; ++attempt) {
-    AHIP_CHECK(hipMemsetAsync(m->c_f.p, 0, (size_t)std::max(nall, 1) * 3 * sizeof(double), s));
-    AHIP_CHECK(hipMemsetAsync(m->c_eatom.p, 0, (size_t)std::max(nall, 1) * sizeof(double), s));
-    rethrow_code(ahip_compute_dev(m, natoms, ng, m->c_x.as<double>(), m->c_mtype.as<int>(), nullptr, m->c_f.as<double>(), m->c_eatom.as<double>(),
-                                  m->c_engvir.as<double>(), s));
-    comm_scatter_local(ng, natoms, m->c_src.as<long long>(), m->c_f.as<double>(), s);      // ghost forces go home (newton on)
-    AHIP_CHECK(hipGetLastError());
+    cell_evaluate_enqueue(m, natoms, ng, s);
     AHIP_CHECK(hipStreamSynchronize(s));
     if (const int bad = inactive_take(*m)) throw ArgError(who + ": " + inactive_message(*m, bad, "this evaluation") + " (nothing was written to f)");
     if (alarm_take(*m)) {
@@ -1433,8 +1438,11 @@ static void cell_evaluate(ahip_model *m, const std::string &who, int natoms, int
       throw StateError("fused_arith=f16x2: an edge gradient was not finite (an activation left float16's range, or the input was not finite): the forces of this "
                        "evaluation are invalid and were not written to f; set option fused_arith=f32 (or auto) for this model");
     }
-    break;
+    return attempt + 1;
   }
+}
+// the downloads of an evaluation that has been waited for
+static void cell_download(ahip_model *m, int natoms, double *f, double *eatom, double *eng, double *virial) {
   double ev[7];
   copy_d2h(ev, m->c_engvir.p, 7 * sizeof(double));
   if (natoms > 0) {
@@ -1444,15 +1452,17 @@ static void cell_evaluate(ahip_model *m, const std::string &who, int natoms, int
   *eng = ev[0];
   if (virial) for (int k = 0; k < 6; ++k) virial[k] = ev[1 + k];
 }
+static void cell_evaluate(ahip_model *m, const std::string &who, int natoms, int ng, double *f, double *eatom, double *eng, double *virial, hipStream_t s) {
+  cell_evaluate_dev(m, who, natoms, ng, s);
+  cell_download(m, natoms, f, eatom, eng, virial);
+}
 
-// ahip_compute_cell, and the rebuild path of ahip_compute_cell_reuse: upload, wrap, ghosts, list, evaluation, download.  Returns the number of ghosts.
-static int cell_rebuild(ahip_model *m, const std::string &who, const std::vector<int> &present, int natoms, const double *x, const int *mtype, const double *cell,
-                        const int *pbc, double skin, double *f, double *eatom, double *eng, double *virial) {
+// Rows and list of a cell: positions in (from the host, or with x_on_device from device memory), wrap, ghosts, neighbor list.  Returns the number of ghosts.
+static int cell_rows(ahip_model *m, const std::string &who, const std::vector<int> &present, int natoms, const double *x, bool x_on_device, const int *mtype,
+                     const double *cell, const int *pbc, double skin) {
   const double rc = *std::max_element(m->rcut_model_host.begin(), m->rcut_model_host.end()) + skin;
   AHIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = nullptr;
-  *eng = 0;
-  if (virial) for (int k = 0; k < 6; ++k) virial[k] = 0;
   m->hold.serial = 0;                         // the rows of a held list are overwritten from here on
   // upload, wrap, ghosts: rows [0, natoms) of c_x / c_mtype are the atoms, the images go behind them.  The first capacity is the last call's count when the
   // system has the same size, else none (the call then only counts); a grown buffer loses its content, so the one retry uploads again
@@ -1467,7 +1477,8 @@ static int cell_rebuild(ahip_model *m, const std::string &who, const std::vector
     m->c_src.reserve(std::max<size_t>((size_t)cap, 1) * sizeof(long long));
     m->c_shift.reserve(std::max<size_t>((size_t)cap, 1) * 3 * sizeof(double));
     if (natoms > 0) {
-      copy_h2d(m->c_x.p, x, (size_t)natoms * 3 * sizeof(double));
+      if (x_on_device) AHIP_CHECK(hipMemcpyAsync(m->c_x.p, x, (size_t)natoms * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+      else copy_h2d(m->c_x.p, x, (size_t)natoms * 3 * sizeof(double));
       copy_h2d(m->c_mtype.p, mtype, (size_t)natoms * sizeof(int));
     }
     wrap_cell(*m, natoms, m->c_x.as<double>(), cell, pbc, s);
@@ -1486,7 +1497,15 @@ static int cell_rebuild(ahip_model *m, const std::string &who, const std::vector
   m->c_f.reserve((size_t)std::max(nall, 1) * 3 * sizeof(double));
   m->c_eatom.reserve((size_t)std::max(nall, 1) * sizeof(double));
   m->c_engvir.reserve(8 * sizeof(double));
-  cell_evaluate(m, who, natoms, ng, f, eatom, eng, virial, s);
+  return ng;
+}
+// ahip_compute_cell, and the rebuild path of ahip_compute_cell_reuse: upload, wrap, ghosts, list, evaluation, download.  Returns the number of ghosts.
+static int cell_rebuild(ahip_model *m, const std::string &who, const std::vector<int> &present, int natoms, const double *x, const int *mtype, const double *cell,
+                        const int *pbc, double skin, double *f, double *eatom, double *eng, double *virial) {
+  *eng = 0;
+  if (virial) for (int k = 0; k < 6; ++k) virial[k] = 0;
+  const int ng = cell_rows(m, who, present, natoms, x, false, mtype, cell, pbc, skin);
+  cell_evaluate(m, who, natoms, ng, f, eatom, eng, virial, nullptr);
   return ng;
 }
 
@@ -1553,6 +1572,101 @@ int ahip_cell_reuse_stats(ahip_model *m, long long *calls, long long *rebuilds) 
     require_model(m);
     if (calls) *calls = m->reuse_calls;
     if (rebuilds) *rebuilds = m->reuse_rebuilds;
+  });
+}
+
+int ahip_relax_params_default(ahip_relax_params *p) {
+  return guarded([&] {
+    if (!p) throw ArgError("ahip_relax_params_default: p is NULL");
+    *p = ahip_relax_params{0.05, 500, 4, 0.1, 1.0, 0.2, 5, 1.1, 0.5, 0.1, 0.99};
+  });
+}
+
+// FIRE at fixed cell with the optimiser's state on the device (algorithm and statuses: include/allegro_hip.h; kernels: neigh.hip).  Nothing of the caller's is
+// written before the last read-back has succeeded.
+int ahip_relax_cell(ahip_model *m, int natoms, double *x, const int *mtype, const double *cell, const int *pbc, double skin, const int *fixed,
+                    const ahip_relax_params *p, double *f, double *eatom, double *eng, double *virial, int *steps, int *converged, double *fmax_out,
+                    int *evaluations, int *rebuilds) {
+  return guarded([&] {
+    require_model(m);
+    const std::string who = "ahip_relax_cell";
+    const std::vector<int> present = cell_check_args(m, who, natoms, x, mtype, cell, pbc, skin, f, eng);
+    if (!(skin > 0.0)) throw ArgError(who + ": skin must be > 0 (the skin is what the atoms may move through before the list is rebuilt)");
+    if (!p) throw ArgError(who + ": p is NULL (ahip_relax_params_default fills one)");
+    const auto finite_in = [](double v, double lo, double hi) { return std::isfinite(v) && v >= lo && v <= hi; };
+    if (!finite_in(p->fmax, 0.0, INFINITY)) throw ArgError(who + ": fmax must be a finite number >= 0");
+    if (p->max_steps < 0) throw ArgError(who + ": max_steps must be >= 0");
+    if (p->check_every < 1) throw ArgError(who + ": check_every must be >= 1");
+    if (!finite_in(p->dt_start, 0.0, INFINITY) || !(p->dt_start > 0.0) || !finite_in(p->dt_max, p->dt_start, INFINITY))
+      throw ArgError(who + ": need 0 < dt_start <= dt_max, both finite");
+    if (!finite_in(p->max_step, 0.0, INFINITY) || !(p->max_step > 0.0)) throw ArgError(who + ": max_step must be a finite number > 0");
+    if (p->n_min < 0) throw ArgError(who + ": n_min must be >= 0");
+    if (!finite_in(p->f_inc, 1.0, INFINITY)) throw ArgError(who + ": f_inc must be a finite number >= 1");
+    if (!finite_in(p->f_dec, 0.0, 1.0) || !(p->f_dec > 0.0)) throw ArgError(who + ": f_dec must be in (0, 1]");
+    if (!finite_in(p->alpha_start, 0.0, 1.0)) throw ArgError(who + ": alpha_start must be in [0, 1]");
+    if (!finite_in(p->f_alpha, 0.0, 1.0) || !(p->f_alpha > 0.0)) throw ArgError(who + ": f_alpha must be in (0, 1]");
+    (void)cell_geometry(who.c_str(), cell, pbc, 1.0);      // a singular or non-finite cell is refused here, with the hold as it was
+    // Whatever fails from here on fails behind a launch and leaves nothing held.
+    m->hold.serial = 0;
+    AHIP_CHECK(hipSetDevice(m->device));
+    hipStream_t s = nullptr;
+    const double rc = *std::max_element(m->rcut_model_host.begin(), m->rcut_model_host.end()) + skin;
+    const RelaxFire fire{p->fmax, p->dt_max, p->max_step, p->f_inc, p->f_dec, p->alpha_start, p->f_alpha, skin, p->n_min};
+    int moves = 0, nev = 0, nreb = 0, ng = 0;
+    relax_begin(*m, natoms, x, fixed, p->dt_start, p->alpha_start, s);
+    // rows, list and hold from the positions on the device (those of the last move), then their forces
+    const auto rebuild = [&] {
+      ng = cell_rows(m, who, present, natoms, m->q_x[moves & 1].as<double>(), true, mtype, cell, pbc, skin);
+      cell_hold_take(*m, natoms, ng, cell, pbc, skin, rc, s);
+      relax_rows_fresh(*m, natoms, s);
+      nev += cell_evaluate_dev(m, who, natoms, ng, s);
+      ++nreb;
+    };
+    rebuild();
+    bool may_repeat = true;                   // NONFINITE or the alarm: once, under fused_arith=auto, the frozen positions are evaluated again on the float32 instance
+    while (natoms > 0 && moves < p->max_steps) {
+      const int chunk = std::min(p->check_every, p->max_steps - moves);
+      for (int k = 0; k < chunk; ++k) {       // no wait in here
+        relax_step(*m, (moves + k) & 1, fire, s);
+        cell_evaluate_enqueue(m, natoms, ng, s);
+        ++nev;
+      }
+      const RelaxState st = relax_read(*m, s);
+      moves = st.moves;
+      if (const int bad = inactive_take(*m)) throw ArgError(who + ": " + inactive_message(*m, bad, "this evaluation") + " (nothing was written to x or f)");
+      if (alarm_take(*m) || st.status == RELAX_NONFINITE) {
+        if (!(arith_may_degrade(*m) && may_repeat && m->last_path.find("f16x2") != std::string::npos))      // (no other arithmetic has a float32 instance to fall back to)
+          throw StateError(who + ": a force, a sum over the atoms or a displacement was not finite after " + std::to_string(moves) + " moves (coincident atoms, an input that was "
+                           "not finite, or an activation left float16's range): the forces of this evaluation are invalid and nothing was written to x or f" +
+                           (arith_effective(m->arith.opt) == ArithOpt::F16x2 ? "; set option fused_arith=f32 (or auto) for this model" : ""));
+        may_repeat = false;
+        arith_degrade(*m, "a relaxation met a non-finite force or the float16-range alarm; the positions of its last valid move were evaluated again");
+        if (st.status != RELAX_NEED_REBUILD) {
+          nev += cell_evaluate_dev(m, who, natoms, ng, s);
+          relax_resume(*m, s);
+          continue;
+        }
+      }
+      if (st.status == RELAX_CONVERGED) break;
+      if (st.status == RELAX_NEED_REBUILD) {
+        rebuild();
+        relax_resume(*m, s);
+      }
+    }
+    AHIP_CHECK(hipStreamSynchronize(s));
+    AHIP_CHECK(hipGetLastError());
+    if (natoms > 0) copy_d2h(x, m->q_x[moves & 1].p, (size_t)natoms * 3 * sizeof(double));
+    cell_download(m, natoms, f, eatom, eng, virial);
+    double f2max = 0.0;                        // of the free atoms, from the forces handed out
+    for (int i = 0; i < natoms; ++i)
+      if (!(fixed && fixed[i])) f2max = std::max(f2max, f[3 * i] * f[3 * i] + f[3 * i + 1] * f[3 * i + 1] + f[3 * i + 2] * f[3 * i + 2]);
+    if (steps) *steps = moves;
+    if (converged) *converged = std::sqrt(f2max) <= p->fmax ? 1 : 0;
+    if (fmax_out) *fmax_out = std::sqrt(f2max);
+    if (evaluations) *evaluations = nev;
+    if (rebuilds) *rebuilds = nreb;
+    m->hold.mtype.assign(mtype, mtype + natoms);
+    m->hold.serial = m->list_serial;
   });
 }
 

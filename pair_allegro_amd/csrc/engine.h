@@ -187,6 +187,10 @@ struct Model {
   } hold;
   DevBuf r_xin, r_xhold, r_img, r_disp;
   long long reuse_calls = 0, reuse_rebuilds = 0;
+  // ahip_relax_cell (neigh.hip: relax_*): the optimiser's state lives on the device.  Unwrapped positions and velocities in two buffers each (a move reads one
+  // pair and writes the other), the fixed-atom mask, per atom [v.F, F.F, v.v] and the float32 bits of |F|^2, and the RelaxState block with the reduced
+  // sums and maxima behind it.  The rows, the hold and the displacement bits are those of ahip_compute_cell_reuse above.
+  DevBuf q_x[2], q_v[2], q_fixed, q_part, q_fbits, q_state;
 
   // edge list + workspace
   DevBuf b_cnt, b_eoff, b_eii, b_ej, b_rvec, b_partial, b_ws, b_misc;
@@ -450,6 +454,29 @@ void cell_bounding_box(const double *cell, double margin, double *lo, double *hi
 // (k_cell_refresh), reads the largest displacement back (one synchronisation) and says whether the held list still holds every pair within the cutoffs.
 void cell_hold_take(Model &m, int natoms, int nghost, const double *cell, const int *pbc, double skin, double rc, hipStream_t s);
 bool cell_hold_refresh(Model &m, const double *x_host, const double *cell, hipStream_t s);
+// FIRE on the device (ahip_relax_cell; algorithm: include/allegro_hip.h).  RelaxState is the block the host reads back every check_every moves; k_relax_decide
+// is its only writer on the device.  relax_begin uploads the start (never wrapped), zeroes the velocities and writes the initial state; relax_rows_fresh says
+// that the rows of m.c_x were just rebuilt from the current positions (displacements 0); relax_step enqueues gather, the two reductions, decide and move for
+// the move whose input buffers are `in` (0 or 1) -- no wait; relax_read waits for the stream and returns the state; relax_resume sets the status back to RUNNING.
+// The positions that count after a read are q_x[state.moves & 1].
+enum { RELAX_RUNNING = 0, RELAX_CONVERGED = 1, RELAX_NEED_REBUILD = 2, RELAX_NONFINITE = 3 };
+struct RelaxFire {
+  double fmax, dt_max, max_step, f_inc, f_dec, alpha_start, f_alpha, skin;
+  int n_min;
+};
+struct RelaxState {
+  double dt, alpha, c1, c2, s;       // s: the factor min(1, max_step / |dr|) of the last move
+  double fmax2, u2;                  // what the last decision saw: max |F_i|^2 and U^2 (float32 values)
+  double sums[3];                    // v.F, F.F, v.v (prim_sum_columns_f64)
+  int npos, status, moves;
+  int fbits, ubits;                  // prim_max_i32 of the |F_i|^2 and displacement bit patterns
+  int pad;
+};
+void relax_begin(Model &m, int natoms, const double *x_host, const int *fixed_host, double dt_start, double alpha_start, hipStream_t s);
+void relax_rows_fresh(Model &m, int natoms, hipStream_t s);
+void relax_step(Model &m, int in, const RelaxFire &p, hipStream_t s);
+RelaxState relax_read(Model &m, hipStream_t s);
+void relax_resume(Model &m, hipStream_t s);
 // A batch of cells as one non-periodic cloud (neigh.hip).  cells_plan is host-only and throws ArgError before any launch: per structure the geometry (a singular
 // or non-finite cell names its index), the 32-bit bound on atoms + images, the extent of its rows -- the Cartesian bounding box of its parallelepiped with the
 // fractional range [-m_d, 1 + m_d] on periodic axes and the range its atoms have on open ones -- and its origin: uniform slots of the largest extent plus

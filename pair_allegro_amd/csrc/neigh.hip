@@ -539,6 +539,144 @@ bool cell_hold_refresh(Model &m, const double *x_host, const double *cell, hipSt
   return 2.0 * std::sqrt((double)u2) + sum_mg <= h.skin;
 }
 
+// ---- FIRE with its state on the device (ahip_relax_cell; the algorithm is stated in include/allegro_hip.h) ----
+// Per move: k_relax_gather (one thread per atom), the column sums and the two maxima through prims, k_relax_decide (one thread, the only writer of the state),
+// k_relax_move (one thread per row).  Once the status is not RUNNING all three return at once, so the positions, the rows and the state stay those of the
+// last decision while the host has not looked.  No kernel here needs a barrier.
+__global__ void k_relax_gather(int natoms, const double *f, const double *v, const int *fixed, const RelaxState *st, double *part, int *fbits) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= natoms || st->status != RELAX_RUNNING) return;
+  double vf = 0.0, ff = 0.0, vv = 0.0;
+  if (!(fixed && fixed[i]))
+    for (int d = 0; d < 3; ++d) {
+      const double fd = f[3 * i + d], vd = v[3 * i + d];
+      vf += vd * fd; ff += fd * fd; vv += vd * vd;
+    }
+  part[3 * i] = vf; part[3 * i + 1] = ff; part[3 * i + 2] = vv;
+  const float q = (float)ff;                 // non-negative floats order like their bit patterns (k_cell_refresh)
+  fbits[i] = q >= 0.f && q <= 3.0e38f ? float_bits(q) : 0x7fffffff;
+}
+__device__ __host__ inline float bits_float(int b) {
+  float v;
+  __builtin_memcpy(&v, &b, sizeof(v));
+  return v;
+}
+__global__ void k_relax_decide(RelaxState *st, RelaxFire p) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || st->status != RELAX_RUNNING) return;
+  const double vf = st->sums[0], ff = st->sums[1], vv = st->sums[2];
+  const double u2 = (double)bits_float(st->ubits), f2 = (double)bits_float(st->fbits);
+  st->u2 = u2; st->fmax2 = f2;
+  if (st->ubits == 0x7fffffff) { st->status = RELAX_NONFINITE; return; }
+  if (2.0 * sqrt(u2) > p.skin) { st->status = RELAX_NEED_REBUILD; return; }
+  if (st->fbits == 0x7fffffff || !isfinite(vf) || !isfinite(ff) || !isfinite(vv)) { st->status = RELAX_NONFINITE; return; }
+  if (sqrt(f2) <= p.fmax) { st->status = RELAX_CONVERGED; return; }
+  double dt = st->dt, c1, c2;
+  if (vf > 0.0) {
+    c1 = 1.0 - st->alpha;
+    c2 = st->alpha * sqrt(vv / ff);
+    if (st->npos > p.n_min) {
+      dt = fmin(dt * p.f_inc, p.dt_max);
+      st->alpha *= p.f_alpha;
+    }
+    st->npos += 1;
+  } else {
+    c1 = c2 = 0.0;
+    st->alpha = p.alpha_start;
+    dt *= p.f_dec;
+    st->npos = 0;
+  }
+  // |dr|^2 = |dt v'|^2 with v' = c1 v + (c2 + dt) F, expanded in the three sums: no second pass over the atoms
+  const double k = c2 + dt, dr = dt * sqrt(fmax(c1 * c1 * vv + 2.0 * c1 * k * vf + k * k * ff, 0.0));
+  st->dt = dt; st->c1 = c1; st->c2 = c2;
+  st->s = dr > p.max_step ? p.max_step / dr : 1.0;
+  st->moves += 1;
+}
+// x' and v' of the row's source atom from the buffers of the move before, the row as k_cell_refresh writes it; atom rows also store x', v' and the
+// displacement bits.  xin / vin are never written by this launch.
+__global__ void k_relax_move(int natoms, int nrows, const RelaxState *st, const double *xin, const double *vin, const double *f, const int *fixed,
+                             const double *xhold, const long long *src, const int *img, CellGeom g, double *xout, double *vout, double *x, int *disp) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nrows || st->status != RELAX_RUNNING) return;
+  const long long a = r < natoms ? r : src[r - natoms];
+  const bool fix = fixed && fixed[a];
+  const double c1 = st->c1, k = st->c2 + st->dt, sdt = st->s * st->dt;
+  double xn[3], vn[3], dx[3];
+  for (int d = 0; d < 3; ++d) {
+    vn[d] = fix ? 0.0 : c1 * vin[3 * a + d] + k * f[3 * a + d];
+    xn[d] = fix ? xin[3 * a + d] : xin[3 * a + d] + sdt * vn[d];
+    dx[d] = xn[d] - xhold[3 * a + d];
+  }
+  double c[3];                               // the row is x'_a + c . A
+  for (int d = 0; d < 3; ++d) c[d] = g.pbc[d] ? -floor(cell_frac(g, dx, d) + 0.5) : 0.0;
+  if (r < natoms) {
+    double u2 = 0.0;
+    for (int d = 0; d < 3; ++d) {
+      const double u = dx[d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+      u2 += u * u;
+      xout[3 * r + d] = xn[d]; vout[3 * r + d] = vn[d];
+    }
+    const float q = (float)u2 * 1.000001f;   // rounded up: the criterion must not miss
+    disp[r] = q >= 0.f && q <= 3.0e38f ? float_bits(q) : 0x7fffffff;
+  } else {
+    for (int d = 0; d < 3; ++d) c[d] += (double)img[3 * (r - natoms) + d];
+  }
+  for (int d = 0; d < 3; ++d) x[3 * r + d] = xn[d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+}
+void relax_begin(Model &m, int natoms, const double *x_host, const int *fixed_host, double dt_start, double alpha_start, hipStream_t s) {
+  const size_t n = (size_t)std::max(natoms, 1);
+  for (int k = 0; k < 2; ++k) { m.q_x[k].reserve(n * 3 * sizeof(double)); m.q_v[k].reserve(n * 3 * sizeof(double)); }
+  m.q_part.reserve(n * 3 * sizeof(double));
+  m.q_fbits.reserve(n * sizeof(int));
+  m.q_state.reserve(sizeof(RelaxState));
+  m.q_fixed.release();                       // no mask: the kernels take a null pointer
+  if (natoms > 0) {
+    copy_h2d(m.q_x[0].p, x_host, (size_t)natoms * 3 * sizeof(double));
+    AHIP_CHECK(hipMemsetAsync(m.q_v[0].p, 0, (size_t)natoms * 3 * sizeof(double), s));
+    if (fixed_host) {
+      m.q_fixed.reserve(n * sizeof(int));
+      copy_h2d(m.q_fixed.p, fixed_host, (size_t)natoms * sizeof(int));
+    }
+  }
+  RelaxState st{};
+  st.dt = dt_start; st.alpha = alpha_start; st.s = 1.0; st.status = RELAX_RUNNING;
+  copy_h2d(m.q_state.p, &st, sizeof(st));
+}
+void relax_rows_fresh(Model &m, int natoms, hipStream_t s) {
+  m.r_disp.reserve(((size_t)natoms + 1) * sizeof(int));
+  AHIP_CHECK(hipMemsetAsync(m.r_disp.p, 0, ((size_t)natoms + 1) * sizeof(int), s));
+}
+void relax_step(Model &m, int in, const RelaxFire &p, hipStream_t s) {
+  const Model::CellHold &h = m.hold;
+  const int natoms = h.natoms, nrows = h.natoms + h.nghost;
+  if (natoms == 0) return;
+  const CellGeom g = cell_geometry("ahip_relax_cell", h.cell, h.pbc, 0.0);
+  RelaxState *st = m.q_state.as<RelaxState>();
+  const double *f = m.c_f.as<double>();
+  const int *fixed = m.q_fixed.as<int>();
+  const unsigned nb = (unsigned)((natoms + 255) / 256);
+  hipLaunchKernelGGL(k_relax_gather, dim3(nb), dim3(256), 0, s, natoms, f, m.q_v[in].as<double>(), fixed, st, m.q_part.as<double>(), m.q_fbits.as<int>());
+  AHIP_CHECK(prim_sum_columns_f64(m.prim, m.q_part.as<double>(), natoms, 3, st->sums, s));
+  AHIP_CHECK(prim_max_i32(m.q_fbits.as<int>(), natoms, &st->fbits, s));
+  AHIP_CHECK(prim_max_i32(m.r_disp.as<int>(), natoms, &st->ubits, s));
+  hipLaunchKernelGGL(k_relax_decide, dim3(1), dim3(64), 0, s, st, p);
+  hipLaunchKernelGGL(k_relax_move, dim3((unsigned)(((long long)nrows + 255) / 256)), dim3(256), 0, s, natoms, nrows, st, m.q_x[in].as<double>(), m.q_v[in].as<double>(), f,
+                     fixed, m.r_xhold.as<double>(), m.c_src.as<long long>(), m.r_img.as<int>(), g, m.q_x[in ^ 1].as<double>(), m.q_v[in ^ 1].as<double>(),
+                     m.c_x.as<double>(), m.r_disp.as<int>());
+  AHIP_CHECK(hipGetLastError());
+}
+RelaxState relax_read(Model &m, hipStream_t s) {
+  AHIP_CHECK(hipStreamSynchronize(s));
+  AHIP_CHECK(hipGetLastError());
+  RelaxState st;
+  copy_d2h(&st, m.q_state.p, sizeof(st));
+  return st;
+}
+void relax_resume(Model &m, hipStream_t s) {
+  const int running = RELAX_RUNNING;
+  AHIP_CHECK(hipStreamSynchronize(s));
+  copy_h2d(&m.q_state.as<RelaxState>()->status, &running, sizeof(int));
+}
+
 // ---- a batch of cells as ONE non-periodic cloud (ahip_compute_cells) ----
 // Every structure keeps its own frame for the wrap and for its ghost images; only before the list build is every row (atom or ghost) translated by its
 // structure's origin, chosen on the host so that rows of different structures are farther apart than the list cutoff.  Behind that the batch is one list of
