@@ -461,6 +461,61 @@ int ahip_relax_cell(ahip_model *m, int natoms, double *x, const int *mtype, cons
                     const ahip_relax_params *p, double *f, double *eatom, double *eng, double *virial, int *steps, int *converged, double *fmax_out,
                     int *evaluations, int *rebuilds);
 
+/* A RELAXATION of the atomic positions AND THE CELL in one call: the FIRE of ahip_relax_cell over natoms + 3 rows, the strain degrees of freedom among them, with
+ * the optimiser's state -- the cell included -- on the device.  HOST pointers; arguments, argument errors and the parameters of `fire` are those of
+ * ahip_relax_cell, and besides: an open axis (a slab is relaxed with the strain mask, not with an open axis), cell_out == NULL, smax < 0, cell_factor < 0, or a
+ * pressure, smax or cell_factor that is not finite.  All of them are AHIP_ERR_ARG before any launch, with x untouched and a held list as it was.
+ *   cell      [9]  in: A0, rows = lattice vectors;   cell_out [9]: the relaxed cell
+ *   x         in: the start; out: the relaxed positions in cell_out, NEVER wrapped
+ *   f, eatom (or NULL), eng, virial (or NULL): those of the returned x in cell_out, with the contract of ahip_compute_cell
+ *   steps, converged, fmax_out, evaluations, rebuilds: as in ahip_relax_cell;  smax_out: max_ab |W_ext,ab| / V of the returned configuration;  converged: both
+ *   conditions below, from the forces and the virial handed out.  Each may be NULL.
+ * STATE.  A deformation gradient D (3 x 3, D = I at the start) and reference coordinates q_i (q_i = x_i at the start).  The configuration is A = A0 D^T (row
+ * a_d = D a0_d) and x_i = D q_i.  The generalised coordinates are the natoms + 3 rows (q_1 .. q_n, c D), c = cell_factor, 0 meaning natoms.
+ * GENERALISED FORCES.  W: the symmetric virial matrix of the evaluation in the sign this library reports (W = -dE/d(strain)); V = |det A|;
+ *   W_ext = W - pressure V I;   hydrostatic: W_ext = (tr W_ext / 3) I;   then W_ext,ab = 0 wherever mask (xx, yy, zz, xy, xz, yz) is 0.
+ *   atoms:  G_i = D^T F_i, 0 for a fixed atom (which follows the cell affinely: its q never changes);   strain rows:  G_D = W_ext D^-T / c
+ * These are -dH/dq_i and -dH/d(c D) of H = E + pressure V at fixed q resp. fixed D (mask and hydrostatic project the latter).
+ * FIRE is that of ahip_relax_cell with F replaced by G and v by the velocities of the natoms + 3 rows: vf = sum v.G, ff = sum G.G, vv = sum v.v, c1, c2, dt, alpha,
+ * npos, |dr| and s = min(1, max_step / |dr|) exactly as stated there.  Then v' = c1 v + (c2 + dt) G for every row, q' = q + s dt v' and D' = D + s dt v'_D / c.
+ * U is the displacement ahip_compute_cell_reuse would measure for x = D q in the cell A against the rows of the last rebuild (minimum image in A; squared, in
+ * float32, rounded up); g_d = |a_d - a_d(hold)| against the cell of the last rebuild, M_d and h0_d those of that cell.  Before every move, in this order:
+ *   1. U is not finite                                                          -> NONFINITE
+ *   2. not (2 U + sum_d M_d g_d <= skin and sum_d g_d <= min_d h0_d)            -> NEED_REBUILD (the forces just computed are discarded)
+ *   3. vf, ff, vv, max |F_i|^2, V, W_ext or det D is not finite, or det D <= 0  -> NONFINITE
+ *   4. max_i |F_i| <= fmax (Cartesian forces, free atoms) and max_ab |W_ext,ab| / V <= smax (eV/A^3)   -> CONVERGED
+ *   5. the move; but if det D' is not finite or <= 0, or A0 D'^T is singular, nothing moves            -> NONFINITE
+ * When max_steps moves are made, the configuration of the last one passes 1-4 once more without a move, so what is handed out was evaluated on a list that
+ * holds for it (a rebuild there evaluates it again).
+ * DEVICE.  k_vcell_gather writes G_i, [v.G, G.G, v.v] and the float32 bits of the Cartesian |F_i|^2 per atom; k_vcell_decide, one thread, adds the nine strain
+ * terms from the virial the evaluation left on the device, decides, and writes the coefficients, D', v'_D and the geometry (cell, inverse) of A0 D'^T into the
+ * state block -- the host has not seen that cell; k_vcell_move, one thread per row (atoms, then ghosts), recomputes q' and v' of the row's source atom, forms
+ * x' = D' q' and writes the row as the exact periodic image in A' that ahip_compute_cell_reuse would write.  q and v alternate between two buffers; no thread
+ * reads what another thread of the same launch writes; once the status is not RUNNING every kernel returns at once.
+ * HOST.  The loop of ahip_relax_cell.  At NEED_REBUILD the host takes the cell from the state block it has just read, forms x = D q on the device and builds rows,
+ * list and hold in that cell; the moves go on with v, v_D, dt, alpha and npos as they were.  NONFINITE, the float16-range alarm and an inactive type: as there
+ * (AHIP_ERR_STATE resp. AHIP_ERR_ARG, nothing written to x, cell_out or f); a cell_factor far too small for max_step ends so, by decision 5.
+ * On success the model holds the list of the last rebuild: ahip_compute_cell_reuse at the returned x and cell_out with the same skin runs on it.
+ * A model without an equilibrium volume (random weights) expands or collapses until a rebuild fails or the atoms leave each other's cutoff: choose a pressure.
+ * Measured on one MI355X (tools/vcell_relax_cost.py, profiles/vcell_relax_cost.txt): 200 moves from a 0.05 A jitter at skin 1.0 A, fmax = smax = 0, c = natoms,
+ * float32 model S at the virial pressure of the start, host clock per move, against the same algorithm in numpy over Calculator(reuse=True).compute: 64-atom Si cell
+ * 247.6 / 238.3 / 343.2 us at check_every 1 / 4 / 16 against 313.3 us (the random-weight model has no stable volume: det D reaches 1.97 with 33 rebuilds on both
+ * routes; 265 / 315 / 553 evaluations -- at 16 the evaluations wasted at each rebuild cost more than the synchronisations saved, and the call is slower than the
+ * Python loop), 10 648-atom Si box 499.9 / 468.9 / 459.5 us against 1683.5 us (2 rebuilds; 203 / 204 / 204 evaluations).  At the default check_every 4 not slower
+ * at either size; the end points of the two routes agree to 1e-14 A (64 atoms) and 5e-8 A (10 648 atoms, float32 forces summed in another order). */
+typedef struct ahip_vcell_params {
+  ahip_relax_params fire;   /* fmax, max_steps, check_every and the FIRE constants, as in ahip_relax_cell */
+  double smax;              /* converged when also max_ab |W_ext,ab| / V <= smax (eV/A^3); >= 0 */
+  double pressure;          /* external pressure, eV/A^3; finite */
+  double cell_factor;       /* c > 0, or 0 for natoms: the weight of the strain rows among the generalised coordinates */
+  int    hydrostatic;       /* non-zero: only the volume changes */
+  int    mask[6];           /* xx, yy, zz, xy, xz, yz: 0 = that component of W_ext is not followed */
+} ahip_vcell_params;
+int ahip_vcell_params_default(ahip_vcell_params *p);   /* ahip_relax_params_default; smax 1e-3, pressure 0, cell_factor 0, not hydrostatic, mask all 1 */
+int ahip_relax_vcell(ahip_model *m, int natoms, double *x, const int *mtype, const double *cell, const int *pbc, double skin, const int *fixed,
+                     const ahip_vcell_params *p, double *cell_out, double *f, double *eatom, double *eng, double *virial, int *steps, int *converged,
+                     double *fmax_out, double *smax_out, int *evaluations, int *rebuilds);
+
 /* A BATCH of structures in one call: what ahip_compute_cell computes for each of `nstruct` structures alone, with one upload, one ghost build, one neighbor
  * list and one evaluation for all of them (a data set of small cells is launch- and synchronisation-bound one structure at a time).  HOST pointers.
  *   first  [nstruct + 1], first[0] = 0, non-decreasing: structure s owns the atoms first[s] .. first[s+1] - 1 (an empty structure is allowed; nstruct == 0 too)

@@ -7,6 +7,7 @@
     outs = calc.compute_many([(cell, positions, symbols), ...])      # a data set: one library call for many structures (ahip_compute_cells)
     calc = Calculator("model.nequip.pth", skin=1.0, reuse=True)      # a trajectory: ghosts and neighbor list are kept from call to call (ahip_compute_cell_reuse)
     out = calc.relax(cell, positions, symbols, fmax=0.05)            # a FIRE relaxation at fixed cell in one library call (ahip_relax_cell): out["positions"]
+    out = calc.relax(cell, positions, symbols, variable_cell=True, pressure=0.01)      # ... of positions and cell (ahip_relax_vcell): out["cell"] too
 
 Any cell works: triclinic, thinner than the cutoff (several images per direction), open axes.  No ASE import: an ASE calculator is three lines
 around `compute(atoms.cell.array, atoms.positions, atoms.get_chemical_symbols(), atoms.pbc)`.
@@ -87,7 +88,8 @@ class Calculator:
         return dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, info=info)
 
     def relax(self, cell, positions, symbols: Sequence[str], pbc: Sequence[bool] = (True, True, True), fmax: float = 0.05, max_steps: int = 500, fixed=None,
-              check_every: int = 4, **fire) -> dict:
+              check_every: int = 4, variable_cell: bool = False, smax: Optional[float] = None, pressure: float = 0.0, strain_mask=None,
+              hydrostatic: bool = False, cell_factor: Optional[float] = None, **fire) -> dict:
         """Relaxes the positions at fixed cell: FIRE with the optimiser's state on the device, one library call (ahip_relax_cell; include/allegro_hip.h states
         the algorithm).  Converged when the largest force on a free atom is <= `fmax` (eV/A), or stopped after `max_steps` moves.  `fixed`: a boolean mask of
         atoms that do not move.  `check_every`: moves the host enqueues between two looks at the state.  `fire`: the other fields of ahip_relax_params
@@ -95,7 +97,13 @@ class Calculator:
 
         Returns the dict of `compute` at the relaxed positions plus positions [n][3] (never wrapped: an atom that left the cell keeps its continuous
         coordinate); info gains steps, converged, fmax (the largest force on a free atom), evaluations and rebuilds.  Needs a calculator with skin > 0: the
-        ghosts and the neighbor list are held while the atoms move, as with reuse=True.  A later `compute` of a reuse=True calculator goes on from that hold."""
+        ghosts and the neighbor list are held while the atoms move, as with reuse=True.  A later `compute` of a reuse=True calculator goes on from that hold.
+
+        `variable_cell=True` relaxes the cell with the positions (ahip_relax_vcell, all axes periodic): converged when also the largest component of
+        stress + pressure is <= `smax` (eV/A^3; the library's default when None).  `pressure`: the external pressure (eV/A^3).  `strain_mask`: six flags (xx,
+        yy, zz, xy, xz, yz), False = that strain component is not followed -- the way to relax a slab.  `hydrostatic`: only the volume changes.
+        `cell_factor`: the weight of the strain rows among the generalised coordinates (None: the number of atoms).  The result gains cell [3][3], positions
+        and stress are those in that cell, and info gains smax.  A model without an equilibrium volume needs a pressure."""
         if not self.skin > 0:
             raise ValueError("relax needs a calculator with skin > 0: the skin is what the atoms may move through before the neighbor list is rebuilt")
         cell = np.asarray(cell, dtype=np.float64)
@@ -104,15 +112,31 @@ class Calculator:
             raise ValueError("positions and symbols differ in length")
         pbc = tuple(bool(p) for p in pbc)
         mt = self.model_types(symbols)
-        x, energy, forces, eatom, vir, rinfo = self.model.relax_cell(pos, mt, cell, pbc, self.skin, fixed=fixed, fmax=fmax, max_steps=max_steps,
-                                                                     check_every=check_every, **fire)
+        if variable_cell:
+            par = dict(fire, pressure=pressure, hydrostatic=int(bool(hydrostatic)))
+            if smax is not None:
+                par["smax"] = smax
+            if strain_mask is not None:
+                par["mask"] = strain_mask
+            if cell_factor is not None:
+                par["cell_factor"] = cell_factor
+            x, energy, forces, eatom, vir, rinfo, cell = self.model.relax_vcell(pos, mt, cell, pbc, self.skin, fixed=fixed, fmax=fmax, max_steps=max_steps,
+                                                                                check_every=check_every, **par)
+        else:
+            if smax is not None or pressure != 0.0 or strain_mask is not None or hydrostatic or cell_factor is not None:
+                raise ValueError("smax, pressure, strain_mask, hydrostatic and cell_factor belong to variable_cell=True")
+            x, energy, forces, eatom, vir, rinfo = self.model.relax_cell(pos, mt, cell, pbc, self.skin, fixed=fixed, fmax=fmax, max_steps=max_steps,
+                                                                         check_every=check_every, **fire)
         rows = self.model.last_cell_rows()
         stress = None
         if all(pbc):
             vm = np.array([[vir[0], vir[3], vir[4]], [vir[3], vir[1], vir[5]], [vir[4], vir[5], vir[2]]])
             stress = -vm / abs(np.linalg.det(cell))
         info = dict(path=self.model.last_path, nghost=int(len(rows) - len(pos)), nedges=self.model.nedges(), row_atom=rows, **rinfo)
-        return dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, positions=x, info=info)
+        out = dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, positions=x, info=info)
+        if variable_cell:
+            out["cell"] = cell
+        return out
 
     def compute_many(self, structures: Sequence, max_atoms: int = 1 << 20) -> list:
         """A data set in as few library calls as possible (ahip_compute_cells: one upload, one ghost build, one neighbor list and one evaluation per call,

@@ -43,6 +43,7 @@ SYMBOLS = [
     "ahip_comm_migrate_cell", "ahip_comm_borders_cell",
     "ahip_compute_cell_reuse", "ahip_cell_reuse_reset", "ahip_cell_reuse_stats",
     "ahip_relax_params_default", "ahip_relax_cell",
+    "ahip_vcell_params_default", "ahip_relax_vcell",
 ]
 
 
@@ -50,6 +51,11 @@ class RelaxParams(C.Structure):
     """ahip_relax_params (include/allegro_hip.h)"""
     _fields_ = [("fmax", C.c_double), ("max_steps", C.c_int), ("check_every", C.c_int), ("dt_start", C.c_double), ("dt_max", C.c_double), ("max_step", C.c_double),
                 ("n_min", C.c_int), ("f_inc", C.c_double), ("f_dec", C.c_double), ("alpha_start", C.c_double), ("f_alpha", C.c_double)]
+
+
+class VcellParams(C.Structure):
+    """ahip_vcell_params (include/allegro_hip.h)"""
+    _fields_ = [("fire", RelaxParams), ("smax", C.c_double), ("pressure", C.c_double), ("cell_factor", C.c_double), ("hydrostatic", C.c_int), ("mask", C.c_int * 6)]
 
 
 class XferOp(C.Structure):
@@ -460,6 +466,61 @@ class Model:
                                                  C.byref(conv), C.byref(fmax), C.byref(nev), C.byref(nreb)))
         info = dict(steps=steps.value, converged=bool(conv.value), fmax=fmax.value, evaluations=nev.value, rebuilds=nreb.value)
         return xr, eng.value, f, ea, vir, info
+
+    def vcell_params(self, **par) -> VcellParams:
+        """the library's defaults (ahip_vcell_params_default) with the named fields replaced: those of ahip_vcell_params (smax, pressure, cell_factor,
+        hydrostatic, mask) and those of its ahip_relax_params; an unknown name is a TypeError"""
+        p = VcellParams()
+        self.L.lib.ahip_vcell_params_default.argtypes = [C.POINTER(VcellParams)]
+        self.L.check(self.L.lib.ahip_vcell_params_default(C.byref(p)))
+        fire = {n for n, _ in RelaxParams._fields_}
+        own = {n for n, _ in VcellParams._fields_} - {"fire"}
+        for k, v in par.items():
+            if k == "mask":
+                v = [int(bool(e)) for e in v]
+                if len(v) != 6:
+                    raise ValueError("mask has six flags: xx, yy, zz, xy, xz, yz")
+                p.mask = (C.c_int * 6)(*v)
+            elif k in own:
+                setattr(p, k, v)
+            elif k in fire:
+                setattr(p.fire, k, v)
+            else:
+                raise TypeError(f"unknown relaxation parameter {k!r} (known: {', '.join(sorted(own | fire))})")
+        return p
+
+    def relax_vcell(self, x: np.ndarray, mtype: np.ndarray, cell, pbc=(True, True, True), skin: float = 1.0, fixed=None, want_eatom: bool = True,
+                    x_inout: Optional[np.ndarray] = None, f: Optional[np.ndarray] = None, params: Optional[VcellParams] = None, **par):
+        """FIRE relaxation of positions and cell on the device (ahip_relax_vcell).  `par`: fields of ahip_vcell_params and of its ahip_relax_params (fmax, smax,
+        pressure, mask, hydrostatic, cell_factor, max_steps, check_every, dt_start, ...); `params`: a ready VcellParams instead, or False for a NULL pointer.  Returns (positions, energy, forces, atomic energies or None, virial [6],
+        info, cell [3][3]) with info = dict(steps, converged, fmax, smax, evaluations, rebuilds).  The positions are never wrapped."""
+        c, p = self._cell_args(cell, pbc)
+        xr = np.array(x, dtype=np.float64).reshape(-1, 3) if x_inout is None else x_inout
+        mt = np.ascontiguousarray(mtype, dtype=np.int32).reshape(-1)
+        n = len(xr)
+        if len(mt) != n:
+            raise ValueError("positions and types differ in length")
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.int32).reshape(-1)
+            if len(fx) != n:
+                raise ValueError("positions and the fixed mask differ in length")
+        f = np.zeros((n, 3)) if f is None else f
+        for a in (xr, f):
+            if a.dtype != np.float64 or not a.flags.c_contiguous or a.shape != (n, 3):
+                raise ValueError("x_inout and f must be C-contiguous float64 arrays of shape [n][3]")
+        par_p = C.byref(self.vcell_params(**par)) if params is None else (None if params is False else C.byref(params))
+        ea = np.zeros(n) if want_eatom else None
+        eng, fmax, smax = C.c_double(0), C.c_double(0), C.c_double(0)
+        vir, cell_out = np.zeros(6), np.zeros((3, 3))
+        steps, conv, nev, nreb = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        D, I = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        self.L.lib.ahip_relax_vcell.argtypes = [C.c_void_p, C.c_int, D, I, D, I, C.c_double, I, C.POINTER(VcellParams), D, D, D, D, D, I, I, D, D, I, I]
+        self.L.check(self.L.lib.ahip_relax_vcell(self.h, n, _p(xr, C.c_double), _p(mt, C.c_int), _p(c, C.c_double), _p(p, C.c_int), float(skin), _p(fx, C.c_int),
+                                                  par_p, _p(cell_out, C.c_double), _p(f, C.c_double), _p(ea, C.c_double), C.byref(eng), _p(vir, C.c_double),
+                                                  C.byref(steps), C.byref(conv), C.byref(fmax), C.byref(smax), C.byref(nev), C.byref(nreb)))
+        info = dict(steps=steps.value, converged=bool(conv.value), fmax=fmax.value, smax=smax.value, evaluations=nev.value, rebuilds=nreb.value)
+        return xr, eng.value, f, ea, vir, info, cell_out
 
     def cell_reuse_reset(self) -> None:
         """drop the held list (and the counters): the next compute_cell_reuse rebuilds"""

@@ -255,7 +255,7 @@ void ahip_model_free(ahip_model *m) {
                     &m->b_engvir, &m->b_cutsq, &m->b_cnt, &m->b_eoff, &m->b_eii, &m->b_ej, &m->b_rvec, &m->b_ett, &m->b_partial,
                     &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom,
                     &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist, &m->c_x, &m->c_mtype, &m->c_f, &m->c_eatom, &m->c_src, &m->c_shift, &m->c_engvir, &m->c_in, &m->c_xp, &m->c_out, &m->r_xin, &m->r_xhold, &m->r_img, &m->r_disp,
-                    &m->q_x[0], &m->q_x[1], &m->q_v[0], &m->q_v[1], &m->q_fixed, &m->q_part, &m->q_fbits, &m->q_state})
+                    &m->q_x[0], &m->q_x[1], &m->q_v[0], &m->q_v[1], &m->q_fixed, &m->q_part, &m->q_fbits, &m->q_state, &m->q_g, &m->q_xc, &m->q_vstate})
     b->release();
   for (auto &t : m->slots) for (auto &e : t.ring) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (hipEvent_t e : m->f_events) (void)hipEventDestroy(e);
@@ -1582,6 +1582,22 @@ int ahip_relax_params_default(ahip_relax_params *p) {
   });
 }
 
+// the ranges of ahip_relax_params (include/allegro_hip.h)
+static void relax_check_params(const std::string &who, const ahip_relax_params *p) {
+  const auto finite_in = [](double v, double lo, double hi) { return std::isfinite(v) && v >= lo && v <= hi; };
+  if (!finite_in(p->fmax, 0.0, INFINITY)) throw ArgError(who + ": fmax must be a finite number >= 0");
+  if (p->max_steps < 0) throw ArgError(who + ": max_steps must be >= 0");
+  if (p->check_every < 1) throw ArgError(who + ": check_every must be >= 1");
+  if (!finite_in(p->dt_start, 0.0, INFINITY) || !(p->dt_start > 0.0) || !finite_in(p->dt_max, p->dt_start, INFINITY))
+    throw ArgError(who + ": need 0 < dt_start <= dt_max, both finite");
+  if (!finite_in(p->max_step, 0.0, INFINITY) || !(p->max_step > 0.0)) throw ArgError(who + ": max_step must be a finite number > 0");
+  if (p->n_min < 0) throw ArgError(who + ": n_min must be >= 0");
+  if (!finite_in(p->f_inc, 1.0, INFINITY)) throw ArgError(who + ": f_inc must be a finite number >= 1");
+  if (!finite_in(p->f_dec, 0.0, 1.0) || !(p->f_dec > 0.0)) throw ArgError(who + ": f_dec must be in (0, 1]");
+  if (!finite_in(p->alpha_start, 0.0, 1.0)) throw ArgError(who + ": alpha_start must be in [0, 1]");
+  if (!finite_in(p->f_alpha, 0.0, 1.0) || !(p->f_alpha > 0.0)) throw ArgError(who + ": f_alpha must be in (0, 1]");
+}
+
 // FIRE at fixed cell with the optimiser's state on the device (algorithm and statuses: include/allegro_hip.h; kernels: neigh.hip).  Nothing of the caller's is
 // written before the last read-back has succeeded.
 int ahip_relax_cell(ahip_model *m, int natoms, double *x, const int *mtype, const double *cell, const int *pbc, double skin, const int *fixed,
@@ -1593,18 +1609,7 @@ int ahip_relax_cell(ahip_model *m, int natoms, double *x, const int *mtype, cons
     const std::vector<int> present = cell_check_args(m, who, natoms, x, mtype, cell, pbc, skin, f, eng);
     if (!(skin > 0.0)) throw ArgError(who + ": skin must be > 0 (the skin is what the atoms may move through before the list is rebuilt)");
     if (!p) throw ArgError(who + ": p is NULL (ahip_relax_params_default fills one)");
-    const auto finite_in = [](double v, double lo, double hi) { return std::isfinite(v) && v >= lo && v <= hi; };
-    if (!finite_in(p->fmax, 0.0, INFINITY)) throw ArgError(who + ": fmax must be a finite number >= 0");
-    if (p->max_steps < 0) throw ArgError(who + ": max_steps must be >= 0");
-    if (p->check_every < 1) throw ArgError(who + ": check_every must be >= 1");
-    if (!finite_in(p->dt_start, 0.0, INFINITY) || !(p->dt_start > 0.0) || !finite_in(p->dt_max, p->dt_start, INFINITY))
-      throw ArgError(who + ": need 0 < dt_start <= dt_max, both finite");
-    if (!finite_in(p->max_step, 0.0, INFINITY) || !(p->max_step > 0.0)) throw ArgError(who + ": max_step must be a finite number > 0");
-    if (p->n_min < 0) throw ArgError(who + ": n_min must be >= 0");
-    if (!finite_in(p->f_inc, 1.0, INFINITY)) throw ArgError(who + ": f_inc must be a finite number >= 1");
-    if (!finite_in(p->f_dec, 0.0, 1.0) || !(p->f_dec > 0.0)) throw ArgError(who + ": f_dec must be in (0, 1]");
-    if (!finite_in(p->alpha_start, 0.0, 1.0)) throw ArgError(who + ": alpha_start must be in [0, 1]");
-    if (!finite_in(p->f_alpha, 0.0, 1.0) || !(p->f_alpha > 0.0)) throw ArgError(who + ": f_alpha must be in (0, 1]");
+    relax_check_params(who, p);
     (void)cell_geometry(who.c_str(), cell, pbc, 1.0);      // a singular or non-finite cell is refused here, with the hold as it was
     // Whatever fails from here on fails behind a launch and leaves nothing held.
     m->hold.serial = 0;
@@ -1663,6 +1668,129 @@ int ahip_relax_cell(ahip_model *m, int natoms, double *x, const int *mtype, cons
     if (steps) *steps = moves;
     if (converged) *converged = std::sqrt(f2max) <= p->fmax ? 1 : 0;
     if (fmax_out) *fmax_out = std::sqrt(f2max);
+    if (evaluations) *evaluations = nev;
+    if (rebuilds) *rebuilds = nreb;
+    m->hold.mtype.assign(mtype, mtype + natoms);
+    m->hold.serial = m->list_serial;
+  });
+}
+
+int ahip_vcell_params_default(ahip_vcell_params *p) {
+  return guarded([&] {
+    if (!p) throw ArgError("ahip_vcell_params_default: p is NULL");
+    *p = ahip_vcell_params{ahip_relax_params{0.05, 500, 4, 0.1, 1.0, 0.2, 5, 1.1, 0.5, 0.1, 0.99}, 1e-3, 0.0, 0.0, 0, {1, 1, 1, 1, 1, 1}};
+  });
+}
+
+// max_ab |W_ext,ab| / V of a virial in the cell `a`, as k_vcell_decide forms it
+static double vcell_sext(const double *virial, const double *a, const ahip_vcell_params *p) {
+  const double V = std::fabs(a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) + a[2] * (a[3] * a[7] - a[4] * a[6]));
+  double w[6];
+  for (int k = 0; k < 6; ++k) w[k] = virial[k] - (k < 3 ? p->pressure * V : 0.0);
+  if (p->hydrostatic) {
+    const double t = (w[0] + w[1] + w[2]) / 3.0;
+    for (int k = 0; k < 6; ++k) w[k] = k < 3 ? t : 0.0;
+  }
+  double wmax = 0.0;
+  for (int k = 0; k < 6; ++k) wmax = std::max(wmax, p->mask[k] ? std::fabs(w[k]) : 0.0);
+  return wmax / V;
+}
+
+// FIRE over the atoms and the cell with the optimiser's state on the device (algorithm and statuses: include/allegro_hip.h; kernels: neigh.hip).  The loop is that
+// of ahip_relax_cell; the cell of a rebuild is the one the state block holds.  Nothing of the caller's is written before the last read-back has succeeded.
+int ahip_relax_vcell(ahip_model *m, int natoms, double *x, const int *mtype, const double *cell, const int *pbc, double skin, const int *fixed,
+                     const ahip_vcell_params *p, double *cell_out, double *f, double *eatom, double *eng, double *virial, int *steps, int *converged,
+                     double *fmax_out, double *smax_out, int *evaluations, int *rebuilds) {
+  return guarded([&] {
+    require_model(m);
+    const std::string who = "ahip_relax_vcell";
+    const std::vector<int> present = cell_check_args(m, who, natoms, x, mtype, cell, pbc, skin, f, eng);
+    if (!(skin > 0.0)) throw ArgError(who + ": skin must be > 0 (the skin is what the atoms and the cell may move through before the list is rebuilt)");
+    if (!p) throw ArgError(who + ": p is NULL (ahip_vcell_params_default fills one)");
+    if (!cell_out) throw ArgError(who + ": cell_out is NULL");
+    if (!(pbc[0] && pbc[1] && pbc[2])) throw ArgError(who + ": all three axes must be periodic (relax a slab with the strain mask, not with an open axis)");
+    relax_check_params(who, &p->fire);
+    if (!std::isfinite(p->smax) || p->smax < 0.0) throw ArgError(who + ": smax must be a finite number >= 0");
+    if (!std::isfinite(p->pressure)) throw ArgError(who + ": pressure must be finite");
+    if (!std::isfinite(p->cell_factor) || p->cell_factor < 0.0) throw ArgError(who + ": cell_factor must be a finite number >= 0 (0: the number of atoms)");
+    (void)cell_geometry(who.c_str(), cell, pbc, 1.0);      // a singular or non-finite cell is refused here, with the hold as it was
+    // Whatever fails from here on fails behind a launch and leaves nothing held.
+    m->hold.serial = 0;
+    AHIP_CHECK(hipSetDevice(m->device));
+    hipStream_t s = nullptr;
+    const double rc = *std::max_element(m->rcut_model_host.begin(), m->rcut_model_host.end()) + skin;
+    VcellPar par{};
+    par.fire = RelaxFire{p->fire.fmax, p->fire.dt_max, p->fire.max_step, p->fire.f_inc, p->fire.f_dec, p->fire.alpha_start, p->fire.f_alpha, skin, p->fire.n_min};
+    par.smax = p->smax; par.pressure = p->pressure; par.hydrostatic = p->hydrostatic != 0;
+    par.cfac = p->cell_factor > 0.0 ? p->cell_factor : (double)std::max(natoms, 1);
+    for (int k = 0; k < 6; ++k) par.mask[k] = p->mask[k] != 0;
+    int moves = 0, nev = 0, nreb = 0, ng = 0;
+    vcell_begin(*m, natoms, x, fixed, cell, p->fire.dt_start, p->fire.alpha_start, s);
+    VcellState st = vcell_read(*m, s);
+    // rows, list and hold from x = D q of the last move in the cell of the state block, then their forces
+    const auto rebuild = [&] {
+      vcell_positions(*m, natoms, moves & 1, s);
+      ng = cell_rows(m, who, present, natoms, m->q_xc.as<double>(), true, mtype, st.geom.h, pbc, skin);
+      cell_hold_take(*m, natoms, ng, st.geom.h, pbc, skin, rc, s);
+      relax_rows_fresh(*m, natoms, s);
+      nev += cell_evaluate_dev(m, who, natoms, ng, s);
+      vcell_held(*m, st, s);
+      ++nreb;
+    };
+    rebuild();
+    bool may_repeat = true;                   // NONFINITE or the alarm: once, under fused_arith=auto, the frozen configuration is evaluated again on the float32 instance
+    bool checked = true;                      // the configuration on the device has passed the decisions 1-4 (or is that of a rebuild)
+    while (natoms > 0 && (moves < p->fire.max_steps || !checked)) {
+      const bool last = moves >= p->fire.max_steps;      // no move left: the configuration of the last move is only checked
+      const int chunk = std::min(p->fire.check_every, p->fire.max_steps - moves);
+      if (last) vcell_check(*m, moves & 1, par, s);
+      for (int k = 0; k < chunk; ++k) {       // no wait in here
+        vcell_step(*m, (moves + k) & 1, par, s);
+        cell_evaluate_enqueue(m, natoms, ng, s);
+        ++nev;
+      }
+      st = vcell_read(*m, s);
+      checked = last;
+      moves = st.moves;
+      if (const int bad = inactive_take(*m)) throw ArgError(who + ": " + inactive_message(*m, bad, "this evaluation") + " (nothing was written to x, cell_out or f)");
+      if (alarm_take(*m) || st.status == RELAX_NONFINITE) {
+        if (!(arith_may_degrade(*m) && may_repeat && m->last_path.find("f16x2") != std::string::npos))      // (no other arithmetic has a float32 instance to fall back to)
+          throw StateError(who + ": a force, a sum over the rows, a displacement or the cell was not finite, or the cell would invert, after " + std::to_string(moves) +
+                           " moves (coincident atoms, an input that was not finite, a cell_factor too small for max_step, or an activation left float16's range): the forces "
+                           "of this evaluation are invalid and nothing was written to x, cell_out or f" +
+                           (arith_effective(m->arith.opt) == ArithOpt::F16x2 ? "; set option fused_arith=f32 (or auto) for this model" : ""));
+        may_repeat = false;
+        checked = false;
+        arith_degrade(*m, "a relaxation met a non-finite force or the float16-range alarm; the configuration of its last valid move was evaluated again");
+        if (st.status != RELAX_NEED_REBUILD) {
+          nev += cell_evaluate_dev(m, who, natoms, ng, s);
+          vcell_resume(*m, s);
+          continue;
+        }
+      }
+      if (st.status == RELAX_CONVERGED) break;
+      if (st.status == RELAX_NEED_REBUILD) {
+        rebuild();
+        checked = true;
+      }
+    }
+    AHIP_CHECK(hipStreamSynchronize(s));
+    AHIP_CHECK(hipGetLastError());
+    vcell_positions(*m, natoms, moves & 1, s);
+    AHIP_CHECK(hipStreamSynchronize(s));
+    if (natoms > 0) copy_d2h(x, m->q_xc.p, (size_t)natoms * 3 * sizeof(double));
+    double vir[6];
+    cell_download(m, natoms, f, eatom, eng, vir);
+    if (virial) std::copy(vir, vir + 6, virial);
+    std::copy(st.geom.h, st.geom.h + 9, cell_out);
+    double f2max = 0.0;                        // of the free atoms, from the forces handed out
+    for (int i = 0; i < natoms; ++i)
+      if (!(fixed && fixed[i])) f2max = std::max(f2max, f[3 * i] * f[3 * i] + f[3 * i + 1] * f[3 * i + 1] + f[3 * i + 2] * f[3 * i + 2]);
+    const double sext = vcell_sext(vir, cell_out, p);
+    if (steps) *steps = moves;
+    if (converged) *converged = std::sqrt(f2max) <= p->fire.fmax && sext <= p->smax ? 1 : 0;
+    if (fmax_out) *fmax_out = std::sqrt(f2max);
+    if (smax_out) *smax_out = sext;
     if (evaluations) *evaluations = nev;
     if (rebuilds) *rebuilds = nreb;
     m->hold.mtype.assign(mtype, mtype + natoms);

@@ -34,27 +34,37 @@ __device__ __host__ inline void cell_wrap_row(const CellGeom &g, double *xi) {
   if (k[0] == 0.0 && k[1] == 0.0 && k[2] == 0.0) return;
   for (int d = 0; d < 3; ++d) xi[d] += k[0] * g.h[d] + k[1] * g.h[3 + d] + k[2] * g.h[6 + d];
 }
-// cell (row-major, rows = lattice vectors), its inverse and rc / height; ArgError for a singular or non-finite cell
-static CellGeom cell_geometry(const char *who, const double *cell, const int *pbc, double rc) {
-  CellGeom g;
+// cell (row-major, rows = lattice vectors), its inverse and rc / height, without an exception: 0, or 1 for a non-finite entry, 2 for a singular cell (g is then
+// partly written).  Device code calls it where the host has not seen the cell (neigh.hip: k_vcell_decide)
+__device__ __host__ inline int cell_geometry_try(const double *cell, const int *pbc, double rc, CellGeom &g) {
   double scale = 0.0;
   for (int k = 0; k < 9; ++k) {
-    if (!std::isfinite(cell[k])) throw ArgError(std::string(who) + ": the cell has a non-finite entry");
+    if (!std::isfinite(cell[k])) return 1;
     g.h[k] = cell[k];
-    scale = std::max(scale, std::fabs(cell[k]));
+    const double e = std::fabs(cell[k]);
+    scale = scale < e ? e : scale;
   }
   const double *a = g.h, *b = g.h + 3, *c = g.h + 6;
   const double bc[3] = {b[1] * c[2] - b[2] * c[1], b[2] * c[0] - b[0] * c[2], b[0] * c[1] - b[1] * c[0]};
   const double ca[3] = {c[1] * a[2] - c[2] * a[1], c[2] * a[0] - c[0] * a[2], c[0] * a[1] - c[1] * a[0]};
   const double ab[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
   const double det = a[0] * bc[0] + a[1] * bc[1] + a[2] * bc[2];
-  if (!std::isfinite(det) || !(std::fabs(det) > 1e-12 * scale * scale * scale)) throw ArgError(std::string(who) + ": the cell is singular");
+  if (!std::isfinite(det) || !(std::fabs(det) > 1e-12 * scale * scale * scale)) return 2;
   const double *cr[3] = {bc, ca, ab};                      // column d of cell^-1 = (cross product of the other two rows) / det
   for (int d = 0; d < 3; ++d) {
     double nrm = 0.0;
     for (int k = 0; k < 3; ++k) { g.inv[3 * k + d] = cr[d][k] / det; nrm += cr[d][k] * cr[d][k]; }
     g.m[d] = rc * std::sqrt(nrm) / std::fabs(det);         // rc / h_d,  h_d = volume / |cross product|
     g.pbc[d] = pbc[d] != 0;
+  }
+  return 0;
+}
+// the same with an ArgError for a singular or non-finite cell
+static CellGeom cell_geometry(const char *who, const double *cell, const int *pbc, double rc) {
+  CellGeom g;
+  switch (cell_geometry_try(cell, pbc, rc, g)) {
+    case 1: throw ArgError(std::string(who) + ": the cell has a non-finite entry");
+    case 2: throw ArgError(std::string(who) + ": the cell is singular");
   }
   return g;
 }

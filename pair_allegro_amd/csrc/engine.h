@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "arith_policy.h"
+#include "cell_geom.h"
 #include "fused_shapes.h"
 #include "model_io.h"
 #include "prims.h"
@@ -191,6 +192,8 @@ struct Model {
   // pair and writes the other), the fixed-atom mask, per atom [v.F, F.F, v.v] and the float32 bits of |F|^2, and the RelaxState block with the reduced
   // sums and maxima behind it.  The rows, the hold and the displacement bits are those of ahip_compute_cell_reuse above.
   DevBuf q_x[2], q_v[2], q_fixed, q_part, q_fbits, q_state;
+  // ahip_relax_vcell: q_x holds the reference coordinates q; besides, per atom G = D^T F, the unwrapped x = D q, and the VcellState block
+  DevBuf q_g, q_xc, q_vstate;
 
   // edge list + workspace
   DevBuf b_cnt, b_eoff, b_eii, b_ej, b_rvec, b_partial, b_ws, b_misc;
@@ -477,6 +480,37 @@ void relax_rows_fresh(Model &m, int natoms, hipStream_t s);
 void relax_step(Model &m, int in, const RelaxFire &p, hipStream_t s);
 RelaxState relax_read(Model &m, hipStream_t s);
 void relax_resume(Model &m, hipStream_t s);
+// FIRE over the atoms and the cell (ahip_relax_vcell; algorithm: include/allegro_hip.h).  The fixed-cell kernels and RelaxState above are not touched: the
+// variable cell has a state block of its own, which also carries what the host cannot hand over by value because it does not look between moves -- the
+// deformation gradient D with its velocity, the start cell A0, the hold (cell, M_d, min h0) the reuse criterion is taken against, and the geometry of the current
+// cell A0 D^T.  k_vcell_decide is its only writer on the device; the host writes it at the start and behind a rebuild (vcell_held), with the stream idle.
+// vcell_step: gather, reductions, decide, move for the move whose input buffers are `in`; vcell_check: gather, reductions and the decisions 1-4 without a move,
+// for the configuration the last move of a run left.  vcell_positions forms the unwrapped x = D q of buffer `in` in m.q_xc (device).
+struct VcellPar {
+  RelaxFire fire;
+  double smax, pressure, cfac;       // cfac: the factor c of the strain rows, > 0
+  int hydrostatic, mask[6];          // mask: xx, yy, zz, xy, xz, yz
+  int check_only;
+};
+struct VcellState {
+  double dt, alpha, c1, c2, s;
+  double fmax2, u2, sext, detD;      // what the last decision saw: max |F_i|^2, U^2 (float32 values), max |W_ext,ab| / V; det D of the current cell
+  double sums[3];                    // v.G, G.G, v.v over the atom rows (prim_sum_columns_f64); the decision adds the strain rows
+  double D[9], vD[9];                // row-major; x = D q, a_d = D a0_d
+  double A0[9];
+  double hold_cell[9], hold_images[3], hold_min_height;
+  CellGeom geom;                     // of the current cell: h = A0 D^T, inv; pbc all set
+  int npos, status, moves;
+  int fbits, ubits;
+  int pad;
+};
+void vcell_begin(Model &m, int natoms, const double *x_host, const int *fixed_host, const double *cell, double dt_start, double alpha_start, hipStream_t s);
+void vcell_step(Model &m, int in, const VcellPar &p, hipStream_t s);
+void vcell_check(Model &m, int in, const VcellPar &p, hipStream_t s);
+void vcell_positions(Model &m, int natoms, int in, hipStream_t s);
+VcellState vcell_read(Model &m, hipStream_t s);
+void vcell_held(Model &m, VcellState st, hipStream_t s);
+void vcell_resume(Model &m, hipStream_t s);
 // A batch of cells as one non-periodic cloud (neigh.hip).  cells_plan is host-only and throws ArgError before any launch: per structure the geometry (a singular
 // or non-finite cell names its index), the 32-bit bound on atoms + images, the extent of its rows -- the Cartesian bounding box of its parallelepiped with the
 // fractional range [-m_d, 1 + m_d] on periodic axes and the range its atoms have on open ones -- and its origin: uniform slots of the largest extent plus

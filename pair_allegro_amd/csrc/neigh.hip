@@ -677,6 +677,229 @@ void relax_resume(Model &m, hipStream_t s) {
   copy_h2d(&m.q_state.as<RelaxState>()->status, &running, sizeof(int));
 }
 
+// ---- FIRE over the atoms and the cell (ahip_relax_vcell; the algorithm is stated in include/allegro_hip.h) ----
+// The generalised coordinates are the reference positions q and c D; the rows of m.c_x are images of x = D q in the cell A0 D^T, whose geometry the decision
+// computes on the device (cell_geometry_try) because the host does not look between moves.  Per move: k_vcell_gather (one thread per atom), the reductions,
+// k_vcell_decide (one thread, the only writer of the state block), k_vcell_move (one thread per row).  As at fixed cell every kernel returns at once when the
+// status is not RUNNING, q and v alternate between two buffers, and no kernel needs a barrier.
+__device__ __host__ inline void vcell_apply(const double *D, const double *q, double *x) {
+  for (int a = 0; a < 3; ++a) x[a] = D[3 * a] * q[0] + D[3 * a + 1] * q[1] + D[3 * a + 2] * q[2];
+}
+__device__ __host__ inline double det3(const double *m) {
+  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+}
+// G_i = D^T F_i (0 for a fixed atom), [v.G, G.G, v.v], and the float32 bits of the CARTESIAN |F_i|^2 of a free atom
+__global__ void k_vcell_gather(int natoms, const double *f, const double *v, const int *fixed, const VcellState *st, double *gen, double *part, int *fbits) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= natoms || st->status != RELAX_RUNNING) return;
+  double vf = 0.0, gg = 0.0, vv = 0.0, ff = 0.0, G[3] = {0.0, 0.0, 0.0};
+  if (!(fixed && fixed[i])) {
+    const double F[3] = {f[3 * i], f[3 * i + 1], f[3 * i + 2]};
+    const double *D = st->D;
+    for (int d = 0; d < 3; ++d) {
+      G[d] = D[d] * F[0] + D[3 + d] * F[1] + D[6 + d] * F[2];
+      const double vd = v[3 * i + d];
+      vf += vd * G[d]; gg += G[d] * G[d]; vv += vd * vd; ff += F[d] * F[d];
+    }
+  }
+  for (int d = 0; d < 3; ++d) gen[3 * i + d] = G[d];
+  part[3 * i] = vf; part[3 * i + 1] = gg; part[3 * i + 2] = vv;
+  const float q = (float)ff;
+  fbits[i] = q >= 0.f && q <= 3.0e38f ? float_bits(q) : 0x7fffffff;
+}
+__global__ void k_vcell_decide(VcellState *st, const double *engvir, VcellPar p) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || st->status != RELAX_RUNNING) return;
+  const double u2 = (double)bits_float(st->ubits), f2 = (double)bits_float(st->fbits);
+  st->u2 = u2; st->fmax2 = f2;
+  // 1, 2: the largest displacement and the reuse criterion of ahip_compute_cell_reuse, the current cell against the cell of the last rebuild
+  if (st->ubits == 0x7fffffff) { st->status = RELAX_NONFINITE; return; }
+  double sum_g = 0.0, sum_mg = 0.0;
+  for (int d = 0; d < 3; ++d) {
+    double q = 0.0;
+    for (int k = 0; k < 3; ++k) { const double e = st->geom.h[3 * d + k] - st->hold_cell[3 * d + k]; q += e * e; }
+    sum_g += sqrt(q);
+    sum_mg += st->hold_images[d] * sqrt(q);
+  }
+  if (!(sum_g <= st->hold_min_height) || !(2.0 * sqrt(u2) + sum_mg <= p.fire.skin)) { st->status = RELAX_NEED_REBUILD; return; }
+  // the generalised force of the strain rows: W_ext = W - pressure V, hydrostatic, mask; G_D = W_ext D^-T / c
+  const double *D = st->D;
+  const double detD = det3(D), V = fabs(det3(st->geom.h));
+  st->detD = detD;
+  double W[9] = {engvir[1], engvir[4], engvir[5], engvir[4], engvir[2], engvir[6], engvir[5], engvir[6], engvir[3]};
+  for (int a = 0; a < 3; ++a) W[4 * a] -= p.pressure * V;
+  if (p.hydrostatic) {
+    const double t = (W[0] + W[4] + W[8]) / 3.0;
+    for (int k = 0; k < 9; ++k) W[k] = k % 4 == 0 ? t : 0.0;
+  }
+  const int mk[9] = {p.mask[0], p.mask[3], p.mask[4], p.mask[3], p.mask[1], p.mask[5], p.mask[4], p.mask[5], p.mask[2]};
+  double wmax = 0.0;
+  for (int k = 0; k < 9; ++k) {
+    if (!mk[k]) W[k] = 0.0;
+    wmax = fmax(wmax, fabs(W[k]));       // (fmax drops a NaN: the sums below catch it)
+  }
+  const double sext = wmax / V;
+  st->sext = sext;
+  // D^-1 by cofactors: inv[3 c + b] = cof[3 b + c] / det
+  const double cof[9] = {D[4] * D[8] - D[5] * D[7], D[5] * D[6] - D[3] * D[8], D[3] * D[7] - D[4] * D[6],
+                         D[2] * D[7] - D[1] * D[8], D[0] * D[8] - D[2] * D[6], D[1] * D[6] - D[0] * D[7],
+                         D[1] * D[5] - D[2] * D[4], D[2] * D[3] - D[0] * D[5], D[0] * D[4] - D[1] * D[3]};
+  double GD[9], vf = st->sums[0], ff = st->sums[1], vv = st->sums[2];
+  for (int a = 0; a < 3; ++a)
+    for (int c = 0; c < 3; ++c) {
+      // (W_ext D^-T)_ac = sum_b W_ab (D^-1)_cb,  (D^-1)_cb = cof[3 b + c] / det
+      const double g = (W[3 * a] * cof[c] + W[3 * a + 1] * cof[3 + c] + W[3 * a + 2] * cof[6 + c]) / detD / p.cfac;
+      GD[3 * a + c] = g;
+      vf += st->vD[3 * a + c] * g; ff += g * g; vv += st->vD[3 * a + c] * st->vD[3 * a + c];
+    }
+  // 3
+  if (st->fbits == 0x7fffffff || !isfinite(vf) || !isfinite(ff) || !isfinite(vv) || !isfinite(V) || !isfinite(sext) || !isfinite(detD) || !(detD > 0.0)) {
+    st->status = RELAX_NONFINITE;
+    return;
+  }
+  // 4
+  if (sqrt(f2) <= p.fire.fmax && sext <= p.smax) { st->status = RELAX_CONVERGED; return; }
+  if (p.check_only) return;
+  // 5: FIRE over all natoms + 3 rows
+  double dt = st->dt, alpha = st->alpha, c1, c2;
+  int npos = st->npos;
+  if (vf > 0.0) {
+    c1 = 1.0 - alpha;
+    c2 = alpha * sqrt(vv / ff);
+    if (npos > p.fire.n_min) {
+      dt = fmin(dt * p.fire.f_inc, p.fire.dt_max);
+      alpha *= p.fire.f_alpha;
+    }
+    npos += 1;
+  } else {
+    c1 = c2 = 0.0;
+    alpha = p.fire.alpha_start;
+    dt *= p.fire.f_dec;
+    npos = 0;
+  }
+  const double k = c2 + dt, dr = dt * sqrt(fmax(c1 * c1 * vv + 2.0 * c1 * k * vf + k * k * ff, 0.0));
+  const double sc = dr > p.fire.max_step ? p.fire.max_step / dr : 1.0;
+  double Dn[9], vDn[9], An[9];
+  for (int e = 0; e < 9; ++e) {
+    vDn[e] = c1 * st->vD[e] + k * GD[e];
+    Dn[e] = D[e] + sc * dt * vDn[e] / p.cfac;
+  }
+  for (int d = 0; d < 3; ++d) vcell_apply(Dn, st->A0 + 3 * d, An + 3 * d);      // a_d = D' a0_d
+  const int pbc[3] = {1, 1, 1};
+  const double detn = det3(Dn);
+  CellGeom gn;
+  // a move into a cell that is inverted, singular or not finite is not made: the state stays that of the last valid move
+  if (!isfinite(detn) || !(detn > 0.0) || cell_geometry_try(An, pbc, 0.0, gn) != 0) { st->status = RELAX_NONFINITE; return; }
+  for (int e = 0; e < 9; ++e) { st->D[e] = Dn[e]; st->vD[e] = vDn[e]; }
+  st->geom = gn;
+  st->dt = dt; st->alpha = alpha; st->npos = npos; st->c1 = c1; st->c2 = c2; st->s = sc;
+  st->moves += 1;
+}
+// q' and v' of the row's source atom from the buffers of the move before and the G of k_vcell_gather, x' = D' q', the row as k_cell_refresh writes it in the
+// cell of the state block; atom rows also store q', v' and the displacement bits.  qin / vin / gen are never written by this launch.
+__global__ void k_vcell_move(int natoms, int nrows, const VcellState *st, const double *qin, const double *vin, const double *gen, const int *fixed,
+                             const double *xhold, const long long *src, const int *img, double *qout, double *vout, double *x, int *disp) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nrows || st->status != RELAX_RUNNING) return;
+  const long long a = r < natoms ? r : src[r - natoms];
+  const bool fix = fixed && fixed[a];
+  const double c1 = st->c1, k = st->c2 + st->dt, sdt = st->s * st->dt;
+  const CellGeom &g = st->geom;
+  double qn[3], vn[3], xn[3], dx[3];
+  for (int d = 0; d < 3; ++d) {
+    vn[d] = fix ? 0.0 : c1 * vin[3 * a + d] + k * gen[3 * a + d];
+    qn[d] = fix ? qin[3 * a + d] : qin[3 * a + d] + sdt * vn[d];
+  }
+  vcell_apply(st->D, qn, xn);
+  for (int d = 0; d < 3; ++d) dx[d] = xn[d] - xhold[3 * a + d];
+  double c[3];                               // the row is x'_a + c . A'
+  for (int d = 0; d < 3; ++d) c[d] = -floor(cell_frac(g, dx, d) + 0.5);
+  if (r < natoms) {
+    double u2 = 0.0;
+    for (int d = 0; d < 3; ++d) {
+      const double u = dx[d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+      u2 += u * u;
+      qout[3 * r + d] = qn[d]; vout[3 * r + d] = vn[d];
+    }
+    const float q = (float)u2 * 1.000001f;   // rounded up: the criterion must not miss
+    disp[r] = q >= 0.f && q <= 3.0e38f ? float_bits(q) : 0x7fffffff;
+  } else {
+    for (int d = 0; d < 3; ++d) c[d] += (double)img[3 * (r - natoms) + d];
+  }
+  for (int d = 0; d < 3; ++d) x[3 * r + d] = xn[d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+}
+__global__ void k_vcell_positions(int natoms, const VcellState *st, const double *q, double *x) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= natoms) return;
+  double xi[3];
+  vcell_apply(st->D, q + 3 * i, xi);
+  for (int d = 0; d < 3; ++d) x[3 * i + d] = xi[d];
+}
+void vcell_begin(Model &m, int natoms, const double *x_host, const int *fixed_host, const double *cell, double dt_start, double alpha_start, hipStream_t s) {
+  relax_begin(m, natoms, x_host, fixed_host, dt_start, alpha_start, s);      // q = x, v = 0, the mask
+  const size_t n = (size_t)std::max(natoms, 1);
+  m.q_g.reserve(n * 3 * sizeof(double));
+  m.q_xc.reserve(n * 3 * sizeof(double));
+  m.q_vstate.reserve(sizeof(VcellState));
+  VcellState st{};
+  st.dt = dt_start; st.alpha = alpha_start; st.s = 1.0; st.detD = 1.0; st.status = RELAX_RUNNING;
+  const int pbc[3] = {1, 1, 1};
+  st.geom = cell_geometry("ahip_relax_vcell", cell, pbc, 0.0);
+  for (int k = 0; k < 9; ++k) { st.A0[k] = cell[k]; st.D[k] = k % 4 == 0 ? 1.0 : 0.0; }
+  copy_h2d(m.q_vstate.p, &st, sizeof(st));
+}
+static void vcell_gather_decide(Model &m, int in, const VcellPar &p, hipStream_t s) {
+  const int natoms = m.hold.natoms;
+  VcellState *st = m.q_vstate.as<VcellState>();
+  hipLaunchKernelGGL(k_vcell_gather, dim3((unsigned)((natoms + 255) / 256)), dim3(256), 0, s, natoms, m.c_f.as<double>(), m.q_v[in].as<double>(), m.q_fixed.as<int>(), st,
+                     m.q_g.as<double>(), m.q_part.as<double>(), m.q_fbits.as<int>());
+  AHIP_CHECK(prim_sum_columns_f64(m.prim, m.q_part.as<double>(), natoms, 3, st->sums, s));
+  AHIP_CHECK(prim_max_i32(m.q_fbits.as<int>(), natoms, &st->fbits, s));
+  AHIP_CHECK(prim_max_i32(m.r_disp.as<int>(), natoms, &st->ubits, s));
+  hipLaunchKernelGGL(k_vcell_decide, dim3(1), dim3(64), 0, s, st, m.c_engvir.as<double>(), p);
+}
+void vcell_step(Model &m, int in, const VcellPar &p, hipStream_t s) {
+  const int natoms = m.hold.natoms, nrows = m.hold.natoms + m.hold.nghost;
+  if (natoms == 0) return;
+  vcell_gather_decide(m, in, p, s);
+  hipLaunchKernelGGL(k_vcell_move, dim3((unsigned)(((long long)nrows + 255) / 256)), dim3(256), 0, s, natoms, nrows, m.q_vstate.as<VcellState>(), m.q_x[in].as<double>(),
+                     m.q_v[in].as<double>(), m.q_g.as<double>(), m.q_fixed.as<int>(), m.r_xhold.as<double>(), m.c_src.as<long long>(), m.r_img.as<int>(),
+                     m.q_x[in ^ 1].as<double>(), m.q_v[in ^ 1].as<double>(), m.c_x.as<double>(), m.r_disp.as<int>());
+  AHIP_CHECK(hipGetLastError());
+}
+void vcell_check(Model &m, int in, const VcellPar &p, hipStream_t s) {
+  if (m.hold.natoms == 0) return;
+  VcellPar q = p;
+  q.check_only = 1;
+  vcell_gather_decide(m, in, q, s);
+  AHIP_CHECK(hipGetLastError());
+}
+void vcell_positions(Model &m, int natoms, int in, hipStream_t s) {
+  if (natoms == 0) return;
+  hipLaunchKernelGGL(k_vcell_positions, dim3((unsigned)((natoms + 255) / 256)), dim3(256), 0, s, natoms, m.q_vstate.as<VcellState>(), m.q_x[in].as<double>(), m.q_xc.as<double>());
+  AHIP_CHECK(hipGetLastError());
+}
+VcellState vcell_read(Model &m, hipStream_t s) {
+  AHIP_CHECK(hipStreamSynchronize(s));
+  AHIP_CHECK(hipGetLastError());
+  VcellState st;
+  copy_d2h(&st, m.q_vstate.p, sizeof(st));
+  return st;
+}
+// behind a rebuild in the cell st.geom.h: the hold the criterion is taken against from now on, status RUNNING.  The stream is idle (the caller has read st).
+void vcell_held(Model &m, VcellState st, hipStream_t s) {
+  AHIP_CHECK(hipStreamSynchronize(s));
+  for (int k = 0; k < 9; ++k) st.hold_cell[k] = m.hold.cell[k];
+  for (int d = 0; d < 3; ++d) st.hold_images[d] = m.hold.images[d];
+  st.hold_min_height = m.hold.min_height;
+  st.status = RELAX_RUNNING;
+  copy_h2d(m.q_vstate.p, &st, sizeof(st));
+}
+void vcell_resume(Model &m, hipStream_t s) {
+  const int running = RELAX_RUNNING;
+  AHIP_CHECK(hipStreamSynchronize(s));
+  copy_h2d(&m.q_vstate.as<VcellState>()->status, &running, sizeof(int));
+}
+
 // ---- a batch of cells as ONE non-periodic cloud (ahip_compute_cells) ----
 // Every structure keeps its own frame for the wrap and for its ghost images; only before the list build is every row (atom or ghost) translated by its
 // structure's origin, chosen on the host so that rows of different structures are farther apart than the list cutoff.  Behind that the batch is one list of
