@@ -516,6 +516,77 @@ int ahip_relax_vcell(ahip_model *m, int natoms, double *x, const int *mtype, con
                      const ahip_vcell_params *p, double *cell_out, double *f, double *eatom, double *eng, double *virial, int *steps, int *converged,
                      double *fmax_out, double *smax_out, int *evaluations, int *rebuilds);
 
+/* MOLECULAR DYNAMICS in one call: NVE (velocity Verlet) or Langevin dynamics (BAOAB, Leimkuhler and Matthews 2013) with the integrator's state on the device.  The
+ * host enqueues check_every steps -- each with its evaluation -- without a wait and then reads one small state block back, where a loop over
+ * ahip_compute_cell_reuse pays an upload, three downloads and two synchronisations per step.  HOST pointers; arguments and argument errors are those of
+ * ahip_relax_cell, and besides: a parameter outside the range given below, v or mass NULL, a mass that is not finite and positive, a v that is not finite,
+ * frames != NULL with frame_every == 0 or the reverse, and frames that would take more than 1 GiB on the device (call again with fewer steps and carry x, v and
+ * step0 over).  All of them are AHIP_ERR_ARG before any launch, with x, v and f untouched and a held list as it was.
+ *   x, v   [natoms][3]  in: the start; out: the state after nsteps steps.  x is NEVER wrapped, as in ahip_relax_cell.
+ *   mass   [natoms], per atom
+ *   fixed  [natoms] or NULL: non-zero = the atom keeps x, has v = 0 and is left out of ke.  Its force is reported as the model gives it.
+ *   f, eatom (or NULL), eng, virial (or NULL): those of the returned x, with the contract of ahip_compute_cell
+ *   thermo [nsteps / sample_every + 1][8] or NULL: {pe, ke, vxx, vyy, vzz, vxy, vxz, vyz} of the configurations 0, sample_every, 2 sample_every, ...
+ *   frames [nsteps / frame_every + 1][natoms][3], unwrapped positions of the configurations 0, frame_every, ...; NULL iff frame_every == 0
+ *   evaluations, rebuilds (each may be NULL): as in ahip_relax_cell
+ * natoms == 0 launches nothing: eng, virial and the thermo rows are 0.
+ * ALGORITHM.  BAOAB.  hdtf = 0.5 dt ftm2v, c1 = exp(-gamma dt) and c2 = sqrt(1 - c1^2) are formed on the host in double; gamma = 0 gives c1 = 1, c2 = 0: velocity
+ * Verlet with two half drifts.  The device holds the unwrapped x and the post-thermostat velocity w in two buffers each, as the relaxation does (w = v at the
+ * start), vnow [natoms][3], mass, the mask, an MdState block, the thermo rows and the frames.  With the forces F_n of configuration n on the device
+ * (n = 0 .. nsteps), each iteration runs three kernels.
+ * 1. k_md_gather, one thread per atom: v_n = w + (n > 0 ? hdtf F_n / m : 0), 0 for a fixed atom.  It writes vnow, m |v_n|^2 and the float32 bits of |F_i|^2 as
+ *    k_relax_gather does, and the frame row when n % frame_every == 0.  prim_sum_columns_f64 and prim_max_i32 then reduce these, and the displacement bits the
+ *    move before left.
+ * 2. k_md_decide, one thread, the only device writer of the state.  In this order:
+ *      1. U is not finite                              -> NONFINITE
+ *      2. 2 U > skin                                   -> NEED_REBUILD (the forces just computed are discarded and no thermo row is written)
+ *      3. the ke sum, max |F_i|^2 or pe is not finite  -> NONFINITE
+ *      4. n % sample_every == 0: thermo row n / sample_every is written; pe and the virial are the 7 doubles the evaluation left on the device,
+ *         ke = 0.5 mvv2e sum_i m_i |v_n,i|^2
+ *      5. n == nsteps                                  -> DONE
+ *      6. otherwise n += 1 and the move happens.
+ * 3. k_md_move, one thread per row (atoms, then ghosts), on the row's source atom a, out of configuration n (the n of before decision 6):
+ *      v' = vnow_a + hdtf F_a / m_a;   xh = x_a + 0.5 dt v';   w' = gamma > 0 ? c1 v' + c2 sqrt(kT / (m_a mvv2e)) xi(a, step0 + n) : v';   x' = xh + 0.5 dt w'
+ *    (a fixed atom: x' = x_a, w' = 0).  The row is written as the exact periodic image, the way k_relax_move writes it; atom rows also store x', w' and the
+ *    displacement bits.  No thread reads what another thread of the same launch writes.
+ * Once the status is not RUNNING, all three kernels return at once.
+ * NOISE.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key (seed lo32, seed hi32), counter (atom lo32, step lo32,
+ * step hi32, j), j = 0, 1.  From the output words (w0, w1, w2, w3): u1 = (((uint64)w0 << 21 | w1 >> 11) + 0.5) 2^-53, u2 likewise from w2, w3;
+ * z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2 ln u1) sin(2 pi u2);  xi = (z0, z1 of j = 0; z0 of j = 1).  The noise of a step depends only on (seed, atom,
+ * step): not on check_every, on rebuilds, on the degradation replay, on ghost threads recomputing it, or on how a trajectory is cut into calls.  With gamma = 0
+ * no random number is drawn.  ahip_debug_md_noise runs exactly this device function for atoms 0 .. n-1 (out [n][3], HOST).
+ * HOST.  The loop of ahip_relax_cell: rebuild rows, list and hold from x, evaluate; per chunk min(check_every, steps left) times {gather, reduce, decide, move,
+ * zero f, evaluation, ghost forces home} without a wait, then one read-back of the state block.  The step count is known in advance, so iteration n == nsteps is
+ * enqueued as gather, reduce, decide only, behind the last move's evaluation, with no evaluation behind it: what is handed out was evaluated on a list that
+ * holds for it.  NEED_REBUILD: rows, list and hold are built from the positions on the device, which are evaluated; w and n stay as they were.  NONFINITE, the
+ * float16-range alarm and an inactive type: exactly as in ahip_relax_cell (one degradation to the float32 instance under fused_arith=auto; otherwise
+ * AHIP_ERR_STATE resp. AHIP_ERR_ARG with nothing written to x, v or f).  At the end v is vnow.  At check_every = 1 the evaluations are
+ * nsteps + 1 + 2 (rebuilds - 1), minus one when the final check was what rebuilt.
+ * On success the model holds the list of the last rebuild: ahip_compute_cell_reuse at the returned x with the same skin runs on it, and a following ahip_md_cell
+ * with the returned x, v and step0 + nsteps continues the trajectory (its first thermo row is this call's last).  A failure behind a launch ends the hold.
+ * Measured on one MI355X (tools/md_cost.py, profiles/md_cost.txt): 200 steps of 0.001 ps from 300 K and a 0.05 A jitter at skin 1.0 A, float32 model S, a thermo
+ * row per step, host clock per step, against the same BAOAB written in numpy over Calculator(reuse=True).compute.  64-atom Si cell: NVE 178.8 / 151.5 / 150.8 us at
+ * check_every 1 / 4 / 16 against 259.9 us (7 rebuilds; 213 / 227 / 247 evaluations), Langevin (gamma 5 / ps) 159.3 / 138.0 / 141.1 us against 246.5 us (6 rebuilds;
+ * 211 / 218 / 238 evaluations).  10 648-atom Si box: NVE 551.7 / 533.5 / 619.9 us against 1555.0 us (9 rebuilds; 217 / 228 / 273 evaluations), Langevin 527.9 / 519.9 /
+ * 578.3 us against 1903.1 us (8 rebuilds; 215 / 223 / 253 evaluations).  At the default check_every 4 not slower than the Python loop at either size; at 16 the
+ * evaluations wasted at each rebuild cost more than the synchronisations saved.  The NVE end points of the two routes agree to 2e-14 A. */
+typedef struct ahip_md_params {
+  int    nsteps;        /* steps to make; >= 0 */
+  int    check_every;   /* steps enqueued between two looks of the host at the state; >= 1 */
+  int    sample_every;  /* a thermo row at steps 0, sample_every, 2 sample_every, ... <= nsteps; >= 1 */
+  int    frame_every;   /* a frame of positions at those steps; 0 = none */
+  double dt;            /* > 0 */
+  double ftm2v, mvv2e;  /* unit factors as in LAMMPS: a = ftm2v F / m, ke = 0.5 mvv2e m v^2; both > 0 */
+  double gamma;         /* friction, 1 / time; 0 = NVE (no random number is drawn) */
+  double kT;            /* bath temperature in energy units; >= 0; read only when gamma > 0 */
+  unsigned long long seed, step0;   /* noise key; index of this call's first step (continuing a trajectory) */
+} ahip_md_params;
+int ahip_md_params_default(ahip_md_params *p);   /* metal units, dt 0.001 ps, gamma 0, check_every 4, sample_every 1, frame_every 0 */
+int ahip_md_cell(ahip_model *m, int natoms, double *x, double *v, const int *mtype, const double *mass, const double *cell, const int *pbc,
+                 double skin, const int *fixed, const ahip_md_params *p, double *f, double *eatom, double *eng, double *virial,
+                 double *thermo, double *frames, int *evaluations, int *rebuilds);
+int ahip_debug_md_noise(unsigned long long seed, unsigned long long step, int n, double *out /* [n][3] */);
+
 /* A BATCH of structures in one call: what ahip_compute_cell computes for each of `nstruct` structures alone, with one upload, one ghost build, one neighbor
  * list and one evaluation for all of them (a data set of small cells is launch- and synchronisation-bound one structure at a time).  HOST pointers.
  *   first  [nstruct + 1], first[0] = 0, non-decreasing: structure s owns the atoms first[s] .. first[s+1] - 1 (an empty structure is allowed; nstruct == 0 too)

@@ -8,6 +8,7 @@
     calc = Calculator("model.nequip.pth", skin=1.0, reuse=True)      # a trajectory: ghosts and neighbor list are kept from call to call (ahip_compute_cell_reuse)
     out = calc.relax(cell, positions, symbols, fmax=0.05)            # a FIRE relaxation at fixed cell in one library call (ahip_relax_cell): out["positions"]
     out = calc.relax(cell, positions, symbols, variable_cell=True, pressure=0.01)      # ... of positions and cell (ahip_relax_vcell): out["cell"] too
+    out = calc.md(cell, positions, symbols, steps=1000, dt=0.001, temperature=300.0, friction=5.0)      # MD in one library call (ahip_md_cell): out["thermo"]
 
 Any cell works: triclinic, thinner than the cutoff (several images per direction), open axes.  No ASE import: an ASE calculator is three lines
 around `compute(atoms.cell.array, atoms.positions, atoms.get_chemical_symbols(), atoms.pbc)`.
@@ -19,6 +20,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import capi
+from .units import FTM2V, KB, MVV2E, masses_of, maxwell_boltzmann
 
 
 class Calculator:
@@ -137,6 +139,53 @@ class Calculator:
         if variable_cell:
             out["cell"] = cell
         return out
+
+    def md(self, cell, positions, symbols: Sequence[str], pbc: Sequence[bool] = (True, True, True), steps: int = 100, dt: float = 0.001, velocities=None,
+           temperature: Optional[float] = None, friction: float = 0.0, seed: int = 0, step0: int = 0, masses: Optional[dict] = None, fixed=None,
+           sample_every: int = 1, frame_every: int = 0, check_every: int = 4) -> dict:
+        """Molecular dynamics with the integrator's state on the device, one library call (ahip_md_cell; include/allegro_hip.h states the algorithm): `steps`
+        steps of `dt`, NVE (velocity Verlet) when `friction` is 0, else Langevin dynamics by BAOAB at `temperature` with friction `friction`.  Metal units: A, eV,
+        ps, amu, K, 1 / ps.  `velocities` [n][3] in A / ps; None draws Maxwell-Boltzmann velocities at `temperature` with zero total momentum from `seed`.
+        `seed` also keys the thermostat's noise, which depends only on (seed, atom, step0 + step): a trajectory cut into calls, each started from the positions
+        and velocities the last returned with `step0` advanced by its steps, is the trajectory of one call.  `masses`: symbol -> amu over the standard atomic
+        weights of units.py; a symbol in neither is a ValueError.  `fixed`: a boolean mask of atoms that keep their position, have velocity 0 and are left out
+        of the kinetic energy.  `sample_every` / `frame_every`: a thermo row / a frame of positions every so many steps (0: no frames), step 0 included.
+        `check_every`: steps the host enqueues between two looks at the state.
+
+        Returns the dict of `compute` at the final positions plus positions (never wrapped) and velocities [n][3]; thermo: a dict of arrays step, pe, ke,
+        temperature = 2 ke / (3 N_free kB) and virial [.][6]; frames [.][n][3] or None; info gains steps, evaluations and rebuilds.  Needs a calculator with
+        skin > 0, like `relax`; a later `compute` of a reuse=True calculator goes on from the hold of the run."""
+        if not self.skin > 0:
+            raise ValueError("md needs a calculator with skin > 0: the skin is what the atoms may move through before the neighbor list is rebuilt")
+        cell = np.asarray(cell, dtype=np.float64)
+        pos = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
+        if len(symbols) != len(pos):
+            raise ValueError("positions and symbols differ in length")
+        pbc = tuple(bool(p) for p in pbc)
+        mt = self.model_types(symbols)
+        mass = masses_of(symbols, masses)
+        if friction > 0 and temperature is None:
+            raise ValueError("friction > 0 needs a temperature: the bath's")
+        if velocities is None:
+            if temperature is None:
+                raise ValueError("give velocities, or a temperature to draw them at")
+            velocities = maxwell_boltzmann(len(pos), mass, float(temperature), int(seed)) if len(pos) else np.zeros((0, 3))
+        vel = np.asarray(velocities, dtype=np.float64).reshape(-1, 3)
+        if len(vel) != len(pos):
+            raise ValueError("positions and velocities differ in length")
+        x, v, energy, forces, eatom, vir, th, frames, minfo = self.model.md_cell(
+            pos, vel, mt, mass, cell, pbc, self.skin, fixed=fixed, nsteps=int(steps), dt=float(dt), gamma=float(friction), kT=KB * float(temperature or 0.0),
+            seed=int(seed), step0=int(step0), ftm2v=FTM2V, mvv2e=MVV2E, sample_every=int(sample_every), frame_every=int(frame_every), check_every=int(check_every))
+        nfree = len(pos) - (int(np.count_nonzero(np.asarray(fixed).astype(bool))) if fixed is not None else 0)
+        thermo = dict(step=int(step0) + int(sample_every) * np.arange(len(th)), pe=th[:, 0].copy(), ke=th[:, 1].copy(),
+                      temperature=2.0 * th[:, 1] / (3.0 * max(nfree, 1) * KB), virial=th[:, 2:].copy())
+        rows = self.model.last_cell_rows() if len(pos) else np.zeros(0, dtype=np.int64)
+        stress = None
+        if all(pbc):
+            vm = np.array([[vir[0], vir[3], vir[4]], [vir[3], vir[1], vir[5]], [vir[4], vir[5], vir[2]]])
+            stress = -vm / abs(np.linalg.det(cell))
+        info = dict(path=self.model.last_path, nghost=int(len(rows) - len(pos)), nedges=self.model.nedges() if len(pos) else 0, row_atom=rows, **minfo)
+        return dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, positions=x, velocities=v, thermo=thermo, frames=frames, info=info)
 
     def compute_many(self, structures: Sequence, max_atoms: int = 1 << 20) -> list:
         """A data set in as few library calls as possible (ahip_compute_cells: one upload, one ghost build, one neighbor list and one evaluation per call,

@@ -44,6 +44,7 @@ SYMBOLS = [
     "ahip_compute_cell_reuse", "ahip_cell_reuse_reset", "ahip_cell_reuse_stats",
     "ahip_relax_params_default", "ahip_relax_cell",
     "ahip_vcell_params_default", "ahip_relax_vcell",
+    "ahip_md_params_default", "ahip_md_cell", "ahip_debug_md_noise",
 ]
 
 
@@ -56,6 +57,12 @@ class RelaxParams(C.Structure):
 class VcellParams(C.Structure):
     """ahip_vcell_params (include/allegro_hip.h)"""
     _fields_ = [("fire", RelaxParams), ("smax", C.c_double), ("pressure", C.c_double), ("cell_factor", C.c_double), ("hydrostatic", C.c_int), ("mask", C.c_int * 6)]
+
+
+class MdParams(C.Structure):
+    """ahip_md_params (include/allegro_hip.h)"""
+    _fields_ = [("nsteps", C.c_int), ("check_every", C.c_int), ("sample_every", C.c_int), ("frame_every", C.c_int), ("dt", C.c_double), ("ftm2v", C.c_double),
+                ("mvv2e", C.c_double), ("gamma", C.c_double), ("kT", C.c_double), ("seed", C.c_ulonglong), ("step0", C.c_ulonglong)]
 
 
 class XferOp(C.Structure):
@@ -199,6 +206,13 @@ class Library:
         assert Cbuf.size == E * ldc and (silu_out is None or silu_out.size == E * ldc) and (dsilu_z is None or dsilu_z.size == E * ldc)
         self.check(self.lib.ahip_debug_gemm_f32(E, K, N, _p(A, C.c_float), lda, a_off, _p(W, C.c_float), ldw, int(transB), _p(Cbuf, C.c_float), ldc,
                                                 int(accumulate), _p(silu_out, C.c_float), _p(dsilu_z, C.c_float)))
+
+    def debug_md_noise(self, seed: int, step: int, n: int) -> np.ndarray:
+        """xi of atoms 0 .. n-1 at one step [n][3], by the device function the Langevin move of ahip_md_cell uses (ahip_debug_md_noise)"""
+        out = np.zeros((n, 3))
+        self.lib.ahip_debug_md_noise.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_int, C.POINTER(C.c_double)]
+        self.check(self.lib.ahip_debug_md_noise(int(seed), int(step), n, _p(out, C.c_double)))
+        return out
 
     def check(self, rc: int) -> None:
         if rc != 0:
@@ -521,6 +535,67 @@ class Model:
                                                   C.byref(steps), C.byref(conv), C.byref(fmax), C.byref(smax), C.byref(nev), C.byref(nreb)))
         info = dict(steps=steps.value, converged=bool(conv.value), fmax=fmax.value, smax=smax.value, evaluations=nev.value, rebuilds=nreb.value)
         return xr, eng.value, f, ea, vir, info, cell_out
+
+    def md_params(self, **par) -> MdParams:
+        """the library's defaults (ahip_md_params_default) with the named fields replaced; an unknown name is a TypeError"""
+        p = MdParams()
+        self.L.lib.ahip_md_params_default.argtypes = [C.POINTER(MdParams)]
+        self.L.check(self.L.lib.ahip_md_params_default(C.byref(p)))
+        names = {n for n, _ in MdParams._fields_}
+        for k, v in par.items():
+            if k not in names:
+                raise TypeError(f"unknown MD parameter {k!r} (known: {', '.join(n for n, _ in MdParams._fields_)})")
+            setattr(p, k, v)
+        return p
+
+    def md_cell(self, x: np.ndarray, v: np.ndarray, mtype: np.ndarray, mass: np.ndarray, cell, pbc=(True, True, True), skin: float = 1.0, fixed=None,
+                want_eatom: bool = True, want_thermo: bool = True, x_inout: Optional[np.ndarray] = None, v_inout: Optional[np.ndarray] = None,
+                f: Optional[np.ndarray] = None, params=None, **par):
+        """MD on the device (ahip_md_cell): NVE, or Langevin dynamics by BAOAB when gamma > 0.  `par`: fields of ahip_md_params (nsteps, dt, gamma, kT, seed, step0,
+        check_every, sample_every, frame_every, ftm2v, mvv2e); `params`: a ready MdParams instead, or False for a NULL pointer.  Returns (x, v, energy, forces,
+        atomic energies or None, virial [6], thermo [nsteps / sample_every + 1][8] or None, frames [nsteps / frame_every + 1][n][3] or None, info) with info =
+        dict(steps, evaluations, rebuilds).  The positions are never wrapped.  `x_inout` / `v_inout` / `f` (C-contiguous float64 [n][3]): the arrays the library
+        itself reads and writes, instead of copies of `x` and `v`."""
+        c, p = self._cell_args(cell, pbc)
+        xr = np.array(x, dtype=np.float64).reshape(-1, 3) if x_inout is None else x_inout
+        vr = np.array(v, dtype=np.float64).reshape(-1, 3) if v_inout is None else v_inout
+        mt = np.ascontiguousarray(mtype, dtype=np.int32).reshape(-1)
+        ms = np.ascontiguousarray(mass, dtype=np.float64).reshape(-1)
+        n = len(xr)
+        if len(mt) != n or len(ms) != n:
+            raise ValueError("positions, types and masses differ in length")
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.int32).reshape(-1)
+            if len(fx) != n:
+                raise ValueError("positions and the fixed mask differ in length")
+        f = np.zeros((n, 3)) if f is None else f
+        for a in (xr, vr, f):
+            if a.dtype != np.float64 or not a.flags.c_contiguous or a.shape != (n, 3):
+                raise ValueError("x_inout, v_inout and f must be C-contiguous float64 arrays of shape [n][3]")
+        mp = self.md_params(**par) if params is None else params
+        if mp is False:
+            mp_ref, thermo, frames, nsteps = None, None, None, 0
+        else:
+            mp_ref, nsteps = C.byref(mp), int(mp.nsteps)
+            ok = nsteps >= 0 and mp.sample_every >= 1 and mp.frame_every >= 0          # (a range the library refuses: no buffer can be sized, it gets none)
+            thermo = np.zeros((nsteps // mp.sample_every + 1, 8)) if want_thermo and ok else None
+            frames = np.zeros((nsteps // mp.frame_every + 1, n, 3)) if ok and mp.frame_every > 0 else None
+        ea = np.zeros(n) if want_eatom else None
+        eng = C.c_double(0)
+        vir = np.zeros(6)
+        nev, nreb = C.c_int(0), C.c_int(0)
+        D, I = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        self.L.lib.ahip_md_cell.argtypes = [C.c_void_p, C.c_int, D, D, I, D, D, I, C.c_double, I, C.POINTER(MdParams), D, D, D, D, D, D, I, I]
+        self.L.check(self.L.lib.ahip_md_cell(self.h, n, _p(xr, C.c_double), _p(vr, C.c_double), _p(mt, C.c_int), _p(ms, C.c_double), _p(c, C.c_double), _p(p, C.c_int),
+                                              float(skin), _p(fx, C.c_int), mp_ref, _p(f, C.c_double), _p(ea, C.c_double), C.byref(eng), _p(vir, C.c_double),
+                                              _p(thermo, C.c_double), _p(frames, C.c_double), C.byref(nev), C.byref(nreb)))
+        info = dict(steps=nsteps, evaluations=nev.value, rebuilds=nreb.value)
+        return xr, vr, eng.value, f, ea, vir, thermo, frames, info
+
+    def debug_md_noise(self, seed: int, step: int, n: int) -> np.ndarray:
+        """xi of atoms 0 .. n-1 at one step [n][3], by the device function the Langevin move uses (ahip_debug_md_noise; the call needs no model)"""
+        return self.L.debug_md_noise(seed, step, n)
 
     def cell_reuse_reset(self) -> None:
         """drop the held list (and the counters): the next compute_cell_reuse rebuilds"""

@@ -194,6 +194,9 @@ struct Model {
   DevBuf q_x[2], q_v[2], q_fixed, q_part, q_fbits, q_state;
   // ahip_relax_vcell: q_x holds the reference coordinates q; besides, per atom G = D^T F, the unwrapped x = D q, and the VcellState block
   DevBuf q_g, q_xc, q_vstate;
+  // ahip_md_cell (neigh.hip: md_*): q_x holds the unwrapped positions and q_v the post-thermostat velocity w, as the relaxation holds x and v; besides, the
+  // velocity v_n of the configuration whose forces are on the device, the masses, the MdState block, the thermo rows and the frames
+  DevBuf q_vnow, q_mass, q_mstate, q_thermo, q_frames;
 
   // edge list + workspace
   DevBuf b_cnt, b_eoff, b_eii, b_ej, b_rvec, b_partial, b_ws, b_misc;
@@ -511,6 +514,30 @@ void vcell_positions(Model &m, int natoms, int in, hipStream_t s);
 VcellState vcell_read(Model &m, hipStream_t s);
 void vcell_held(Model &m, VcellState st, hipStream_t s);
 void vcell_resume(Model &m, hipStream_t s);
+// MD on the device (ahip_md_cell; algorithm: include/allegro_hip.h).  BAOAB over the held rows with the buffers, the row writer and the rebuild decision of the
+// relaxation, whose kernels and state blocks are not touched.  MdState is the block the host reads back every check_every steps; k_md_decide is its only writer
+// on the device.  md_begin uploads the start (never wrapped), w = v, the masses and the mask, and sizes the thermo rows and the frames; md_step enqueues gather,
+// the reductions and decide for the configuration whose buffers are `in` (0 or 1), and with `move` the move into the other pair -- no wait; md_read waits for the
+// stream and returns the state; md_resume sets the status back to RUNNING.  The positions that count after a read are q_x[state.n & 1].  md_noise: xi of atoms
+// 0 .. n-1 at one step, by the device function the move uses.
+enum { MD_RUNNING = 0, MD_DONE = 1, MD_NEED_REBUILD = 2, MD_NONFINITE = 3 };
+struct MdPar {
+  double dt, hdtf, c1, c2, gamma, kT, mvv2e, skin;      // hdtf = 0.5 dt ftm2v; c1 = exp(-gamma dt); c2 = sqrt(1 - c1^2)
+  unsigned long long seed, step0;
+  int nsteps, sample_every, frame_every;
+};
+struct MdState {
+  double u2, fmax2;                  // what the last decision saw: U^2 and max |F_i|^2 (float32 values)
+  double sums[1];                    // sum_i m_i |v_i|^2 (prim_sum_columns_f64)
+  int status, n;                     // n: the configuration whose forces are on the device, 0 .. nsteps
+  int fbits, ubits;                  // prim_max_i32 of the |F_i|^2 and displacement bit patterns
+};
+void md_begin(Model &m, int natoms, const double *x_host, const double *v_host, const double *mass_host, const int *fixed_host, size_t thermo_rows, size_t frame_rows,
+              hipStream_t s);
+void md_step(Model &m, int in, const MdPar &p, bool move, hipStream_t s);
+MdState md_read(Model &m, hipStream_t s);
+void md_resume(Model &m, hipStream_t s);
+void md_noise(unsigned long long seed, unsigned long long step, int n, double *out_dev, hipStream_t s);
 // A batch of cells as one non-periodic cloud (neigh.hip).  cells_plan is host-only and throws ArgError before any launch: per structure the geometry (a singular
 // or non-finite cell names its index), the 32-bit bound on atoms + images, the extent of its rows -- the Cartesian bounding box of its parallelepiped with the
 // fractional range [-m_d, 1 + m_d] on periodic axes and the range its atoms have on open ones -- and its origin: uniform slots of the largest extent plus

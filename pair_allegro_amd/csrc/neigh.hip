@@ -900,6 +900,178 @@ void vcell_resume(Model &m, hipStream_t s) {
   copy_h2d(&m.q_vstate.as<VcellState>()->status, &running, sizeof(int));
 }
 
+// ---- MD with its state on the device (ahip_md_cell; the algorithm is stated in include/allegro_hip.h) ----
+// BAOAB over the held rows.  Per configuration n: k_md_gather (one thread per atom), the column sum and the two maxima through prims, k_md_decide (one thread,
+// the only writer of the state), k_md_move (one thread per row).  As in the relaxation every kernel returns at once when the status is not RUNNING, x and w
+// alternate between two buffers, and no kernel needs a barrier.
+// Philox4x32-10 (Salmon et al. 2011) with plain 64-bit products
+__device__ __host__ inline void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned *out) {
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// xi(atom, step): three standard normals from the counters (atom, step lo, step hi, j), j = 0, 1, by Box-Muller on 53-bit uniforms in (0, 1)
+__device__ __host__ inline void md_xi(unsigned long long seed, long long atom, unsigned long long step, double *xi) {
+  for (unsigned j = 0; j < 2; ++j) {
+    unsigned w[4];
+    philox4x32_10((unsigned)atom, (unsigned)step, (unsigned)(step >> 32), j, (unsigned)seed, (unsigned)(seed >> 32), w);
+    const double u1 = ((double)(((unsigned long long)w[0] << 21) | (w[1] >> 11)) + 0.5) * 0x1p-53;
+    const double u2 = ((double)(((unsigned long long)w[2] << 21) | (w[3] >> 11)) + 0.5) * 0x1p-53;
+    const double rad = sqrt(-2.0 * log(u1)), phi = 6.283185307179586 * u2;
+    xi[2 * j] = rad * cos(phi);
+    if (j == 0) xi[1] = rad * sin(phi);
+  }
+}
+__global__ void k_md_noise(unsigned long long seed, unsigned long long step, int n, double *out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  md_xi(seed, i, step, out + 3 * i);
+}
+// v_n of every atom from w and the forces of configuration n; m |v_n|^2 and the |F_i|^2 bits as k_relax_gather forms them; the frame row of n
+__global__ void k_md_gather(int natoms, const double *f, const double *x, const double *w, const double *mass, const int *fixed, const MdState *st, MdPar p,
+                            double *vnow, double *part, int *fbits, double *frames) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= natoms || st->status != MD_RUNNING) return;
+  const int n = st->n;
+  const bool fix = fixed && fixed[i];
+  const double k = n > 0 ? p.hdtf / mass[i] : 0.0;
+  double ff = 0.0, vv = 0.0;
+  for (int d = 0; d < 3; ++d) {
+    const double fd = f[3 * i + d], vd = fix ? 0.0 : w[3 * i + d] + k * fd;
+    vnow[3 * i + d] = vd;
+    vv += vd * vd;
+    if (!fix) ff += fd * fd;
+  }
+  part[i] = mass[i] * vv;
+  const float q = (float)ff;                 // non-negative floats order like their bit patterns (k_cell_refresh)
+  fbits[i] = q >= 0.f && q <= 3.0e38f ? float_bits(q) : 0x7fffffff;
+  if (p.frame_every > 0 && n % p.frame_every == 0) {
+    double *row = frames + ((size_t)(n / p.frame_every) * (size_t)natoms + (size_t)i) * 3;
+    for (int d = 0; d < 3; ++d) row[d] = x[3 * i + d];
+  }
+}
+__global__ void k_md_decide(MdState *st, MdPar p, const double *engvir, double *thermo) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || st->status != MD_RUNNING) return;
+  const double u2 = (double)bits_float(st->ubits), f2 = (double)bits_float(st->fbits);
+  st->u2 = u2; st->fmax2 = f2;
+  if (st->ubits == 0x7fffffff) { st->status = MD_NONFINITE; return; }
+  if (2.0 * sqrt(u2) > p.skin) { st->status = MD_NEED_REBUILD; return; }
+  if (st->fbits == 0x7fffffff || !isfinite(st->sums[0]) || !isfinite(engvir[0])) { st->status = MD_NONFINITE; return; }
+  const int n = st->n;
+  if (n % p.sample_every == 0) {
+    double *row = thermo + 8 * (size_t)(n / p.sample_every);
+    row[0] = engvir[0];
+    row[1] = 0.5 * p.mvv2e * st->sums[0];
+    for (int k = 0; k < 6; ++k) row[2 + k] = engvir[1 + k];
+  }
+  if (n == p.nsteps) { st->status = MD_DONE; return; }
+  st->n = n + 1;
+}
+// The move out of configuration n = st->n - 1 (the decision has counted it already): second half kick, half drift, thermostat, half drift of the row's source
+// atom, the row as k_relax_move writes it; atom rows also store x', w' and the displacement bits.  xin / win / vnow are never written by this launch.
+__global__ void k_md_move(int natoms, int nrows, const MdState *st, MdPar p, const double *xin, const double *vnow, const double *f, const double *mass,
+                          const int *fixed, const double *xhold, const long long *src, const int *img, CellGeom g, double *xout, double *wout, double *x, int *disp) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nrows || st->status != MD_RUNNING) return;
+  const long long a = r < natoms ? r : src[r - natoms];
+  const bool fix = fixed && fixed[a];
+  const double ma = mass[a], k = p.hdtf / ma, hdt = 0.5 * p.dt;
+  double xi[3] = {0.0, 0.0, 0.0}, sig = 0.0;
+  if (p.gamma > 0.0 && !fix) {
+    md_xi(p.seed, a, p.step0 + (unsigned long long)(st->n - 1), xi);
+    sig = p.c2 * sqrt(p.kT / (ma * p.mvv2e));
+  }
+  double xn[3], wn[3], dx[3];
+  for (int d = 0; d < 3; ++d) {
+    const double vh = vnow[3 * a + d] + k * f[3 * a + d];
+    const double xh = xin[3 * a + d] + hdt * vh;
+    wn[d] = fix ? 0.0 : (p.gamma > 0.0 ? p.c1 * vh + sig * xi[d] : vh);
+    xn[d] = fix ? xin[3 * a + d] : xh + hdt * wn[d];
+    dx[d] = xn[d] - xhold[3 * a + d];
+  }
+  double c[3];                               // the row is x'_a + c . A
+  for (int d = 0; d < 3; ++d) c[d] = g.pbc[d] ? -floor(cell_frac(g, dx, d) + 0.5) : 0.0;
+  if (r < natoms) {
+    double u2 = 0.0;
+    for (int d = 0; d < 3; ++d) {
+      const double u = dx[d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+      u2 += u * u;
+      xout[3 * r + d] = xn[d]; wout[3 * r + d] = wn[d];
+    }
+    const float q = (float)u2 * 1.000001f;   // rounded up: the criterion must not miss
+    disp[r] = q >= 0.f && q <= 3.0e38f ? float_bits(q) : 0x7fffffff;
+  } else {
+    for (int d = 0; d < 3; ++d) c[d] += (double)img[3 * (r - natoms) + d];
+  }
+  for (int d = 0; d < 3; ++d) x[3 * r + d] = xn[d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+}
+void md_begin(Model &m, int natoms, const double *x_host, const double *v_host, const double *mass_host, const int *fixed_host, size_t thermo_rows, size_t frame_rows,
+              hipStream_t s) {
+  const size_t n = (size_t)std::max(natoms, 1);
+  for (int k = 0; k < 2; ++k) { m.q_x[k].reserve(n * 3 * sizeof(double)); m.q_v[k].reserve(n * 3 * sizeof(double)); }
+  m.q_vnow.reserve(n * 3 * sizeof(double));
+  m.q_mass.reserve(n * sizeof(double));
+  m.q_part.reserve(n * 3 * sizeof(double));
+  m.q_fbits.reserve(n * sizeof(int));
+  m.q_mstate.reserve(sizeof(MdState));
+  m.q_thermo.reserve(std::max<size_t>(thermo_rows, 1) * 8 * sizeof(double));
+  m.q_frames.reserve(std::max<size_t>(frame_rows * n * 3, 1) * sizeof(double));
+  m.q_fixed.release();                       // no mask: the kernels take a null pointer
+  if (natoms > 0) {
+    copy_h2d(m.q_x[0].p, x_host, (size_t)natoms * 3 * sizeof(double));
+    copy_h2d(m.q_v[0].p, v_host, (size_t)natoms * 3 * sizeof(double));
+    copy_h2d(m.q_mass.p, mass_host, (size_t)natoms * sizeof(double));
+    if (fixed_host) {
+      m.q_fixed.reserve(n * sizeof(int));
+      copy_h2d(m.q_fixed.p, fixed_host, (size_t)natoms * sizeof(int));
+    }
+  }
+  AHIP_CHECK(hipMemsetAsync(m.q_thermo.p, 0, std::max<size_t>(thermo_rows, 1) * 8 * sizeof(double), s));
+  MdState st{};
+  st.status = MD_RUNNING;
+  copy_h2d(m.q_mstate.p, &st, sizeof(st));
+}
+void md_step(Model &m, int in, const MdPar &p, bool move, hipStream_t s) {
+  const Model::CellHold &h = m.hold;
+  const int natoms = h.natoms, nrows = h.natoms + h.nghost;
+  if (natoms == 0) return;
+  const CellGeom g = cell_geometry("ahip_md_cell", h.cell, h.pbc, 0.0);
+  MdState *st = m.q_mstate.as<MdState>();
+  const double *f = m.c_f.as<double>(), *mass = m.q_mass.as<double>();
+  const int *fixed = m.q_fixed.as<int>();
+  hipLaunchKernelGGL(k_md_gather, dim3((unsigned)((natoms + 255) / 256)), dim3(256), 0, s, natoms, f, m.q_x[in].as<double>(), m.q_v[in].as<double>(), mass, fixed, st, p,
+                     m.q_vnow.as<double>(), m.q_part.as<double>(), m.q_fbits.as<int>(), m.q_frames.as<double>());
+  AHIP_CHECK(prim_sum_columns_f64(m.prim, m.q_part.as<double>(), natoms, 1, st->sums, s));
+  AHIP_CHECK(prim_max_i32(m.q_fbits.as<int>(), natoms, &st->fbits, s));
+  AHIP_CHECK(prim_max_i32(m.r_disp.as<int>(), natoms, &st->ubits, s));
+  hipLaunchKernelGGL(k_md_decide, dim3(1), dim3(64), 0, s, st, p, m.c_engvir.as<double>(), m.q_thermo.as<double>());
+  if (move)
+    hipLaunchKernelGGL(k_md_move, dim3((unsigned)(((long long)nrows + 255) / 256)), dim3(256), 0, s, natoms, nrows, st, p, m.q_x[in].as<double>(), m.q_vnow.as<double>(), f,
+                       mass, fixed, m.r_xhold.as<double>(), m.c_src.as<long long>(), m.r_img.as<int>(), g, m.q_x[in ^ 1].as<double>(), m.q_v[in ^ 1].as<double>(),
+                       m.c_x.as<double>(), m.r_disp.as<int>());
+  AHIP_CHECK(hipGetLastError());
+}
+MdState md_read(Model &m, hipStream_t s) {
+  AHIP_CHECK(hipStreamSynchronize(s));
+  AHIP_CHECK(hipGetLastError());
+  MdState st;
+  copy_d2h(&st, m.q_mstate.p, sizeof(st));
+  return st;
+}
+void md_resume(Model &m, hipStream_t s) {
+  const int running = MD_RUNNING;
+  AHIP_CHECK(hipStreamSynchronize(s));
+  copy_h2d(&m.q_mstate.as<MdState>()->status, &running, sizeof(int));
+}
+void md_noise(unsigned long long seed, unsigned long long step, int n, double *out_dev, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_md_noise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seed, step, n, out_dev);
+  AHIP_CHECK(hipGetLastError());
+}
+
 // ---- a batch of cells as ONE non-periodic cloud (ahip_compute_cells) ----
 // Every structure keeps its own frame for the wrap and for its ghost images; only before the list build is every row (atom or ghost) translated by its
 // structure's origin, chosen on the host so that rows of different structures are farther apart than the list cutoff.  Behind that the batch is one list of

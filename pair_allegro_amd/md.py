@@ -29,9 +29,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-FTM2V = 1.0 / 1.0364269e-4          # metal units: (eV/A)/(g/mol) -> A/ps^2
-MVV2E = 1.0364269e-4
-KB = 8.617343e-5
+from .units import FTM2V, KB, MVV2E, maxwell_boltzmann  # noqa: F401  (they live in units.py, which does not import torch; re-exported here)
 
 
 def choose_grid(nranks: int) -> Tuple[int, int, int]:
@@ -920,11 +918,3 @@ class HostStagedDist:
 
     def barrier(self):
         self.d.barrier()
-
-
-def maxwell_boltzmann(n: int, mass: np.ndarray, temperature: float, seed: int) -> np.ndarray:
-    rng = np.random.RandomState(seed)
-    sigma = np.sqrt(KB * temperature / (mass * MVV2E))
-    v = rng.normal(size=(n, 3)) * sigma[:, None]
-    v -= (v * mass[:, None]).sum(0) / mass.sum()
-    return v
