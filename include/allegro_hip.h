@@ -587,6 +587,69 @@ int ahip_md_cell(ahip_model *m, int natoms, double *x, double *v, const int *mty
                  double *thermo, double *frames, int *evaluations, int *rebuilds);
 int ahip_debug_md_noise(unsigned long long seed, unsigned long long step, int n, double *out /* [n][3] */);
 
+/* MOLECULAR DYNAMICS AT CONSTANT PRESSURE in one call: the BAOAB of ahip_md_cell inside an isotropic stochastic cell rescaling (Bernetti and Bussi, J. Chem. Phys.
+ * 153, 114107 (2020), in its epsilon = ln V form, Euler step), with the integrator's state, the barostat's decision, the cell and its inverse on the device: the
+ * host does not look between steps.  HOST pointers; arguments, argument errors, md.* and the outputs are those of ahip_md_cell, and besides: an open axis,
+ * natoms == 0, cell_out == NULL, a pressure that is not finite, a compressibility or tau_p that is not finite and > 0, frame_cells != NULL with frame_every == 0
+ * (it may be NULL otherwise), and md.kT, which is ALWAYS read because it sets the barostat's noise: kT = 0 gives the deterministic (Berendsen-limit) barostat,
+ * gamma = 0 keeps the particles on velocity Verlet.  All of them are AHIP_ERR_ARG before any launch, with x, v, cell_out and f untouched and a held list as it was.
+ *   cell      [9]  in: the start, rows = lattice vectors;   cell_out [9]: the cell after nsteps steps
+ *   x, v      in: the start; out: the state after nsteps steps in cell_out.  x is NEVER wrapped.
+ *   fixed     non-zero = the atom follows the cell affinely (its reduced coordinates never change, as a fixed atom of ahip_relax_vcell), has v = 0, no part in ke
+ *   f, eatom (or NULL), eng, virial (or NULL): those of the returned x in cell_out
+ *   thermo [nsteps / sample_every + 1][10] or NULL: {pe, ke, vxx, vyy, vzz, vxy, vxz, vyz, V, P};   frames as in ahip_md_cell;
+ *   frame_cells [nsteps / frame_every + 1][9] or NULL: the cell of every frame
+ * ALGORITHM.  Configuration n has the cell A_n, the forces F_n and the virial W_n (in the sign this library reports, as W_ext = W - p V I of ahip_relax_vcell
+ * uses it) of its evaluation.  U, g_d, M_d and h0_d are those of ahip_relax_vcell: the displacement by minimum image in A_n against the rows of the last rebuild
+ * (squared, float32, rounded up), g_d = |a_d - a_d(hold)| against the cell of the last rebuild.  Each iteration runs three kernels.
+ * 1. k_npt_gather, one thread per atom: v_n and what goes with it, exactly as k_md_gather.  The reductions follow.
+ * 2. k_npt_decide, one thread, the only device writer of the state.  In this order:
+ *      1. U is not finite                                                          -> NONFINITE
+ *      2. not (2 U + sum_d M_d g_d <= skin and sum_d g_d <= min_d h0_d)            -> NEED_REBUILD (the forces just computed are discarded, no thermo row is
+ *         written and nothing advances)
+ *      3. the ke sum, max |F_i|^2, pe, V = |det A_n| or P is not finite, or V <= 0 -> NONFINITE;   ke = 0.5 mvv2e sum_i m_i |v_n,i|^2,
+ *         P = (2 ke + W_xx + W_yy + W_zz) / (3 V)
+ *      4. n % sample_every == 0: the thermo row;  n % frame_every == 0: the frame's cell
+ *      5. n == nsteps                                                              -> DONE
+ *      6. d eps = -(beta_T / tau_p) (P0 - P) dt + sqrt(2 kT beta_T dt / (V tau_p)) xi_V(step0 + n);   mu = exp(d eps / 3);   A_n+1 = mu A_n entry by entry.
+ *         If mu is not finite or A_n+1 is singular, nothing moves                  -> NONFINITE
+ *         else mu, A_n+1 and its inverse go into the state block, n += 1 and the move happens.
+ * 3. k_npt_move, one thread per row (atoms, then ghosts), on the row's source atom a: (x', w') of k_md_move, then x'' = mu x', w'' = w' / mu (a fixed atom:
+ *    x'' = mu x_a, w'' = 0).  The row is written as the exact periodic image in A_n+1 against the rows of the last rebuild, the way k_vcell_move writes it, with
+ *    the displacement bits rounded up.  No thread reads what another thread of the same launch writes.
+ * Once the status is not RUNNING, all three kernels return at once.
+ * NOISE.  xi_V(step) is the first component of the xi of ahip_md_cell at the atom word 0xFFFFFFFF (natoms is an int: no atom has it).  It depends on (seed, step)
+ * only: not on check_every, on rebuilds, on the degradation replay, or on how a trajectory is cut into calls.  With kT = 0 it is not drawn.
+ * ahip_debug_npt_noise runs exactly this device function (out [1], HOST).
+ * HOST.  The loop of ahip_md_cell.  At NEED_REBUILD the host takes the cell from the state block it has just read and builds rows, list and hold from the device
+ * positions in that cell; w and n stay as they were.  NONFINITE, the float16-range alarm and an inactive type: exactly as in ahip_md_cell (nothing written to x, v,
+ * cell_out or f).  The final iteration is gather, reduce, decide only.  The evaluation count follows the rule stated there.
+ * On success the model holds the list of the last rebuild: ahip_compute_cell_reuse at the returned x and cell_out with the same skin runs on it, and a following
+ * ahip_npt_cell with the returned x, v, cell_out and step0 + nsteps continues the trajectory (its first thermo row is this call's last).
+ * DEFAULTS.  compressibility 1.6 A^3/eV (a bulk modulus of 100 GPa = 0.624 eV/A^3: a typical metal or semiconductor; water is some 70 A^3/eV); tau_p 1 ps.  Only
+ * beta_T / tau_p enters the drift, so a wrong compressibility merely rescales the relaxation time.
+ * Measured on one MI355X (tools/npt_cost.py, profiles/npt_cost.txt): 200 steps of 0.001 ps from 300 K and a 0.05 A jitter at skin 1.0 A, float32 model S at
+ * the virial pressure of the start, beta_T 1.6 A^3/eV, tau_p 0.1 ps, a thermo row per step, host clock per step, against the same algorithm in numpy over
+ * Calculator(reuse=True).compute (the random-weight model has no stable volume: V / V0 reaches 1.12 to 1.13 on both routes).  64-atom Si cell: deterministic
+ * barostat over velocity Verlet 174.6 / 155.3 / 188.1 us at check_every 1 / 4 / 16 against 263.7 us (10 rebuilds; 219 / 233 / 313 evaluations), stochastic barostat
+ * over Langevin (gamma 5 / ps) 170.8 / 152.6 / 177.6 us against 260.4 us (9 rebuilds; 217 / 229 / 293 evaluations).  10 648-atom Si box: deterministic 633.9 /
+ * 657.6 / 1005.7 us against 1511.1 us (26 rebuilds; 251 / 276 / 450 evaluations), stochastic 648.3 / 668.0 / 1019.7 us against 1944.2 us (25 rebuilds; 248 / 272 /
+ * 446 evaluations).  At the default check_every 4 not slower than the Python loop at either size (1.70x, 1.71x, 2.30x, 2.91x); a cell that grows this fast rebuilds
+ * every 8 steps, so on the large box check_every 1 is the fastest and 16 wastes more evaluations than it saves synchronisations, while staying faster than the
+ * loop.  The deterministic end points (positions and cell) of the two routes agree to 9e-15 A (64 atoms) and 5e-9 A (10 648 atoms, float32 forces summed in
+ * another order). */
+typedef struct ahip_npt_params {
+  ahip_md_params md;        /* everything of ahip_md_cell, same meaning and ranges; kT is always read */
+  double pressure;          /* P0, energy / volume (metal: eV/A^3); finite */
+  double compressibility;   /* beta_T, volume / energy; > 0, finite */
+  double tau_p;             /* barostat relaxation time; > 0, finite */
+} ahip_npt_params;
+int ahip_npt_params_default(ahip_npt_params *p);   /* ahip_md_params_default; pressure 0, compressibility 1.6 A^3/eV, tau_p 1 ps */
+int ahip_npt_cell(ahip_model *m, int natoms, double *x, double *v, const int *mtype, const double *mass, const double *cell, const int *pbc,
+                  double skin, const int *fixed, const ahip_npt_params *p, double *cell_out, double *f, double *eatom, double *eng, double *virial,
+                  double *thermo /* [.][10] */, double *frames, double *frame_cells /* [.][9] */, int *evaluations, int *rebuilds);
+int ahip_debug_npt_noise(unsigned long long seed, unsigned long long step, double *out /* [1] */);
+
 /* A BATCH of structures in one call: what ahip_compute_cell computes for each of `nstruct` structures alone, with one upload, one ghost build, one neighbor
  * list and one evaluation for all of them (a data set of small cells is launch- and synchronisation-bound one structure at a time).  HOST pointers.
  *   first  [nstruct + 1], first[0] = 0, non-decreasing: structure s owns the atoms first[s] .. first[s+1] - 1 (an empty structure is allowed; nstruct == 0 too)

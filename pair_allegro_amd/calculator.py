@@ -9,6 +9,7 @@
     out = calc.relax(cell, positions, symbols, fmax=0.05)            # a FIRE relaxation at fixed cell in one library call (ahip_relax_cell): out["positions"]
     out = calc.relax(cell, positions, symbols, variable_cell=True, pressure=0.01)      # ... of positions and cell (ahip_relax_vcell): out["cell"] too
     out = calc.md(cell, positions, symbols, steps=1000, dt=0.001, temperature=300.0, friction=5.0)      # MD in one library call (ahip_md_cell): out["thermo"]
+    out = calc.md(cell, positions, symbols, steps=1000, temperature=300.0, friction=5.0, pressure=0.0, compressibility=1.6, tau_p=1.0)     # ... at constant pressure (ahip_npt_cell): out["cell"]
 
 Any cell works: triclinic, thinner than the cutoff (several images per direction), open axes.  No ASE import: an ASE calculator is three lines
 around `compute(atoms.cell.array, atoms.positions, atoms.get_chemical_symbols(), atoms.pbc)`.
@@ -142,7 +143,8 @@ class Calculator:
 
     def md(self, cell, positions, symbols: Sequence[str], pbc: Sequence[bool] = (True, True, True), steps: int = 100, dt: float = 0.001, velocities=None,
            temperature: Optional[float] = None, friction: float = 0.0, seed: int = 0, step0: int = 0, masses: Optional[dict] = None, fixed=None,
-           sample_every: int = 1, frame_every: int = 0, check_every: int = 4) -> dict:
+           sample_every: int = 1, frame_every: int = 0, check_every: int = 4, pressure: Optional[float] = None, compressibility: Optional[float] = None,
+           tau_p: Optional[float] = None) -> dict:
         """Molecular dynamics with the integrator's state on the device, one library call (ahip_md_cell; include/allegro_hip.h states the algorithm): `steps`
         steps of `dt`, NVE (velocity Verlet) when `friction` is 0, else Langevin dynamics by BAOAB at `temperature` with friction `friction`.  Metal units: A, eV,
         ps, amu, K, 1 / ps.  `velocities` [n][3] in A / ps; None draws Maxwell-Boltzmann velocities at `temperature` with zero total momentum from `seed`.
@@ -154,9 +156,23 @@ class Calculator:
 
         Returns the dict of `compute` at the final positions plus positions (never wrapped) and velocities [n][3]; thermo: a dict of arrays step, pe, ke,
         temperature = 2 ke / (3 N_free kB) and virial [.][6]; frames [.][n][3] or None; info gains steps, evaluations and rebuilds.  Needs a calculator with
-        skin > 0, like `relax`; a later `compute` of a reuse=True calculator goes on from the hold of the run."""
+        skin > 0, like `relax`; a later `compute` of a reuse=True calculator goes on from the hold of the run.
+
+        `pressure` (eV/A^3) makes it MD at constant pressure (ahip_npt_cell, all axes periodic): an isotropic stochastic cell rescaling around the same
+        integrator, with `compressibility` (A^3/eV; 1.6 is a solid of 100 GPa bulk modulus) and the relaxation time `tau_p` (ps), both required.  The barostat's
+        noise is that of `temperature`: None or 0 gives the deterministic (Berendsen-limit) barostat; `friction` 0 keeps the particles on velocity Verlet.  The
+        result gains cell [3][3] and frame_cells [.][3][3] (None without frames), thermo gains volume and pressure, positions, velocities and stress are those
+        in the returned cell, and a fixed atom follows the cell affinely.  A continuation carries the cell over with positions, velocities and `step0`."""
         if not self.skin > 0:
             raise ValueError("md needs a calculator with skin > 0: the skin is what the atoms may move through before the neighbor list is rebuilt")
+        if pressure is None:
+            if compressibility is not None or tau_p is not None:
+                raise ValueError("compressibility and tau_p belong to a run with a pressure")
+        else:
+            if not all(bool(p) for p in pbc):
+                raise ValueError("md at a pressure needs all three axes periodic: the cell rescaling is isotropic")
+            if compressibility is None or tau_p is None:
+                raise ValueError("md at a pressure needs compressibility and tau_p")
         cell = np.asarray(cell, dtype=np.float64)
         pos = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
         if len(symbols) != len(pos):
@@ -173,19 +189,28 @@ class Calculator:
         vel = np.asarray(velocities, dtype=np.float64).reshape(-1, 3)
         if len(vel) != len(pos):
             raise ValueError("positions and velocities differ in length")
-        x, v, energy, forces, eatom, vir, th, frames, minfo = self.model.md_cell(
-            pos, vel, mt, mass, cell, pbc, self.skin, fixed=fixed, nsteps=int(steps), dt=float(dt), gamma=float(friction), kT=KB * float(temperature or 0.0),
-            seed=int(seed), step0=int(step0), ftm2v=FTM2V, mvv2e=MVV2E, sample_every=int(sample_every), frame_every=int(frame_every), check_every=int(check_every))
+        par = dict(nsteps=int(steps), dt=float(dt), gamma=float(friction), kT=KB * float(temperature or 0.0), seed=int(seed), step0=int(step0), ftm2v=FTM2V,
+                   mvv2e=MVV2E, sample_every=int(sample_every), frame_every=int(frame_every), check_every=int(check_every))
+        if pressure is None:
+            x, v, energy, forces, eatom, vir, th, frames, minfo = self.model.md_cell(pos, vel, mt, mass, cell, pbc, self.skin, fixed=fixed, **par)
+        else:
+            x, v, energy, forces, eatom, vir, th, frames, minfo, cell, frame_cells = self.model.npt_cell(
+                pos, vel, mt, mass, cell, pbc, self.skin, fixed=fixed, pressure=float(pressure), compressibility=float(compressibility), tau_p=float(tau_p), **par)
         nfree = len(pos) - (int(np.count_nonzero(np.asarray(fixed).astype(bool))) if fixed is not None else 0)
         thermo = dict(step=int(step0) + int(sample_every) * np.arange(len(th)), pe=th[:, 0].copy(), ke=th[:, 1].copy(),
-                      temperature=2.0 * th[:, 1] / (3.0 * max(nfree, 1) * KB), virial=th[:, 2:].copy())
+                      temperature=2.0 * th[:, 1] / (3.0 * max(nfree, 1) * KB), virial=th[:, 2:8].copy())
+        if pressure is not None:
+            thermo.update(volume=th[:, 8].copy(), pressure=th[:, 9].copy())
         rows = self.model.last_cell_rows() if len(pos) else np.zeros(0, dtype=np.int64)
         stress = None
         if all(pbc):
             vm = np.array([[vir[0], vir[3], vir[4]], [vir[3], vir[1], vir[5]], [vir[4], vir[5], vir[2]]])
             stress = -vm / abs(np.linalg.det(cell))
         info = dict(path=self.model.last_path, nghost=int(len(rows) - len(pos)), nedges=self.model.nedges() if len(pos) else 0, row_atom=rows, **minfo)
-        return dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, positions=x, velocities=v, thermo=thermo, frames=frames, info=info)
+        out = dict(energy=energy, forces=forces, atomic_energy=eatom, virial=vir, stress=stress, positions=x, velocities=v, thermo=thermo, frames=frames, info=info)
+        if pressure is not None:
+            out.update(cell=cell, frame_cells=frame_cells)
+        return out
 
     def compute_many(self, structures: Sequence, max_atoms: int = 1 << 20) -> list:
         """A data set in as few library calls as possible (ahip_compute_cells: one upload, one ghost build, one neighbor list and one evaluation per call,

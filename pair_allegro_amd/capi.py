@@ -45,6 +45,7 @@ SYMBOLS = [
     "ahip_relax_params_default", "ahip_relax_cell",
     "ahip_vcell_params_default", "ahip_relax_vcell",
     "ahip_md_params_default", "ahip_md_cell", "ahip_debug_md_noise",
+    "ahip_npt_params_default", "ahip_npt_cell", "ahip_debug_npt_noise",
 ]
 
 
@@ -63,6 +64,11 @@ class MdParams(C.Structure):
     """ahip_md_params (include/allegro_hip.h)"""
     _fields_ = [("nsteps", C.c_int), ("check_every", C.c_int), ("sample_every", C.c_int), ("frame_every", C.c_int), ("dt", C.c_double), ("ftm2v", C.c_double),
                 ("mvv2e", C.c_double), ("gamma", C.c_double), ("kT", C.c_double), ("seed", C.c_ulonglong), ("step0", C.c_ulonglong)]
+
+
+class NptParams(C.Structure):
+    """ahip_npt_params (include/allegro_hip.h)"""
+    _fields_ = [("md", MdParams), ("pressure", C.c_double), ("compressibility", C.c_double), ("tau_p", C.c_double)]
 
 
 class XferOp(C.Structure):
@@ -213,6 +219,13 @@ class Library:
         self.lib.ahip_debug_md_noise.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_int, C.POINTER(C.c_double)]
         self.check(self.lib.ahip_debug_md_noise(int(seed), int(step), n, _p(out, C.c_double)))
         return out
+
+    def debug_npt_noise(self, seed: int, step: int) -> float:
+        """xi_V of one step, by the device function the decision of ahip_npt_cell uses (ahip_debug_npt_noise)"""
+        out = np.zeros(1)
+        self.lib.ahip_debug_npt_noise.argtypes = [C.c_ulonglong, C.c_ulonglong, C.POINTER(C.c_double)]
+        self.check(self.lib.ahip_debug_npt_noise(int(seed), int(step), _p(out, C.c_double)))
+        return float(out[0])
 
     def check(self, rc: int) -> None:
         if rc != 0:
@@ -596,6 +609,76 @@ class Model:
     def debug_md_noise(self, seed: int, step: int, n: int) -> np.ndarray:
         """xi of atoms 0 .. n-1 at one step [n][3], by the device function the Langevin move uses (ahip_debug_md_noise; the call needs no model)"""
         return self.L.debug_md_noise(seed, step, n)
+
+    def npt_params(self, **par) -> NptParams:
+        """the library's defaults (ahip_npt_params_default) with the named fields replaced: pressure, compressibility, tau_p and those of its ahip_md_params; an
+        unknown name is a TypeError"""
+        p = NptParams()
+        self.L.lib.ahip_npt_params_default.argtypes = [C.POINTER(NptParams)]
+        self.L.check(self.L.lib.ahip_npt_params_default(C.byref(p)))
+        md = {n for n, _ in MdParams._fields_}
+        own = {n for n, _ in NptParams._fields_} - {"md"}
+        for k, v in par.items():
+            if k in own:
+                setattr(p, k, v)
+            elif k in md:
+                setattr(p.md, k, v)
+            else:
+                raise TypeError(f"unknown NPT parameter {k!r} (known: {', '.join(sorted(own | md))})")
+        return p
+
+    def npt_cell(self, x: np.ndarray, v: np.ndarray, mtype: np.ndarray, mass: np.ndarray, cell, pbc=(True, True, True), skin: float = 1.0, fixed=None,
+                 want_eatom: bool = True, want_thermo: bool = True, want_frame_cells: bool = True, x_inout: Optional[np.ndarray] = None,
+                 v_inout: Optional[np.ndarray] = None, f: Optional[np.ndarray] = None, cell_out: Optional[np.ndarray] = None, params=None, **par):
+        """MD at constant pressure on the device (ahip_npt_cell): the BAOAB of md_cell inside an isotropic stochastic cell rescaling.  `par`: pressure,
+        compressibility, tau_p and the fields of ahip_md_params; `params`: a ready NptParams instead, or False for a NULL pointer.  Returns (x, v, energy, forces,
+        atomic energies or None, virial [6], thermo [nsteps / sample_every + 1][10] or None, frames or None, info, cell [3][3], frame_cells [.][3][3] or None) with
+        info = dict(steps, evaluations, rebuilds).  The positions are never wrapped.  `x_inout` / `v_inout` / `f` / `cell_out`: the arrays the library itself reads
+        and writes; `cell_out=False` passes a NULL pointer."""
+        c, p = self._cell_args(cell, pbc)
+        xr = np.array(x, dtype=np.float64).reshape(-1, 3) if x_inout is None else x_inout
+        vr = np.array(v, dtype=np.float64).reshape(-1, 3) if v_inout is None else v_inout
+        mt = np.ascontiguousarray(mtype, dtype=np.int32).reshape(-1)
+        ms = np.ascontiguousarray(mass, dtype=np.float64).reshape(-1)
+        n = len(xr)
+        if len(mt) != n or len(ms) != n:
+            raise ValueError("positions, types and masses differ in length")
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.int32).reshape(-1)
+            if len(fx) != n:
+                raise ValueError("positions and the fixed mask differ in length")
+        f = np.zeros((n, 3)) if f is None else f
+        for a in (xr, vr, f):
+            if a.dtype != np.float64 or not a.flags.c_contiguous or a.shape != (n, 3):
+                raise ValueError("x_inout, v_inout and f must be C-contiguous float64 arrays of shape [n][3]")
+        co = None if cell_out is False else (np.zeros((3, 3)) if cell_out is None else cell_out)
+        if co is not None and (co.dtype != np.float64 or not co.flags.c_contiguous or co.shape != (3, 3)):
+            raise ValueError("cell_out must be a C-contiguous float64 array of shape [3][3]")
+        mp = self.npt_params(**par) if params is None else params
+        if mp is False:
+            mp_ref, thermo, frames, fcells, nsteps = None, None, None, None, 0
+        else:
+            mp_ref, nsteps, md = C.byref(mp), int(mp.md.nsteps), mp.md
+            ok = nsteps >= 0 and md.sample_every >= 1 and md.frame_every >= 0          # (a range the library refuses: no buffer can be sized, it gets none)
+            thermo = np.zeros((nsteps // md.sample_every + 1, 10)) if want_thermo and ok else None
+            frames = np.zeros((nsteps // md.frame_every + 1, n, 3)) if ok and md.frame_every > 0 else None
+            fcells = np.zeros((nsteps // md.frame_every + 1, 3, 3)) if ok and md.frame_every > 0 and want_frame_cells else None
+        ea = np.zeros(n) if want_eatom else None
+        eng = C.c_double(0)
+        vir = np.zeros(6)
+        nev, nreb = C.c_int(0), C.c_int(0)
+        D, I = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        self.L.lib.ahip_npt_cell.argtypes = [C.c_void_p, C.c_int, D, D, I, D, D, I, C.c_double, I, C.POINTER(NptParams), D, D, D, D, D, D, D, D, I, I]
+        self.L.check(self.L.lib.ahip_npt_cell(self.h, n, _p(xr, C.c_double), _p(vr, C.c_double), _p(mt, C.c_int), _p(ms, C.c_double), _p(c, C.c_double), _p(p, C.c_int),
+                                               float(skin), _p(fx, C.c_int), mp_ref, _p(co, C.c_double), _p(f, C.c_double), _p(ea, C.c_double), C.byref(eng),
+                                               _p(vir, C.c_double), _p(thermo, C.c_double), _p(frames, C.c_double), _p(fcells, C.c_double), C.byref(nev), C.byref(nreb)))
+        info = dict(steps=nsteps, evaluations=nev.value, rebuilds=nreb.value)
+        return xr, vr, eng.value, f, ea, vir, thermo, frames, info, co, fcells
+
+    def debug_npt_noise(self, seed: int, step: int) -> float:
+        """xi_V of one step (ahip_debug_npt_noise; the call needs no model)"""
+        return self.L.debug_npt_noise(seed, step)
 
     def cell_reuse_reset(self) -> None:
         """drop the held list (and the counters): the next compute_cell_reuse rebuilds"""

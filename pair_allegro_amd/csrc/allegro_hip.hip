@@ -256,7 +256,7 @@ void ahip_model_free(ahip_model *m) {
                     &m->b_ws, &m->b_misc, &m->b_chk, &m->hv_eoff, &m->hv_eii, &m->hv_ej, &m->hv_rvec, &m->hv_ilist, &m->hv_engvir, &m->b_tile_a0, &m->b_tile_e0, &m->b_centre, &m->b_ntiles, &m->b_vatom,
                     &m->lt_eoff, &m->lt_eii, &m->lt_ej, &m->lt_rvec, &m->lt_ilist, &m->c_x, &m->c_mtype, &m->c_f, &m->c_eatom, &m->c_src, &m->c_shift, &m->c_engvir, &m->c_in, &m->c_xp, &m->c_out, &m->r_xin, &m->r_xhold, &m->r_img, &m->r_disp,
                     &m->q_x[0], &m->q_x[1], &m->q_v[0], &m->q_v[1], &m->q_fixed, &m->q_part, &m->q_fbits, &m->q_state, &m->q_g, &m->q_xc, &m->q_vstate, &m->q_vnow, &m->q_mass, &m->q_mstate,
-                    &m->q_thermo, &m->q_frames})
+                    &m->q_thermo, &m->q_frames, &m->q_nstate, &m->q_nthermo, &m->q_fcells})
     b->release();
   for (auto &t : m->slots) for (auto &e : t.ring) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (hipEvent_t e : m->f_events) (void)hipEventDestroy(e);
@@ -1806,6 +1806,29 @@ int ahip_md_params_default(ahip_md_params *p) {
   });
 }
 
+// the ranges of ahip_md_params and what ahip_md_cell asks of v, mass and frames (include/allegro_hip.h); read_kT: kT is part of this run
+static void md_check_args(const std::string &who, int natoms, const double *v, const double *mass, const ahip_md_params *p, const double *frames, bool read_kT) {
+  const auto positive = [](double q) { return std::isfinite(q) && q > 0.0; };
+  if (p->nsteps < 0) throw ArgError(who + ": nsteps must be >= 0");
+  if (p->check_every < 1) throw ArgError(who + ": check_every must be >= 1");
+  if (p->sample_every < 1) throw ArgError(who + ": sample_every must be >= 1");
+  if (p->frame_every < 0) throw ArgError(who + ": frame_every must be >= 0 (0: no frames)");
+  if (!positive(p->dt)) throw ArgError(who + ": dt must be a finite number > 0");
+  if (!positive(p->ftm2v) || !positive(p->mvv2e)) throw ArgError(who + ": ftm2v and mvv2e must be finite numbers > 0");
+  if (!std::isfinite(p->gamma) || p->gamma < 0.0) throw ArgError(who + ": gamma must be a finite number >= 0 (0: NVE)");
+  if (read_kT && (!std::isfinite(p->kT) || p->kT < 0.0)) throw ArgError(who + ": kT must be a finite number >= 0");
+  if ((frames != nullptr) != (p->frame_every > 0)) throw ArgError(who + ": frames must be NULL when frame_every is 0, and only then");
+  if (natoms > 0 && (!v || !mass)) throw ArgError(who + ": v or mass is NULL");
+  for (int i = 0; i < natoms; ++i) {
+    if (!positive(mass[i])) throw ArgError(who + ": the mass of atom " + std::to_string(i) + " is not a finite number > 0");
+    if (!std::isfinite(v[3 * i]) || !std::isfinite(v[3 * i + 1]) || !std::isfinite(v[3 * i + 2]))
+      throw ArgError(who + ": the velocity of atom " + std::to_string(i) + " is not finite");
+  }
+  const size_t frame_rows = p->frame_every > 0 ? (size_t)(p->nsteps / p->frame_every) + 1 : 0;
+  if ((double)frame_rows * (double)natoms * 3.0 * sizeof(double) > 1073741824.0)
+    throw ArgError(who + ": the frames of this call would take more than 1 GiB on the device: call again with fewer steps and carry x, v and step0 over");
+}
+
 // MD (NVE, or Langevin by BAOAB) with the integrator's state on the device (algorithm and statuses: include/allegro_hip.h; kernels: neigh.hip).  The loop is that
 // of ahip_relax_cell with a step count known in advance.  Nothing of the caller's is written before the last read-back has succeeded.
 int ahip_md_cell(ahip_model *m, int natoms, double *x, double *v, const int *mtype, const double *mass, const double *cell, const int *pbc, double skin,
@@ -1817,25 +1840,8 @@ int ahip_md_cell(ahip_model *m, int natoms, double *x, double *v, const int *mty
     const std::vector<int> present = cell_check_args(m, who, natoms, x, mtype, cell, pbc, skin, f, eng);
     if (!(skin > 0.0)) throw ArgError(who + ": skin must be > 0 (the skin is what the atoms may move through before the list is rebuilt)");
     if (!p) throw ArgError(who + ": p is NULL (ahip_md_params_default fills one)");
-    const auto positive = [](double q) { return std::isfinite(q) && q > 0.0; };
-    if (p->nsteps < 0) throw ArgError(who + ": nsteps must be >= 0");
-    if (p->check_every < 1) throw ArgError(who + ": check_every must be >= 1");
-    if (p->sample_every < 1) throw ArgError(who + ": sample_every must be >= 1");
-    if (p->frame_every < 0) throw ArgError(who + ": frame_every must be >= 0 (0: no frames)");
-    if (!positive(p->dt)) throw ArgError(who + ": dt must be a finite number > 0");
-    if (!positive(p->ftm2v) || !positive(p->mvv2e)) throw ArgError(who + ": ftm2v and mvv2e must be finite numbers > 0");
-    if (!std::isfinite(p->gamma) || p->gamma < 0.0) throw ArgError(who + ": gamma must be a finite number >= 0 (0: NVE)");
-    if (p->gamma > 0.0 && (!std::isfinite(p->kT) || p->kT < 0.0)) throw ArgError(who + ": kT must be a finite number >= 0");
-    if ((frames != nullptr) != (p->frame_every > 0)) throw ArgError(who + ": frames must be NULL when frame_every is 0, and only then");
-    if (natoms > 0 && (!v || !mass)) throw ArgError(who + ": v or mass is NULL");
-    for (int i = 0; i < natoms; ++i) {
-      if (!positive(mass[i])) throw ArgError(who + ": the mass of atom " + std::to_string(i) + " is not a finite number > 0");
-      if (!std::isfinite(v[3 * i]) || !std::isfinite(v[3 * i + 1]) || !std::isfinite(v[3 * i + 2]))
-        throw ArgError(who + ": the velocity of atom " + std::to_string(i) + " is not finite");
-    }
+    md_check_args(who, natoms, v, mass, p, frames, p->gamma > 0.0);
     const size_t thermo_rows = (size_t)(p->nsteps / p->sample_every) + 1, frame_rows = p->frame_every > 0 ? (size_t)(p->nsteps / p->frame_every) + 1 : 0;
-    if ((double)frame_rows * (double)natoms * 3.0 * sizeof(double) > 1073741824.0)
-      throw ArgError(who + ": the frames of this call would take more than 1 GiB on the device: call again with fewer steps and carry x, v and step0 over");
     (void)cell_geometry(who.c_str(), cell, pbc, 1.0);      // a singular or non-finite cell is refused here, with the hold as it was
     *eng = 0;
     if (virial) for (int k = 0; k < 6; ++k) virial[k] = 0;
@@ -1921,6 +1927,123 @@ int ahip_debug_md_noise(unsigned long long seed, unsigned long long step, int n,
       md_noise(seed, step, n, d.as<double>(), nullptr);
       AHIP_CHECK(hipStreamSynchronize(nullptr));
       copy_d2h(out, d.p, (size_t)n * 3 * sizeof(double));
+    } catch (...) { d.release(); throw; }
+    d.release();
+  });
+}
+
+int ahip_npt_params_default(ahip_npt_params *p) {
+  return guarded([&] {
+    if (!p) throw ArgError("ahip_npt_params_default: p is NULL");
+    *p = ahip_npt_params{ahip_md_params{0, 4, 1, 0, 0.001, 1.0 / 1.0364269e-4, 1.0364269e-4, 0.0, 0.0, 0ull, 0ull}, 0.0, 1.6, 1.0};
+  });
+}
+
+// MD at constant pressure with the integrator's and the barostat's state on the device (algorithm and statuses: include/allegro_hip.h; kernels: neigh.hip).  The
+// loop is that of ahip_md_cell; the cell of a rebuild is the one the state block holds.  Nothing of the caller's is written before the last read-back has succeeded.
+int ahip_npt_cell(ahip_model *m, int natoms, double *x, double *v, const int *mtype, const double *mass, const double *cell, const int *pbc, double skin,
+                  const int *fixed, const ahip_npt_params *p, double *cell_out, double *f, double *eatom, double *eng, double *virial, double *thermo, double *frames,
+                  double *frame_cells, int *evaluations, int *rebuilds) {
+  return guarded([&] {
+    require_model(m);
+    const std::string who = "ahip_npt_cell";
+    const std::vector<int> present = cell_check_args(m, who, natoms, x, mtype, cell, pbc, skin, f, eng);
+    if (!(skin > 0.0)) throw ArgError(who + ": skin must be > 0 (the skin is what the atoms and the cell may move through before the list is rebuilt)");
+    if (!p) throw ArgError(who + ": p is NULL (ahip_npt_params_default fills one)");
+    if (natoms == 0) throw ArgError(who + ": natoms is 0 (no atoms, no pressure)");
+    if (!cell_out) throw ArgError(who + ": cell_out is NULL");
+    if (!(pbc[0] && pbc[1] && pbc[2])) throw ArgError(who + ": all three axes must be periodic (the rescaling is isotropic)");
+    md_check_args(who, natoms, v, mass, &p->md, frames, true);
+    if (frame_cells && p->md.frame_every == 0) throw ArgError(who + ": frame_cells must be NULL when frame_every is 0");
+    if (!std::isfinite(p->pressure)) throw ArgError(who + ": pressure must be finite");
+    if (!std::isfinite(p->compressibility) || !(p->compressibility > 0.0)) throw ArgError(who + ": compressibility must be a finite number > 0");
+    if (!std::isfinite(p->tau_p) || !(p->tau_p > 0.0)) throw ArgError(who + ": tau_p must be a finite number > 0");
+    const ahip_md_params &q = p->md;
+    const size_t thermo_rows = (size_t)(q.nsteps / q.sample_every) + 1, frame_rows = q.frame_every > 0 ? (size_t)(q.nsteps / q.frame_every) + 1 : 0;
+    (void)cell_geometry(who.c_str(), cell, pbc, 1.0);      // a singular or non-finite cell is refused here, with the hold as it was
+    *eng = 0;
+    if (virial) for (int k = 0; k < 6; ++k) virial[k] = 0;
+    if (evaluations) *evaluations = 0;
+    if (rebuilds) *rebuilds = 0;
+    // Whatever fails from here on fails behind a launch and leaves nothing held.
+    m->hold.serial = 0;
+    AHIP_CHECK(hipSetDevice(m->device));
+    hipStream_t s = nullptr;
+    const double rc = *std::max_element(m->rcut_model_host.begin(), m->rcut_model_host.end()) + skin;
+    NptPar par{};
+    par.md.dt = q.dt; par.md.hdtf = 0.5 * q.dt * q.ftm2v; par.md.gamma = q.gamma; par.md.kT = q.kT; par.md.mvv2e = q.mvv2e; par.md.skin = skin;
+    par.md.c1 = std::exp(-q.gamma * q.dt); par.md.c2 = std::sqrt(1.0 - par.md.c1 * par.md.c1);
+    par.md.seed = q.seed; par.md.step0 = q.step0;
+    par.md.nsteps = q.nsteps; par.md.sample_every = q.sample_every; par.md.frame_every = q.frame_every;
+    par.p0 = p->pressure; par.beta_over_tau = p->compressibility / p->tau_p;
+    par.noise = std::sqrt(2.0 * q.kT * p->compressibility * q.dt / p->tau_p);
+    int n = 0, nev = 0, nreb = 0, ng = 0;
+    npt_begin(*m, natoms, x, v, mass, fixed, cell, thermo_rows, frame_rows, s);
+    NptState st = npt_read(*m, s);
+    // rows, list and hold from the positions on the device (those of configuration n) in the cell of the state block, then their forces
+    const auto rebuild = [&] {
+      ng = cell_rows(m, who, present, natoms, m->q_x[n & 1].as<double>(), true, mtype, st.geom.h, pbc, skin);
+      cell_hold_take(*m, natoms, ng, st.geom.h, pbc, skin, rc, s);
+      relax_rows_fresh(*m, natoms, s);
+      nev += cell_evaluate_dev(m, who, natoms, ng, s);
+      npt_held(*m, st, s);
+      ++nreb;
+    };
+    rebuild();
+    bool may_repeat = true;                   // NONFINITE or the alarm: once, under fused_arith=auto, the frozen configuration is evaluated again on the float32 instance
+    for (;;) {
+      const int chunk = std::min(q.check_every, q.nsteps - n);
+      for (int k = 0; k < chunk; ++k) {       // no wait in here
+        npt_step(*m, (n + k) & 1, par, true, s);
+        cell_evaluate_enqueue(m, natoms, ng, s);
+        ++nev;
+      }
+      if (n + chunk == q.nsteps) npt_step(*m, q.nsteps & 1, par, false, s);      // the last configuration is only checked and sampled: no evaluation behind it
+      st = npt_read(*m, s);
+      n = st.n;
+      if (const int bad = inactive_take(*m)) throw ArgError(who + ": " + inactive_message(*m, bad, "this evaluation") + " (nothing was written to x, v, cell_out or f)");
+      if (alarm_take(*m) || st.status == MD_NONFINITE) {
+        if (!(arith_may_degrade(*m) && may_repeat && m->last_path.find("f16x2") != std::string::npos))      // (no other arithmetic has a float32 instance to fall back to)
+          throw StateError(who + ": a force, the energy, the kinetic energy, the pressure, a displacement or the cell was not finite after " + std::to_string(n) +
+                           " steps (coincident atoms, an input that was not finite, a time step too large, a tau_p far too small, or an activation left float16's "
+                           "range): the forces of this evaluation are invalid and nothing was written to x, v, cell_out or f" +
+                           (arith_effective(m->arith.opt) == ArithOpt::F16x2 ? "; set option fused_arith=f32 (or auto) for this model" : ""));
+        may_repeat = false;
+        arith_degrade(*m, "an MD run met a non-finite force or the float16-range alarm; the configuration of its last valid step was evaluated again");
+        if (st.status != MD_NEED_REBUILD) {
+          nev += cell_evaluate_dev(m, who, natoms, ng, s);
+          npt_resume(*m, s);
+          continue;
+        }
+      }
+      if (st.status == MD_DONE) break;
+      if (st.status == MD_NEED_REBUILD) rebuild();
+    }
+    AHIP_CHECK(hipStreamSynchronize(s));
+    AHIP_CHECK(hipGetLastError());
+    copy_d2h(x, m->q_x[n & 1].p, (size_t)natoms * 3 * sizeof(double));
+    copy_d2h(v, m->q_vnow.p, (size_t)natoms * 3 * sizeof(double));
+    if (thermo) copy_d2h(thermo, m->q_nthermo.p, thermo_rows * 10 * sizeof(double));
+    if (frames) copy_d2h(frames, m->q_frames.p, frame_rows * (size_t)natoms * 3 * sizeof(double));
+    if (frame_cells) copy_d2h(frame_cells, m->q_fcells.p, frame_rows * 9 * sizeof(double));
+    cell_download(m, natoms, f, eatom, eng, virial);
+    std::copy(st.geom.h, st.geom.h + 9, cell_out);
+    if (evaluations) *evaluations = nev;
+    if (rebuilds) *rebuilds = nreb;
+    m->hold.mtype.assign(mtype, mtype + natoms);
+    m->hold.serial = m->list_serial;
+  });
+}
+
+int ahip_debug_npt_noise(unsigned long long seed, unsigned long long step, double *out) {
+  return guarded([&] {
+    if (!out) throw ArgError("ahip_debug_npt_noise: out is NULL");
+    DevBuf d;
+    d.reserve(sizeof(double));
+    try {
+      npt_noise(seed, step, d.as<double>(), nullptr);
+      AHIP_CHECK(hipStreamSynchronize(nullptr));
+      copy_d2h(out, d.p, sizeof(double));
     } catch (...) { d.release(); throw; }
     d.release();
   });

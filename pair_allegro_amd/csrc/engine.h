@@ -197,6 +197,8 @@ struct Model {
   // ahip_md_cell (neigh.hip: md_*): q_x holds the unwrapped positions and q_v the post-thermostat velocity w, as the relaxation holds x and v; besides, the
   // velocity v_n of the configuration whose forces are on the device, the masses, the MdState block, the thermo rows and the frames
   DevBuf q_vnow, q_mass, q_mstate, q_thermo, q_frames;
+  // ahip_npt_cell (neigh.hip: npt_*): the buffers of ahip_md_cell, and of its own the NptState block, thermo rows of ten columns and the cell of every frame
+  DevBuf q_nstate, q_nthermo, q_fcells;
 
   // edge list + workspace
   DevBuf b_cnt, b_eoff, b_eii, b_ej, b_rvec, b_partial, b_ws, b_misc;
@@ -538,6 +540,32 @@ void md_step(Model &m, int in, const MdPar &p, bool move, hipStream_t s);
 MdState md_read(Model &m, hipStream_t s);
 void md_resume(Model &m, hipStream_t s);
 void md_noise(unsigned long long seed, unsigned long long step, int n, double *out_dev, hipStream_t s);
+// MD at constant pressure on the device (ahip_npt_cell; algorithm: include/allegro_hip.h).  The BAOAB of ahip_md_cell inside an isotropic stochastic cell
+// rescaling, with the cell handling of ahip_relax_vcell; the kernels and state blocks of both are not touched.  NptState carries what MdState carries and,
+// because the host does not look between steps, the current cell with its geometry, the factor mu of the last rescaling, the hold (cell, M_d, min h0) the reuse
+// criterion is taken against, and V and P of the last decision.  k_npt_decide is its only writer on the device; the host writes it at the start and behind a
+// rebuild (npt_held), with the stream idle.  npt_begin: md_begin, the thermo rows of ten columns, the frame cells and the state block in `cell`; npt_step, npt_read,
+// npt_resume: as md_step, md_read, md_resume.  The positions that count after a read are q_x[state.n & 1], in the cell state.geom.h.  npt_noise: xi_V of one step.
+struct NptPar {
+  MdPar md;
+  double p0, beta_over_tau, noise;   // noise = sqrt(2 kT beta_T dt / tau_p): xi_V is scaled by noise / sqrt(V); 0 = no random number is drawn
+};
+struct NptState {
+  double u2, fmax2;                  // what the last decision saw: U^2 and max |F_i|^2 (float32 values)
+  double sums[1];                    // sum_i m_i |v_i|^2 (prim_sum_columns_f64)
+  double mu, V, P;                   // the factor of the last rescaling (1 before the first); volume and pressure of the last decision
+  double hold_cell[9], hold_images[3], hold_min_height;
+  CellGeom geom;                     // of the current cell; pbc all set
+  int status, n;                     // the statuses of MdState; n: the configuration whose forces are on the device, 0 .. nsteps
+  int fbits, ubits;
+};
+void npt_begin(Model &m, int natoms, const double *x_host, const double *v_host, const double *mass_host, const int *fixed_host, const double *cell, size_t thermo_rows,
+               size_t frame_rows, hipStream_t s);
+void npt_step(Model &m, int in, const NptPar &p, bool move, hipStream_t s);
+NptState npt_read(Model &m, hipStream_t s);
+void npt_held(Model &m, NptState st, hipStream_t s);
+void npt_resume(Model &m, hipStream_t s);
+void npt_noise(unsigned long long seed, unsigned long long step, double *out_dev, hipStream_t s);
 // A batch of cells as one non-periodic cloud (neigh.hip).  cells_plan is host-only and throws ArgError before any launch: per structure the geometry (a singular
 // or non-finite cell names its index), the 32-bit bound on atoms + images, the extent of its rows -- the Cartesian bounding box of its parallelepiped with the
 // fractional range [-m_d, 1 + m_d] on periodic axes and the range its atoms have on open ones -- and its origin: uniform slots of the largest extent plus

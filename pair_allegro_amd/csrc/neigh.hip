@@ -1072,6 +1072,190 @@ void md_noise(unsigned long long seed, unsigned long long step, int n, double *o
   AHIP_CHECK(hipGetLastError());
 }
 
+// ---- MD at constant pressure with its state on the device (ahip_npt_cell; the algorithm is stated in include/allegro_hip.h) ----
+// The BAOAB of the MD above inside an isotropic stochastic cell rescaling.  Per configuration n: k_npt_gather (one thread per atom), the reductions, k_npt_decide
+// (one thread, the only writer of the state: it also forms the rescaling factor, the next cell and its geometry, which the host has not seen), k_npt_move (one
+// thread per row, in the cell of the state block).  Every kernel returns at once when the status is not RUNNING, x and w alternate between two buffers, and no
+// kernel needs a barrier.
+#define NPT_NOISE_ATOM 0xFFFFFFFFll      // the atom word of xi_V: natoms is an int, so no atom has it
+// v_n, m |v_n|^2, the |F_i|^2 bits and the frame row of n, exactly as k_md_gather forms them
+__global__ void k_npt_gather(int natoms, const double *f, const double *x, const double *w, const double *mass, const int *fixed, const NptState *st, MdPar p,
+                             double *vnow, double *part, int *fbits, double *frames) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= natoms || st->status != MD_RUNNING) return;
+  const int n = st->n;
+  const bool fix = fixed && fixed[i];
+  const double k = n > 0 ? p.hdtf / mass[i] : 0.0;
+  double ff = 0.0, vv = 0.0;
+  for (int d = 0; d < 3; ++d) {
+    const double fd = f[3 * i + d], vd = fix ? 0.0 : w[3 * i + d] + k * fd;
+    vnow[3 * i + d] = vd;
+    vv += vd * vd;
+    if (!fix) ff += fd * fd;
+  }
+  part[i] = mass[i] * vv;
+  const float q = (float)ff;                 // non-negative floats order like their bit patterns (k_cell_refresh)
+  fbits[i] = q >= 0.f && q <= 3.0e38f ? float_bits(q) : 0x7fffffff;
+  if (p.frame_every > 0 && n % p.frame_every == 0) {
+    double *row = frames + ((size_t)(n / p.frame_every) * (size_t)natoms + (size_t)i) * 3;
+    for (int d = 0; d < 3; ++d) row[d] = x[3 * i + d];
+  }
+}
+__global__ void k_npt_decide(NptState *st, NptPar p, const double *engvir, double *thermo, double *fcells) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || st->status != MD_RUNNING) return;
+  const double u2 = (double)bits_float(st->ubits), f2 = (double)bits_float(st->fbits);
+  st->u2 = u2; st->fmax2 = f2;
+  // 1, 2: the largest displacement and the reuse criterion of ahip_compute_cell_reuse, the current cell against the cell of the last rebuild
+  if (st->ubits == 0x7fffffff) { st->status = MD_NONFINITE; return; }
+  double sum_g = 0.0, sum_mg = 0.0;
+  for (int d = 0; d < 3; ++d) {
+    double q = 0.0;
+    for (int k = 0; k < 3; ++k) { const double e = st->geom.h[3 * d + k] - st->hold_cell[3 * d + k]; q += e * e; }
+    sum_g += sqrt(q);
+    sum_mg += st->hold_images[d] * sqrt(q);
+  }
+  if (!(2.0 * sqrt(u2) + sum_mg <= p.md.skin) || !(sum_g <= st->hold_min_height)) { st->status = MD_NEED_REBUILD; return; }
+  // 3
+  const double V = fabs(det3(st->geom.h)), ke = 0.5 * p.md.mvv2e * st->sums[0];
+  const double P = (2.0 * ke + engvir[1] + engvir[2] + engvir[3]) / (3.0 * V);
+  if (st->fbits == 0x7fffffff || !isfinite(st->sums[0]) || !isfinite(engvir[0]) || !isfinite(V) || !(V > 0.0) || !isfinite(P)) { st->status = MD_NONFINITE; return; }
+  st->V = V; st->P = P;
+  // 4
+  const int n = st->n;
+  if (n % p.md.sample_every == 0) {
+    double *row = thermo + 10 * (size_t)(n / p.md.sample_every);
+    row[0] = engvir[0];
+    row[1] = ke;
+    for (int k = 0; k < 6; ++k) row[2 + k] = engvir[1 + k];
+    row[8] = V; row[9] = P;
+  }
+  if (p.md.frame_every > 0 && n % p.md.frame_every == 0)
+    for (int k = 0; k < 9; ++k) fcells[9 * (size_t)(n / p.md.frame_every) + k] = st->geom.h[k];
+  // 5
+  if (n == p.md.nsteps) { st->status = MD_DONE; return; }
+  // 6: d(ln V), the factor of the lattice vectors, the next cell with its inverse
+  double de = -p.beta_over_tau * (p.p0 - P) * p.md.dt;
+  if (p.noise > 0.0) {
+    double xi[3];
+    md_xi(p.md.seed, NPT_NOISE_ATOM, p.md.step0 + (unsigned long long)n, xi);
+    de += p.noise / sqrt(V) * xi[0];
+  }
+  const double mu = exp(de / 3.0);
+  double An[9];
+  for (int k = 0; k < 9; ++k) An[k] = mu * st->geom.h[k];
+  const int pbc[3] = {1, 1, 1};
+  CellGeom gn;
+  // a rescaling that is not finite, or into a cell that is singular, is not made: the state stays that of the last valid step
+  if (!isfinite(mu) || cell_geometry_try(An, pbc, 0.0, gn) != 0) { st->status = MD_NONFINITE; return; }
+  st->mu = mu;
+  st->geom = gn;
+  st->n = n + 1;
+}
+// The move out of configuration n = st->n - 1 (the decision has counted it already): the BAOAB move of k_md_move on the row's source atom, then x'' = mu x',
+// w'' = w' / mu (a fixed atom follows the cell: x'' = mu x, w'' = 0); the row as k_vcell_move writes it, the exact periodic image in the cell of the state block;
+// atom rows also store x'', w'' and the displacement bits.  xin / vnow are never written by this launch.
+__global__ void k_npt_move(int natoms, int nrows, const NptState *st, MdPar p, const double *xin, const double *vnow, const double *f, const double *mass,
+                           const int *fixed, const double *xhold, const long long *src, const int *img, double *xout, double *wout, double *x, int *disp) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nrows || st->status != MD_RUNNING) return;
+  const long long a = r < natoms ? r : src[r - natoms];
+  const bool fix = fixed && fixed[a];
+  const double ma = mass[a], k = p.hdtf / ma, hdt = 0.5 * p.dt, mu = st->mu;
+  const CellGeom &g = st->geom;
+  double xi[3] = {0.0, 0.0, 0.0}, sig = 0.0;
+  if (p.gamma > 0.0 && !fix) {
+    md_xi(p.seed, a, p.step0 + (unsigned long long)(st->n - 1), xi);
+    sig = p.c2 * sqrt(p.kT / (ma * p.mvv2e));
+  }
+  double xn[3], wn[3], dx[3];
+  for (int d = 0; d < 3; ++d) {
+    const double vh = vnow[3 * a + d] + k * f[3 * a + d];
+    const double xh = xin[3 * a + d] + hdt * vh;
+    const double wd = p.gamma > 0.0 ? p.c1 * vh + sig * xi[d] : vh;
+    wn[d] = fix ? 0.0 : wd / mu;
+    xn[d] = mu * (fix ? xin[3 * a + d] : xh + hdt * wd);
+    dx[d] = xn[d] - xhold[3 * a + d];
+  }
+  double c[3];                               // the row is x''_a + c . A'
+  for (int d = 0; d < 3; ++d) c[d] = -floor(cell_frac(g, dx, d) + 0.5);
+  if (r < natoms) {
+    double u2 = 0.0;
+    for (int d = 0; d < 3; ++d) {
+      const double u = dx[d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+      u2 += u * u;
+      xout[3 * r + d] = xn[d]; wout[3 * r + d] = wn[d];
+    }
+    const float q = (float)u2 * 1.000001f;   // rounded up: the criterion must not miss
+    disp[r] = q >= 0.f && q <= 3.0e38f ? float_bits(q) : 0x7fffffff;
+  } else {
+    for (int d = 0; d < 3; ++d) c[d] += (double)img[3 * (r - natoms) + d];
+  }
+  for (int d = 0; d < 3; ++d) x[3 * r + d] = xn[d] + (c[0] * g.h[d] + c[1] * g.h[3 + d] + c[2] * g.h[6 + d]);
+}
+__global__ void k_npt_noise(unsigned long long seed, unsigned long long step, double *out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double xi[3];
+  md_xi(seed, NPT_NOISE_ATOM, step, xi);
+  out[0] = xi[0];
+}
+void npt_begin(Model &m, int natoms, const double *x_host, const double *v_host, const double *mass_host, const int *fixed_host, const double *cell, size_t thermo_rows,
+               size_t frame_rows, hipStream_t s) {
+  md_begin(m, natoms, x_host, v_host, mass_host, fixed_host, thermo_rows, frame_rows, s);      // x, w = v, the masses, the mask, the frames
+  m.q_nstate.reserve(sizeof(NptState));
+  m.q_nthermo.reserve(std::max<size_t>(thermo_rows, 1) * 10 * sizeof(double));
+  m.q_fcells.reserve(std::max<size_t>(frame_rows, 1) * 9 * sizeof(double));
+  AHIP_CHECK(hipMemsetAsync(m.q_nthermo.p, 0, std::max<size_t>(thermo_rows, 1) * 10 * sizeof(double), s));
+  NptState st{};
+  st.mu = 1.0;
+  st.status = MD_RUNNING;
+  const int pbc[3] = {1, 1, 1};
+  st.geom = cell_geometry("ahip_npt_cell", cell, pbc, 0.0);
+  copy_h2d(m.q_nstate.p, &st, sizeof(st));
+}
+void npt_step(Model &m, int in, const NptPar &p, bool move, hipStream_t s) {
+  const int natoms = m.hold.natoms, nrows = m.hold.natoms + m.hold.nghost;
+  if (natoms == 0) return;
+  NptState *st = m.q_nstate.as<NptState>();
+  const double *f = m.c_f.as<double>(), *mass = m.q_mass.as<double>();
+  const int *fixed = m.q_fixed.as<int>();
+  hipLaunchKernelGGL(k_npt_gather, dim3((unsigned)((natoms + 255) / 256)), dim3(256), 0, s, natoms, f, m.q_x[in].as<double>(), m.q_v[in].as<double>(), mass, fixed, st, p.md,
+                     m.q_vnow.as<double>(), m.q_part.as<double>(), m.q_fbits.as<int>(), m.q_frames.as<double>());
+  AHIP_CHECK(prim_sum_columns_f64(m.prim, m.q_part.as<double>(), natoms, 1, st->sums, s));
+  AHIP_CHECK(prim_max_i32(m.q_fbits.as<int>(), natoms, &st->fbits, s));
+  AHIP_CHECK(prim_max_i32(m.r_disp.as<int>(), natoms, &st->ubits, s));
+  hipLaunchKernelGGL(k_npt_decide, dim3(1), dim3(64), 0, s, st, p, m.c_engvir.as<double>(), m.q_nthermo.as<double>(), m.q_fcells.as<double>());
+  if (move)
+    hipLaunchKernelGGL(k_npt_move, dim3((unsigned)(((long long)nrows + 255) / 256)), dim3(256), 0, s, natoms, nrows, st, p.md, m.q_x[in].as<double>(), m.q_vnow.as<double>(), f,
+                       mass, fixed, m.r_xhold.as<double>(), m.c_src.as<long long>(), m.r_img.as<int>(), m.q_x[in ^ 1].as<double>(), m.q_v[in ^ 1].as<double>(),
+                       m.c_x.as<double>(), m.r_disp.as<int>());
+  AHIP_CHECK(hipGetLastError());
+}
+NptState npt_read(Model &m, hipStream_t s) {
+  AHIP_CHECK(hipStreamSynchronize(s));
+  AHIP_CHECK(hipGetLastError());
+  NptState st;
+  copy_d2h(&st, m.q_nstate.p, sizeof(st));
+  return st;
+}
+// behind a rebuild in the cell st.geom.h: the hold the criterion is taken against from now on, status RUNNING.  The stream is idle (the caller has read st).
+void npt_held(Model &m, NptState st, hipStream_t s) {
+  AHIP_CHECK(hipStreamSynchronize(s));
+  for (int k = 0; k < 9; ++k) st.hold_cell[k] = m.hold.cell[k];
+  for (int d = 0; d < 3; ++d) st.hold_images[d] = m.hold.images[d];
+  st.hold_min_height = m.hold.min_height;
+  st.status = MD_RUNNING;
+  copy_h2d(m.q_nstate.p, &st, sizeof(st));
+}
+void npt_resume(Model &m, hipStream_t s) {
+  const int running = MD_RUNNING;
+  AHIP_CHECK(hipStreamSynchronize(s));
+  copy_h2d(&m.q_nstate.as<NptState>()->status, &running, sizeof(int));
+}
+void npt_noise(unsigned long long seed, unsigned long long step, double *out_dev, hipStream_t s) {
+  hipLaunchKernelGGL(k_npt_noise, dim3(1), dim3(64), 0, s, seed, step, out_dev);
+  AHIP_CHECK(hipGetLastError());
+}
+
 // ---- a batch of cells as ONE non-periodic cloud (ahip_compute_cells) ----
 // Every structure keeps its own frame for the wrap and for its ghost images; only before the list build is every row (atom or ghost) translated by its
 // structure's origin, chosen on the host so that rows of different structures are farther apart than the list cutoff.  Behind that the batch is one list of
